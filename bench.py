@@ -14,10 +14,17 @@ synthetic 256x256 image pairs, 8 GRU iterations, fp32, seeded random weights of 
 architecture (no dataset / checkpoint is reachable).  Inputs are resident in HBM before the
 timed region.  Metric (BASELINE.json): image pairs per second, whole job (all GPUs).
 
-Timing: W warm-up steps (and at least ``--min-warmup-seconds``), then BLOCKS of exactly K steps,
-each bracketed by barrier + synchronize on both sides and reduced with MAX over ranks, repeated
-until ``--min-seconds`` (default 3 s) of timed work have run; ``value`` / ``ms_per_step`` come
-from the MEDIAN block, ``spread`` carries min / max.
+Timing: W warm-up steps (and at least ``--min-warmup-seconds``, untimed), then ONE block of exactly K
+timed steps, bracketed by barrier + synchronize on both sides and reduced with MAX over ranks.
+``--min-seconds S`` > 0 (opt-in) repeats such blocks until S seconds of timed work have run;
+``value`` / ``ms_per_step`` then come from the MEDIAN block, ``timing`` carries min / max.
+
+``--dump-outputs DIR``: rank 0 writes what the timed path returned in its last timed step --
+the seven per-iteration lists of ``get_pose``, each stacked into one array with a leading
+iteration axis -- as ``DIR/<name>.npy`` (float32).  An array of more than DUMP_MAX_ELEMS
+elements is replaced by a fixed sample of its flattened values (positions drawn once by
+``numpy.random.default_rng(0)`` from the array's size, sorted), so that the files stay under
+64 MB in all.  Inputs and weights are seeded: the same arguments give the same inputs.
 
 Extra objects on the JSON line:
   roofline      corr-lookup kernel: algorithmic bytes per launch (2904 B/query) /
@@ -84,8 +91,9 @@ def parse_args(argv=None):
     ap.add_argument('--warmup', type=int, default=3)
     ap.add_argument('--batch', type=int, default=32, help='image pairs per GPU per step')
     ap.add_argument('--iters', type=int, default=8)
-    ap.add_argument('--min-seconds', type=float, default=3.0,
-                    help='repeat blocks of --steps steps until this much timed work has run')
+    ap.add_argument('--min-seconds', type=float, default=0.0,
+                    help='repeat blocks of --steps steps until this much timed work has run (default: one block, '
+                         'i.e. exactly --steps timed steps)')
     ap.add_argument('--min-warmup-seconds', type=float, default=1.0)
     ap.add_argument('--conv-algo', choices=['winograd', 'direct'], default='winograd',
                     help="fp32 3x3 stride-1 layers: 'winograd' = F(2x2,3x3) kernel on large grids (default), "
@@ -110,6 +118,9 @@ def parse_args(argv=None):
                          'line is marked "share_device": true and is NOT a scaling measurement')
     ap.add_argument('--dump-poses', default=None,
                     help='rank 0 writes the gathered final poses of one extra step (torch.save) here')
+    ap.add_argument('--dump-outputs', default=None, metavar='DIR',
+                    help="rank 0 writes the outputs of the last timed step as DIR/<name>.npy (float32; arrays above "
+                         "2**20 elements as a fixed seeded sample), for output-by-output comparison of builds")
     ap.add_argument('--standin', action='store_true',
                     help='launcher self-test (tests/test_bench_launcher.py): the step is a CPU '
                          'stand-in, backend gloo; the line is marked "standin": true and is not a '
@@ -147,6 +158,35 @@ def maybe_self_launch(args) -> None:
 
 
 # ------------------------------------------------------------------ workload
+GET_POSE_OUTPUTS = ('flow_from_pose', 'flow_from_pred', 'rotation_preds', 'translation_preds', 'mask_preds',
+                    'delta_rotation_preds', 'delta_translation_preds')
+DUMP_MAX_ELEMS = 1 << 20        # per array: 4 MiB of float32; 7 arrays (+ 2 gathered poses with --gpus N) stay under 64 MB
+
+
+def dump_outputs(out_dir: str, arrays) -> dict:
+    """``arrays``: name -> tensor (or list of per-iteration tensors, stacked here).  Writes
+    ``out_dir/<name>.npy`` in float32 and returns name -> what was written."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    index = {}
+    for name, val in arrays.items():
+        if isinstance(val, (list, tuple)):
+            val = [v for v in val if v is not None]
+            if not val:
+                continue
+            val = torch.stack([v.detach() for v in val])
+        a = val.detach().float().cpu().numpy()
+        entry = {'shape': list(a.shape)}
+        if a.size > DUMP_MAX_ELEMS:
+            pos = np.sort(np.random.default_rng(0).choice(a.size, DUMP_MAX_ELEMS, replace=False))
+            a = a.reshape(-1)[pos]
+            entry['sample'] = f'{DUMP_MAX_ELEMS} of {int(np.prod(entry["shape"]))} values, default_rng(0)'
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, dtype=np.float32))
+        index[name] = entry
+    return index
+
+
 def build_model(iters: int, device: str):
     import scflow_amd
     shapes = json.load(open(os.path.join(ROOT, 'tests', 'golden', 'state_dict_keys.json')))['shapes']
@@ -435,6 +475,7 @@ def main():
         rank_map = [{'rank': 0, 'local_rank': local, 'device': device, 'name': dev_name,
                      'pid': os.getpid()}]
 
+    last_out = {}       # --dump-outputs: what the most recent step returned
     if standin:
         model = sd = None
         g = torch.Generator().manual_seed(rank)
@@ -446,6 +487,8 @@ def main():
             trans = y[:, 0, :3].contiguous()
             if world > 1:
                 rot, trans = gather_poses(rot, trans, args.batch * world)
+            if args.dump_outputs:
+                last_out.update(rotation=rot, translation=trans)
             return rot, trans
     else:
         model, sd = build_model(args.iters, device)
@@ -456,6 +499,10 @@ def main():
             rot, trans = outs[2][-1], outs[3][-1]
             if world > 1:
                 rot, trans = gather_poses(rot, trans, args.batch * world)
+            if args.dump_outputs:
+                last_out.update(zip(GET_POSE_OUTPUTS, outs))
+                if world > 1:
+                    last_out.update(gathered_rotation=rot, gathered_translation=trans)
             return rot, trans
 
     def sync():
@@ -507,6 +554,12 @@ def main():
 
     blocks, lookup_us, warm_done = timed(args.precision, corr_us)
     dt = _median(blocks)
+    dumped = None
+    if args.dump_outputs:       # before any further (untimed) step replaces them
+        sync()
+        if rank == 0:
+            dumped = dump_outputs(args.dump_outputs, last_out)
+        last_out.clear()
 
     result = None
     conv_launches, cb_us, cb_ev = None, None, []
@@ -581,7 +634,7 @@ def main():
                        'batch_per_gpu': args.batch, 'global_batch': args.batch * world,
                        'height': 256, 'width': 256, 'iters': args.iters,
                        'parallelism': f'batch-split x{world}, no data-path collective'},
-            'timing': {'blocks': len(blocks), 'steps_per_block': args.steps,
+            'timing': {'blocks': len(blocks), 'steps_per_block': args.steps, 'timed_steps': len(blocks) * args.steps,
                        'timed_seconds': round(sum(blocks), 3), 'warmup_steps_run': warm_done,
                        'ms_per_step_median': round(dt / args.steps * 1e3, 3),
                        'ms_per_step_min': round(min(blocks) / args.steps * 1e3, 3),
@@ -590,6 +643,8 @@ def main():
                                'synchronize on both sides, max over ranks per block)'},
             'ranks': rank_map, 'collective_world_size': coll_world,
         }
+        if dumped is not None:
+            result['dumped_outputs'] = {'dir': args.dump_outputs, 'arrays': dumped}
         if standin:
             result['standin'] = True
             result['metric'] = 'LAUNCHER SELF-TEST (CPU stand-in step, not a measurement)'

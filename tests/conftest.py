@@ -1,7 +1,13 @@
 import os
 import sys
 
-import pytest
+# MKL picks its kernels by CPU vendor and ISA (an AVX-512 path on one host, its generic path on another), so the CPU
+# oracle's fp32 sums -- compared with the golden fixtures bit for bit or within 2e-6 -- would depend on the host.  The
+# suite runs on MKL's vendor-independent path, the one tests/golden/make_golden.py generates the fixtures on; it must
+# be set before MKL's first call.
+os.environ.setdefault('MKL_CBWR', 'COMPATIBLE')
+
+import pytest  # noqa: E402
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:

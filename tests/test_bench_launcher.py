@@ -6,6 +6,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -70,3 +72,53 @@ def test_counter_summaries_are_bound_to_the_kernel_sources():
         d = json.load(open(p))
         ok, why = bench._fresh(d, bench.LOOKUP_SOURCES)
         assert ok or why
+
+
+def test_bench_times_exactly_steps_and_dumps_outputs(tmp_path):
+    """--steps K is the number of timed steps (one block by default); --dump-outputs writes the last timed step's
+    outputs as float32 .npy, and the same arguments give the same files."""
+    import numpy as np
+    dumps = []
+    for run in range(2):
+        d = os.path.join(tmp_path, f'run{run}')
+        r = _run(['--gpus', '1', '--steps', '3', '--warmup', '1', '--batch', '4', '--standin',
+                  '--min-warmup-seconds', '0', '--dump-outputs', d])
+        assert r.returncode == 0, r.stderr[-2000:]
+        out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+        assert out['steps'] == 3 and out['timing']['blocks'] == 1 and out['timing']['timed_steps'] == 3
+        assert out['timing']['warmup_steps_run'] == 1
+        assert set(out['dumped_outputs']['arrays']) == {'rotation', 'translation'}
+        dumps.append({n: np.load(os.path.join(d, n + '.npy')) for n in ('rotation', 'translation')})
+    assert dumps[0]['rotation'].shape == (4, 3, 3) and dumps[0]['translation'].shape == (4, 3)
+    for n, a in dumps[0].items():
+        assert a.dtype == np.float32 and np.array_equal(a, dumps[1][n])
+
+
+@pytest.mark.gpu
+def test_bench_dump_outputs_are_the_timed_step(tmp_path):
+    """the dumped arrays are get_pose's outputs on bench.py's seeded batch (rank 0: seed 1000), bit for bit."""
+    import numpy as np
+    import torch
+    sys.path.insert(0, ROOT)
+    import bench
+    d = os.path.join(tmp_path, 'dump')
+    r = _run(['--gpus', '1', '--steps', '2', '--warmup', '1', '--batch', '4', '--min-warmup-seconds', '0',
+              '--no-batch1', '--no-config4', '--no-cpu-baseline', '--dump-outputs', d], timeout=600)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
+    assert out['timing']['timed_steps'] == 2
+    arrays = out['dumped_outputs']['arrays']
+    assert set(arrays) == set(bench.GET_POSE_OUTPUTS)
+    model, _ = bench.build_model(8, 'cuda:0')
+    outs = bench.run_step(model, bench.make_batch(4, 1000, 'cuda:0'))
+    total = 0
+    for name, val in zip(bench.GET_POSE_OUTPUTS, outs):
+        want = torch.stack([v for v in val]).float().cpu().numpy()
+        got = np.load(os.path.join(d, name + '.npy'))
+        total += got.nbytes
+        assert got.dtype == np.float32 and list(want.shape) == arrays[name]['shape']
+        if 'sample' in arrays[name]:
+            pos = np.sort(np.random.default_rng(0).choice(want.size, bench.DUMP_MAX_ELEMS, replace=False))
+            want = want.reshape(-1)[pos]
+        assert np.array_equal(got, want), name
+    assert total <= 64e6

@@ -1,7 +1,8 @@
 """The mini-mmcv used to generate the conv-stack fixtures is 'mmcv 1.3.16 restated'.  Its
 assumptions are written down in tests/golden/MMCV_SHIM_AUDIT.md; this test keeps that table honest:
 every call the reference makes into the mmcv factories on the hot-path files (found by AST), and
-every keyword it passes, must appear in the audit.  Runs only where /root/reference exists."""
+every keyword it passes, must appear in the audit.  The call-site check runs only where the reference checkout
+exists; the check of the shim's own behaviour runs everywhere."""
 import ast
 import os
 import re
@@ -15,8 +16,6 @@ FILES = ['models/decoder/raft_decoder.py', 'models/decoder/scflow_decoder.py',
 APIS = {'ConvModule', 'build_norm_layer', 'build_conv_layer', 'build_activation_layer',
         'build_plugin_layer'}
 AUDIT = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'MMCV_SHIM_AUDIT.md')
-
-pytestmark = pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present')
 
 
 def _call_sites():
@@ -55,6 +54,7 @@ def _audited():
     return lines, kwargs
 
 
+@pytest.mark.skipif(not os.path.isdir(REF), reason='reference checkout not present')
 def test_every_mmcv_call_site_and_kwarg_is_audited():
     sites = _call_sites()
     assert len(sites) >= 30
