@@ -54,6 +54,7 @@ typedef struct scf_conv_log_entry {
   int32_t kernel;             /* SCF_KERNEL_*                                                      */
   int32_t Cin, Cout, KH, KW, stride, Ho, Wo, N;
   int32_t mode;               /* SCF_CONV_*                                                        */
+  int32_t paired;             /* scf_conv2d_pair: 0 = its own launch, 1 / 2 = first / second layer of one merged launch */
 } scf_conv_log_entry;
 int scf_conv_log_enable(int capacity);
 /* measurement knobs (A/B runs of kernel variants from bench.py / tools): returns the previous value, or

@@ -583,83 +583,87 @@ static bool kws_lookup(hipStream_t st, float** ptr, int64_t* floats) {
   return false;
 }
 
-// which kernel family took the launch (SCF_KERNEL_* of scflow_hip_prof.h)
-static int conv2d_launch(const scf_conv_desc* d, scf_stream_t stream, int* which) {
+// what conv2d_walk does with the family that takes a descriptor: launch it (neither pointer set), report its tile
+// selection (info: a dry run without a stream, scf_conv2d_query) or hand its launch back (cap: scf_conv2d_pair)
+struct ConvReq {
+  int32_t* info = nullptr;
+  ScfLaunchCap* cap = nullptr;
+  int which = 0;      // out: the family that took the descriptor (SCF_KERNEL_* of scflow_hip_prof.h)
+};
+
+// THE family order of a convolution, for launch, query and capture alike: a family answers SCF_EUNSUPPORTED (the next one
+// is asked) or ends the walk with its own code
+static int conv2d_walk(const scf_conv_desc* d, scf_stream_t stream, ConvReq& r) {
   ConvPlan pl;
   const int rc = conv_plan(d, &pl);
   if (rc != SCF_OK) return rc;
+  const ConvK& k = pl.k;
+  const int N = d->N;
+  const bool dry = r.info || r.cap;
+  int32_t scratch[4];
+  int32_t* info = r.info ? r.info : r.cap ? scratch : nullptr;
+  hipStream_t st = scf_stream(stream);
+  int out = SCF_EUNSUPPORTED;
+  auto took = [&](int which, int rf) { r.which = which; out = rf; return rf != SCF_EUNSUPPORTED; };
   if (d->k_slices > 1) {        // only the LDS-DMA kernel splits K across blocks
-    *which = SCF_KERNEL_DMA;
-    if (!want_dma(d)) return SCF_EUNSUPPORTED;
-    return scf_conv_dma_dispatch(pl.k, d->N, false, nullptr, scf_stream(stream));
+    r.which = SCF_KERNEL_DMA;
+    return want_dma(d) ? scf_conv_dma_dispatch(k, N, dry, info, st, r.cap) : SCF_EUNSUPPORTED;
   }
-  {
-    *which = SCF_KERNEL_THIN;
-    const int rt = scf_conv_thin_dispatch(pl.k, d->N, false, scf_stream(stream));
-    if (rt != SCF_EUNSUPPORTED) return rt;
-  }
-  if (d->wp_taps) {
-    *which = SCF_KERNEL_TAPS;
-    const int rp = scf_conv_taps_dispatch(pl.k, d->wp_taps, d->N, false, nullptr, scf_stream(stream));
-    if (rp != SCF_EUNSUPPORTED) return rp;
-  }
+  if (took(SCF_KERNEL_THIN, scf_conv_thin_dispatch(k, N, dry, st, r.cap))) return out;
+  if (d->wp_taps && took(SCF_KERNEL_TAPS, scf_conv_taps_dispatch(k, d->wp_taps, N, dry, info, st, r.cap))) return out;
   if (d->wp_wino) {
     int quarter = 0;
-    const int rw = scf_conv_wino_dispatch(pl.k, d->wp_wino, d->N, false, nullptr, scf_stream(stream), &quarter);
-    *which = quarter ? SCF_KERNEL_WINO_Q : SCF_KERNEL_WINO;
-    if (rw != SCF_EUNSUPPORTED) return rw;
+    const int rw = scf_conv_wino_dispatch(k, d->wp_wino, N, dry, info, st, &quarter, r.cap);
+    if (took(quarter ? SCF_KERNEL_WINO_Q : SCF_KERNEL_WINO, rw)) return out;
   }
-  if (d->wp_wino1d4 && g_wino1d4.load(std::memory_order_relaxed)) {
-    *which = SCF_KERNEL_WINO1D4;
-    const int rw = scf_conv_wino1d4_dispatch(pl.k, d->wp_wino1d4, d->N, g_wino1d4.load(std::memory_order_relaxed) == 2, false, nullptr, scf_stream(stream));
-    if (rw != SCF_EUNSUPPORTED) return rw;
-  }
-  if (d->wp_wino1d) {
-    *which = SCF_KERNEL_WINO1D;
-    const int rw = scf_conv_wino1d_dispatch(pl.k, d->wp_wino1d, d->N, false, nullptr, scf_stream(stream));
-    if (rw != SCF_EUNSUPPORTED) return rw;
-  }
-  if (want_f16x3(d)) {
-    *which = SCF_KERNEL_F16X3;
-    const int r16 = scf_conv_f16x3_dispatch(pl.k, d->N, false, nullptr, scf_stream(stream));
-    if (r16 != SCF_EUNSUPPORTED) return r16;
-  }
+  const int w4 = g_wino1d4.load(std::memory_order_relaxed);
+  if (d->wp_wino1d4 && w4 && took(SCF_KERNEL_WINO1D4, scf_conv_wino1d4_dispatch(k, d->wp_wino1d4, N, w4 == 2, dry, info, st)))
+    return out;
+  if (d->wp_wino1d && took(SCF_KERNEL_WINO1D, scf_conv_wino1d_dispatch(k, d->wp_wino1d, N, dry, info, st))) return out;
+  if (want_f16x3(d) && took(SCF_KERNEL_F16X3, scf_conv_f16x3_dispatch(k, N, dry, info, st))) return out;
   if (want_dma(d)) {
-    *which = SCF_KERNEL_DMA;
-    // small-grid launch with a workspace on its stream: S slices into the workspace + the combine launch (conv_dma.hip)
+    // small-grid launch with a workspace on its stream: S slices into the workspace + the combine launch (conv_dma.hip).
+    // A capture of a layer on such a stream is not pairable, whether or not its launch would slice; a query has no stream.
     float* ws = nullptr;
     int64_t ws_floats = 0;
-    if (g_autoslice.load(std::memory_order_relaxed) && d->k_slices <= 1 && kws_lookup(scf_stream(stream), &ws, &ws_floats)) {
-      const int S = scf_conv_dma_autoslice(pl.k, d->N);
-      const int64_t per_slice = (int64_t)d->N * d->Cout * pl.k.Ho * pl.k.Wo;
+    const bool sliced = !r.info && g_autoslice.load(std::memory_order_relaxed) && kws_lookup(st, &ws, &ws_floats);
+    if (sliced && !dry) {
+      const int S = scf_conv_dma_autoslice(k, N);
+      const int64_t per_slice = (int64_t)N * d->Cout * k.Ho * k.Wo;
       if (S > 1 && per_slice * S <= ws_floats) {
-        ConvK part = pl.k;
-        part.out = ws; part.out_ns = (long long)d->Cout * pl.k.Ho * pl.k.Wo;
+        ConvK part = k;
+        part.out = ws; part.out_ns = (long long)d->Cout * k.Ho * k.Wo;
         part.bias = nullptr; part.scale = nullptr; part.shift = nullptr; part.res = nullptr; part.res_ns = 0;
         part.out_div = 1.f; part.out_div_pow2 = 1; part.act = SCF_ACT_NONE; part.act2 = SCF_ACT_NONE; part.act_split = 0;
         part.mode = SCF_CONV_PLAIN; part.gru_h = nullptr; part.gru_aux = nullptr; part.gru_z = nullptr;
         part.kslices = S; part.slice_ns = per_slice;
-        const int rs = scf_conv_dma_dispatch(part, d->N, false, nullptr, scf_stream(stream));
-        if (rs == SCF_OK) return scf_conv_kcombine_launch(pl.k, ws, S, per_slice, d->N, scf_stream(stream));
+        r.which = SCF_KERNEL_DMA;
+        const int rs = scf_conv_dma_dispatch(part, N, false, nullptr, st);
+        if (rs == SCF_OK) return scf_conv_kcombine_launch(k, ws, S, per_slice, N, st);
         if (rs != SCF_EUNSUPPORTED) return rs;
       }
     }
-    const int rd = scf_conv_dma_dispatch(pl.k, d->N, false, nullptr, scf_stream(stream));
-    if (rd != SCF_EUNSUPPORTED) return rd;
+    if (took(SCF_KERNEL_DMA, scf_conv_dma_dispatch(k, N, dry, info, st, r.cap))) {
+      if (sliced && r.cap) r.cap->variant = -1;
+      return out;
+    }
   }
-  const ConvK& k = pl.k;
+  r.which = k.ksplit ? SCF_KERNEL_MFMA_KSPLIT : SCF_KERNEL_MFMA;
   const int WM = pl.WM, WN = pl.WN;
-  const long long nblk = pl.nblk;
-  const size_t lds_bytes = pl.lds_bytes;
-  hipStream_t st = scf_stream(stream);
-  if (k.ksplit) {
-    *which = SCF_KERNEL_MFMA_KSPLIT;
-    if (k.KC == 32) return launch_ksplit<32>(k, (int)nblk, lds_bytes, st);
-    if (k.KC == 8) return launch_ksplit<8>(k, (int)nblk, lds_bytes, st);
-    return launch_ksplit<2>(k, (int)nblk, lds_bytes, st);
+  if (dry) {
+    if (r.info) {
+      r.info[0] = WM; r.info[1] = WN; r.info[2] = (int32_t)pl.nblk;
+      r.info[3] = k.T * (k.KC / 2) * WM * WN / (k.ksplit ? 4 : 1);
+    }
+    return SCF_OK;
   }
-  *which = SCF_KERNEL_MFMA;
-#define SCF_CASE(M, Nn) if (WM == M && WN == Nn) return launch_conv<M, Nn>(k, (int)nblk, lds_bytes, st);
+  const int nblk = (int)pl.nblk;
+  if (k.ksplit) {
+    if (k.KC == 32) return launch_ksplit<32>(k, nblk, pl.lds_bytes, st);
+    if (k.KC == 8) return launch_ksplit<8>(k, nblk, pl.lds_bytes, st);
+    return launch_ksplit<2>(k, nblk, pl.lds_bytes, st);
+  }
+#define SCF_CASE(M, Nn) if (WM == M && WN == Nn) return launch_conv<M, Nn>(k, nblk, pl.lds_bytes, st);
   SCF_CASE(1, 1) SCF_CASE(1, 2) SCF_CASE(2, 1) SCF_CASE(2, 2)
   SCF_CASE(3, 1) SCF_CASE(4, 1)
 #undef SCF_CASE
@@ -722,20 +726,15 @@ extern "C" int scf_conv_log_read(scf_conv_log_entry* out, int max_entries) {
   return n;
 }
 
-static void conv_log_push(const scf_conv_desc* d, int which);
+static void conv_log_push(const scf_conv_desc* d, int which, int paired);
 extern "C" int scf_conv2d(const scf_conv_desc* d, scf_stream_t stream) {
-  int which = 0;
-  const int rc = conv2d_launch(d, stream, &which);
-  if (rc == SCF_OK) conv_log_push(d, which);
+  ConvReq r;
+  const int rc = conv2d_walk(d, stream, r);
+  if (rc == SCF_OK) conv_log_push(d, r.which, 0);
   return rc;
 }
 
-// ---------------------------------------------------------------------------------
-// r6: two INDEPENDENT convolutions as one launch where both fall to the same small-grid kernel instantiation (the K-split
-// LDS-DMA tile, the thin-input kernel): blocks [0, nA) run a, the rest b -- the branch-level concurrency of batch 1-4 without a
-// second stream (conv_dma_pair_kernel).  Anything else: the two launches one after the other.  Same results either way.
-// ---------------------------------------------------------------------------------
-static void conv_log_push(const scf_conv_desc* d, int which) {
+static void conv_log_push(const scf_conv_desc* d, int which, int paired) {
   if (g_log_cap.load(std::memory_order_relaxed) <= 0) return;
   std::lock_guard<std::mutex> lk(g_log_mu);
   if ((int)g_log.size() >= g_log_cap.load()) return;
@@ -743,96 +742,82 @@ static void conv_log_push(const scf_conv_desc* d, int which) {
   e.kernel = which; e.Cin = d->C0 + d->C1; e.Cout = d->Cout; e.KH = d->KH; e.KW = d->KW; e.stride = d->stride;
   e.Ho = (d->H + 2 * d->pad_h - d->KH) / d->stride + 1;
   e.Wo = (d->W + 2 * d->pad_w - d->KW) / d->stride + 1;
-  e.N = d->N; e.mode = d->mode;
+  e.N = d->N; e.mode = d->mode; e.paired = paired;
   g_log.push_back(e);
 }
 
-// the family that WOULD take d (same precedence as conv2d_launch) with its launch captured, or -1 when it is not a pairable one
-static int conv2d_capture(const scf_conv_desc* d, scf_stream_t stream, ScfLaunchCap* cap) {
-  ConvPlan pl;
-  if (conv_plan(d, &pl) != SCF_OK) return -1;
-  int32_t info[4];
-  if (d->k_slices > 1) {
-    if (!want_dma(d)) return -1;
-    return (scf_conv_dma_dispatch(pl.k, d->N, true, info, nullptr, cap) == SCF_OK && cap->variant >= 0) ? SCF_KERNEL_DMA : -1;
+// ---------------------------------------------------------------------------------
+// r6: two INDEPENDENT convolutions as one launch where both fall to the same small-grid kernel instantiation (the K-split
+// LDS-DMA tile, the thin-input kernel): blocks [0, nA) run a, the rest b -- the branch-level concurrency of batch 1-4 without a
+// second stream (conv_dma_pair_kernel).  Anything else: the two launches one after the other.  Same results either way.
+// ---------------------------------------------------------------------------------
+// the captured launch is an instantiation one of the pair launchers takes
+static bool pairable(int which, const ScfLaunchCap& c) {
+  switch (which) {
+    case SCF_KERNEL_THIN: return true;
+    case SCF_KERNEL_TAPS: return c.variant >= 1;
+    case SCF_KERNEL_WINO_Q: return c.variant >= 10 && c.variant < 20;
+    case SCF_KERNEL_WINO: return c.variant >= 20;
+    case SCF_KERNEL_DMA: return c.variant >= 0;
+    default: return false;      // F(4, 5), F(2, 5), split-fp16, the register-staged kernels
   }
-  if (scf_conv_thin_dispatch(pl.k, d->N, true, nullptr, cap) == SCF_OK) return SCF_KERNEL_THIN;
-  if (d->wp_taps) {
-    const int rp = scf_conv_taps_dispatch(pl.k, d->wp_taps, d->N, true, info, nullptr, cap);
-    if (rp == SCF_OK) return cap->variant >= 1 ? SCF_KERNEL_TAPS : -1;
-    if (rp != SCF_EUNSUPPORTED) return -1;
-  }
-  if (d->wp_wino) {
-    int quarter = 0;
-    if (scf_conv_wino_dispatch(pl.k, d->wp_wino, d->N, true, info, nullptr, &quarter, cap) == SCF_OK)
-      return (quarter && cap->variant >= 10 && cap->variant < 20) ? SCF_KERNEL_WINO_Q : (!quarter && cap->variant >= 20) ? SCF_KERNEL_WINO : -1;
-  }
-  if (d->wp_wino1d4 && g_wino1d4.load(std::memory_order_relaxed) &&
-      scf_conv_wino1d4_dispatch(pl.k, d->wp_wino1d4, d->N, g_wino1d4.load(std::memory_order_relaxed) == 2, true, info, nullptr) == SCF_OK)
-    return -1;
-  if (d->wp_wino1d && scf_conv_wino1d_dispatch(pl.k, d->wp_wino1d, d->N, true, info, nullptr) == SCF_OK) return -1;
-  if (want_f16x3(d) && scf_conv_f16x3_dispatch(pl.k, d->N, true, info, nullptr) == SCF_OK) return -1;
-  if (want_dma(d)) {
-    float* ws = nullptr;
-    int64_t ws_floats = 0;
-    if (g_autoslice.load(std::memory_order_relaxed) && kws_lookup(scf_stream(stream), &ws, &ws_floats)) return -1;
-    if (scf_conv_dma_dispatch(pl.k, d->N, true, info, nullptr, cap) == SCF_OK) return cap->variant >= 0 ? SCF_KERNEL_DMA : -1;
-  }
-  return -1;
 }
+
+static bool capture(const scf_conv_desc* d, scf_stream_t stream, ScfLaunchCap* cap, int* which) {
+  ConvReq r;
+  r.cap = cap;
+  const bool ok = conv2d_walk(d, stream, r) == SCF_OK && pairable(r.which, *cap);
+  *which = r.which;
+  return ok;
+}
+
+typedef int (*PairLaunch)(const ScfLaunchCap&, const ScfLaunchCap&, hipStream_t);
 
 extern "C" int scf_conv2d_pair(const scf_conv_desc* a, const scf_conv_desc* b, scf_stream_t stream) {
   if (!a || !b) return SCF_EINVAL;
   ScfLaunchCap ca, cb;
-  const int fa = conv2d_capture(a, stream, &ca);
-  if (fa >= 0) {
-    const int fb = conv2d_capture(b, stream, &cb);
-    // one launch only while both grids are resident together: past that the merged launch is a second round of blocks and
-    // loses (batch 2, corr1 384 + flow1 128 blocks of 100+ KB: +11 us per pair, profiles/r6_b1_pairs.txt)
-    // blocks that can be resident at once: thin-input and quarter-domain Winograd blocks fit two per CU, K-split blocks too while
-    // their ring stays under half the LDS (the 32-channel-chunk packing of tiny grids takes up to 144 KB: one per CU)
+  int fa = 0, fb = 0;
+  // scf_tune(SCF_TUNE_CONV_PAIR, 1): never one launch
+  if (g_pair_mode.load(std::memory_order_relaxed) != 1 && capture(a, stream, &ca, &fa) && capture(b, stream, &cb, &fb)) {
+    // one launch while both grids are resident together: past that the merged launch is a second round of blocks and loses
+    // (batch 2, corr1 384 + flow1 128 blocks of 100+ KB: +11 us per pair, profiles/r6_b1_pairs.txt).  Blocks resident at once:
+    // thin-input and quarter-domain Winograd blocks fit two per CU, K-split blocks too while their ring stays under half the
+    // LDS (the 32-channel-chunk packing of tiny grids takes up to 144 KB: one per CU)
     const size_t lmax = ca.ldsb > cb.ldsb ? ca.ldsb : cb.ldsb;
-    long long slots = (long long)scf_cu_count() * (((fa == SCF_KERNEL_DMA || fb == SCF_KERNEL_DMA) && lmax > 80 * 1024) ? 1 : 2);
-    if (g_pair_mode.load(std::memory_order_relaxed) == 1) slots = 0;      // scf_tune(SCF_TUNE_CONV_PAIR, 1): never one launch
-    if (((fa == SCF_KERNEL_DMA && fb == SCF_KERNEL_TAPS) || (fa == SCF_KERNEL_TAPS && fb == SCF_KERNEL_DMA)) &&
-        (long long)ca.nblk + cb.nblk <= slots && g_pair_mode.load(std::memory_order_relaxed) != 1) {
-      // a K-split layer beside a thin-input layer (corr_net.0 | flow_net.0): one launch, the K-split grid first
-      const bool a_dma = fa == SCF_KERNEL_DMA;
-      const int rc = scf_conv_dma_taps_pair_launch(a_dma ? ca : cb, a_dma ? cb : ca, scf_stream(stream));
-      if (rc == SCF_OK) {
-        conv_log_push(a, fa);
-        conv_log_push(b, fb);
-        return SCF_OK;
+    const long long slots = (long long)scf_cu_count() * (((fa == SCF_KERNEL_DMA || fb == SCF_KERNEL_DMA) && lmax > 80 * 1024) ? 1 : 2);
+    const long long na = ca.nblk, nb = cb.nblk;
+    auto rounds = [](long long n, long long s) { return (n + s - 1) / s; };
+    auto fewer_rounds = [&](long long s) { return rounds(na + nb, s) < rounds(na, s) + rounds(nb, s); };
+    const bool fits = na + nb <= slots;
+    // the launcher of the two families (swap: b's grid goes first) and whether one launch pays
+    PairLaunch launch = nullptr;
+    bool swap = false, pays = fits;
+    if ((fa == SCF_KERNEL_DMA && fb == SCF_KERNEL_TAPS) || (fa == SCF_KERNEL_TAPS && fb == SCF_KERNEL_DMA)) {
+      // a K-split layer beside a thin-input layer (corr_net.0 | flow_net.0): the K-split grid first
+      launch = scf_conv_dma_taps_pair_launch;
+      swap = fb == SCF_KERNEL_DMA;
+    } else if ((fa == SCF_KERNEL_WINO_Q && fb == SCF_KERNEL_WINO) || (fa == SCF_KERNEL_WINO && fb == SCF_KERNEL_WINO_Q)) {
+      // a quarter-domain layer beside a pair-kernel layer (delta_flow_encoder.1 | mask_encoder.1): the quarter-domain grid
+      // first.  The MFMA-bound Winograd kernels also merge while one launch needs fewer ROUNDS of resident blocks than two
+      // (batch 32: corr_net.1 768 + flow_net.1 256 blocks = 1.5 + 0.5 rounds apart, 2 full rounds together)
+      launch = scf_conv_wino_pair_launch;
+      swap = fb == SCF_KERNEL_WINO_Q;
+      pays = fits || fewer_rounds(slots);
+    } else if (fa == fb) {
+      switch (fa) {
+        case SCF_KERNEL_WINO_Q: launch = scf_conv_wino_pair_launch; pays = fits || fewer_rounds(slots); break;
+        // thin-input blocks are light -- ~30 KB of LDS, ~100 registers -- four are resident per CU
+        case SCF_KERNEL_TAPS: launch = scf_conv_taps_pair_launch; pays = fits || fewer_rounds(2 * slots); break;
+        case SCF_KERNEL_THIN: launch = scf_conv_thin_pair_launch; break;
+        case SCF_KERNEL_DMA: launch = scf_conv_dma_pair_launch; break;
+        default: break;
       }
-      if (rc != SCF_EUNSUPPORTED) return rc;
     }
-    // ... or, for the MFMA-bound quarter-domain Winograd kernel, while one launch needs fewer ROUNDS of resident blocks than two
-    // (batch 32: corr_net.1 768 + flow_net.1 256 blocks = 1.5 + 0.5 rounds apart, 2 full rounds together)
-    // (thin-input blocks are light -- ~30 KB of LDS, ~100 registers -- four are resident per CU)
-    const long long rslots = fa == SCF_KERNEL_TAPS ? 2 * slots : slots;
-    const bool fewer_rounds = (fa == SCF_KERNEL_WINO_Q || fa == SCF_KERNEL_TAPS) && fb == fa && g_pair_mode.load(std::memory_order_relaxed) != 1 &&
-                              (ca.nblk + cb.nblk + rslots - 1) / rslots < (ca.nblk + rslots - 1) / rslots + (cb.nblk + rslots - 1) / rslots;
-    if (((fa == SCF_KERNEL_WINO_Q && fb == SCF_KERNEL_WINO) || (fa == SCF_KERNEL_WINO && fb == SCF_KERNEL_WINO_Q)) &&
-        g_pair_mode.load(std::memory_order_relaxed) != 1 &&
-        ((long long)ca.nblk + cb.nblk <= slots ||
-         (ca.nblk + cb.nblk + slots - 1) / slots < (ca.nblk + slots - 1) / slots + (cb.nblk + slots - 1) / slots)) {
-      // a quarter-domain layer beside a pair-kernel layer (delta_flow_encoder.1 | mask_encoder.1): the quarter-domain grid first
-      const bool a_q = fa == SCF_KERNEL_WINO_Q;
-      const int rc = scf_conv_wino_pair_launch(a_q ? ca : cb, a_q ? cb : ca, scf_stream(stream));
+    if (launch && pays) {
+      const int rc = swap ? launch(cb, ca, scf_stream(stream)) : launch(ca, cb, scf_stream(stream));
       if (rc == SCF_OK) {
-        conv_log_push(a, fa);
-        conv_log_push(b, fb);
-        return SCF_OK;
-      }
-      if (rc != SCF_EUNSUPPORTED) return rc;
-    }
-    if (fb == fa && fa != SCF_KERNEL_WINO && ((long long)ca.nblk + cb.nblk <= slots || fewer_rounds)) {
-      const int rc = fa == SCF_KERNEL_WINO_Q ? scf_conv_wino_pair_launch(ca, cb, scf_stream(stream))
-                   : fa == SCF_KERNEL_THIN ? scf_conv_thin_pair_launch(ca, cb, scf_stream(stream)) : fa == SCF_KERNEL_TAPS ? scf_conv_taps_pair_launch(ca, cb, scf_stream(stream))
-                                           : scf_conv_dma_pair_launch(ca, cb, scf_stream(stream));
-      if (rc == SCF_OK) {
-        conv_log_push(a, fa);
-        conv_log_push(b, fb);
+        conv_log_push(a, fa, 1);
+        conv_log_push(b, fb, 2);
         return SCF_OK;
       }
       if (rc != SCF_EUNSUPPORTED) return rc;
@@ -949,47 +934,12 @@ extern "C" int scf_sepconv_gru_ctx(float* hx, int64_t hx_nstride, int N, int Ch,
 // packings (KC = 8 vs 32) without launching.
 extern "C" int scf_conv2d_query(const scf_conv_desc* d, int32_t* info) {
   if (!info) return SCF_EINVAL;
-  ConvPlan pl;
-  const int rc = conv_plan(d, &pl);
+  ConvReq r;
+  r.info = info;
+  const int rc = conv2d_walk(d, nullptr, r);
   if (rc != SCF_OK) return rc;
-  if (d->k_slices > 1) {
-    if (!want_dma(d)) return SCF_EUNSUPPORTED;
-    const int rs = scf_conv_dma_dispatch(pl.k, d->N, true, info, nullptr);
-    if (rs == SCF_OK) info[3] = -info[3];
-    return rs;
-  }
-  if (scf_conv_thin_dispatch(pl.k, d->N, true, nullptr) == SCF_OK) {
-    info[0] = info[1] = 0; info[2] = 0; info[3] = -1;      // vector-ALU thin-output kernel
-    return SCF_OK;
-  }
-  if (d->wp_taps && scf_conv_taps_dispatch(pl.k, d->wp_taps, d->N, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: the thin-input kernel will run, KC of d is irrelevant
-    return SCF_OK;
-  }
-  if (d->wp_wino && scf_conv_wino_dispatch(pl.k, d->wp_wino, d->N, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: the Winograd kernel will run (info = 16 positions, fragments per block, blocks, -LDS bytes)
-    return SCF_OK;
-  }
-  if (d->wp_wino1d4 && g_wino1d4.load(std::memory_order_relaxed) &&
-      scf_conv_wino1d4_dispatch(pl.k, d->wp_wino1d4, d->N, g_wino1d4.load(std::memory_order_relaxed) == 2, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: the F(4, 5) kernel will run (info = 8 positions, 4 fragments per block, blocks, -LDS bytes)
-    return SCF_OK;
-  }
-  if (d->wp_wino1d && scf_conv_wino1d_dispatch(pl.k, d->wp_wino1d, d->N, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: the F(2, 5) kernel will run (info = 6 positions, 4 fragments per block, blocks, -LDS bytes)
-    return SCF_OK;
-  }
-  if (want_f16x3(d) && scf_conv_f16x3_dispatch(pl.k, d->N, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: the split-fp16 kernel will run
-    return SCF_OK;
-  }
-  if (want_dma(d) && scf_conv_dma_dispatch(pl.k, d->N, true, info, nullptr) == SCF_OK) {
-    info[3] = -info[3];      // negative: not the register-staged kernel, KC of d is irrelevant
-    return SCF_OK;
-  }
-  info[0] = pl.WM;
-  info[1] = pl.WN;
-  info[2] = (int32_t)pl.nblk;
-  info[3] = pl.k.T * (pl.k.KC / 2) * pl.WM * pl.WN / (pl.k.ksplit ? 4 : 1);
+  if (r.which == SCF_KERNEL_THIN) { info[0] = info[1] = info[2] = 0; info[3] = -1; }      // vector-ALU thin-output kernel
+  else if (r.which != SCF_KERNEL_MFMA && r.which != SCF_KERNEL_MFMA_KSPLIT)
+    info[3] = -info[3];      // negative: not the register-staged kernel, KC of d is irrelevant (info = that kernel's own)
   return SCF_OK;
 }

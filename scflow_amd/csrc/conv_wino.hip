@@ -865,6 +865,7 @@ int scf_conv_wino_dispatch(ConvK k, const float* wu, int N, bool dry_run, int* i
     const int npi = WQ_NPI(TW, px4), pslot = npi * 256 * TW * (px4 ? 4 : 1);
     const long long nblk = shape(2, TW, pslot);
     if (nblk > 0 && nblk * TW >= min_blocks4) {
+      if (which) *which = 1;
       size_t ldsf = (size_t)NR * (2 * 2048 + pslot);
       if (ldsf < (size_t)TW * 4 * 3072) ldsf = (size_t)TW * 4 * 3072;      // the output exchange reuses the rings
       const size_t ldsb = ldsf * sizeof(float);
@@ -874,7 +875,6 @@ int scf_conv_wino_dispatch(ConvK k, const float* wu, int N, bool dry_run, int* i
         cap->k = k; cap->nblk = (int)nblk; cap->ldsb = ldsb;
         memcpy(cap->aux, &q, sizeof(WinoK));
         cap->variant = (TW == 1 && NR == 3) ? 10 + cfg : -1;
-        if (which) *which = 1;
         return SCF_OK;
       }
       if (dry_run) return SCF_OK;
@@ -889,7 +889,6 @@ int scf_conv_wino_dispatch(ConvK k, const float* wu, int N, bool dry_run, int* i
         return scf_launch_status();
       }
 #endif
-      if (which) *which = 1;
 #ifdef SCF_WINO_LAB
       if (NR == 4 && burst) {
         static std::atomic<unsigned long long> raised_qb[2];

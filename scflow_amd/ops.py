@@ -869,12 +869,13 @@ class record_conv_kernels:
     launch order, INCLUDING those issued inside ``scf_sepconv_gru*`` / ``scf_scflow_iteration``
     (``scf_conv_log_*`` of scflow_hip_prof.h).  Tag = ``'<Cin>-><Cout> <KH>x<KW>/s<stride> @<Ho>x<Wo> N<N>'``
     (the tag ``conv_timing`` uses), family = one of ``_lib.KERNEL_NAMES``' values.  Parity tests assert with
-    it that the kernel they name really ran (the choice depends on grid size and device)."""
+    it that the kernel they name really ran (the choice depends on grid size and device).  The recorder's ``paired`` lists,
+    launch by launch, how ``scf_conv2d_pair`` ran it: 0 = its own launch, 1 / 2 = first / second layer of one merged launch."""
 
     _active = False      # the library keeps ONE process-wide log: a nested recorder would clear the outer one's records
 
     def __init__(self, capacity: int = 1 << 16) -> None:
-        self.capacity, self.ran = capacity, []
+        self.capacity, self.ran, self.paired = capacity, [], []
 
     def __enter__(self):
         if record_conv_kernels._active:
@@ -893,6 +894,7 @@ class record_conv_kernels:
         for e in buf[:n]:
             self.ran.append((f'{e.Cin}->{e.Cout} {e.KH}x{e.KW}/s{e.stride} @{e.Ho}x{e.Wo} N{e.N}',
                              _lib.KERNEL_NAMES.get(e.kernel, str(e.kernel))))
+            self.paired.append(e.paired)
         return False
 
 

@@ -1490,26 +1490,44 @@ PAIR_CASES = [
     ((1, 324, 256, (1, 1), (0, 0), (32, 32)), (1, 2, 128, (7, 7), (3, 3), (32, 32)), True),     # corr_net.0 | flow_net.0: K-split tile + thin-input kernel
     ((1, 2, 128, (7, 7), (3, 3), (32, 32)), (1, 128, 64, (3, 3), (1, 1), (32, 32)), True),      # the same two families, thin-input layer first
     ((1, 128, 64, (3, 3), (1, 1), (32, 32)), (1, 256, 2, (3, 3), (1, 1), (32, 32)), False),     # families without a shared launch (K-split | thin-output)
-    ((32, 128, 64, (3, 3), (1, 1), (32, 32)), (32, 64, 32, (3, 3), (1, 1), (32, 32)), False),   # full grids (Winograd)
+    ((32, 128, 64, (3, 3), (1, 1), (32, 32)), (32, 64, 32, (3, 3), (1, 1), (32, 32)), True),    # full grids: quarter-domain | pair-kernel Winograd, fewer rounds together
     ((3, 224, 128, (3, 3), (1, 1), (12, 20)), (2, 30, 40, (1, 5), (0, 2), (9, 33)), None),      # ragged shapes, whatever it does
 ]
 
 
 @pytest.mark.parametrize('case', PAIR_CASES)
 def test_conv2d_pair_equals_two_launches(case):
-    """scf_conv2d_pair == scf_conv2d(a); scf_conv2d(b) bit for bit, merged or not; the dispatch log names both layers."""
+    """scf_conv2d_pair == scf_conv2d(a); scf_conv2d(b) bit for bit, merged or not; the dispatch log names both layers, with
+    the families the two single launches took, and says whether they shared one launch (``merged``, where the case states
+    it); with tune('conv_pair', 1) nothing merges and the bits stay the same."""
     (na, cia, coa, ka, pa, hwa), (nb, cib, cob, kb, pb, hwb), merged = case
     xa, xb = rnd((na, cia, *hwa), 201).to(DEV), rnd((nb, cib, *hwb), 202).to(DEV)
     wa = rnd((coa, cia, *ka), 203, (1.0 / (cia * ka[0] * ka[1])) ** 0.5).to(DEV)
     wb = rnd((cob, cib, *kb), 204, (1.0 / (cib * kb[0] * kb[1])) ** 0.5).to(DEV)
     pca = ops.PackedConv.from_weight(wa, rnd((coa,), 205, 0.1).to(DEV), padding=pa)
     pcb = ops.PackedConv.from_weight(wb, rnd((cob,), 206, 0.1).to(DEV), padding=pb)
-    want_a = ops.conv2d(pca, xa, act=ops.ACT_RELU)
-    want_b = ops.conv2d(pcb, xb, act=ops.ACT_NONE)
-    with ops.record_conv_kernels() as ran:
+    with ops.record_conv_kernels() as single:
+        want_a = ops.conv2d(pca, xa, act=ops.ACT_RELU)
+        want_b = ops.conv2d(pcb, xb, act=ops.ACT_NONE)
+    rec = ops.record_conv_kernels()
+    with rec as ran:
         got_a, got_b = ops.conv2d_pair((pca, xa, dict(act=ops.ACT_RELU)), (pcb, xb, dict(act=ops.ACT_NONE)))
     torch.cuda.synchronize()
     assert torch.equal(got_a, want_a) and torch.equal(got_b, want_b)
     assert len(ran) == 2 and ran[0][0].startswith(f'{cia}->{coa}') and ran[1][0].startswith(f'{cib}->{cob}'), ran
+    assert ran == single, (ran, single)             # the pair's capture took the families the launches take
+    assert rec.paired in ([0, 0], [1, 2]), rec.paired
+    if merged is not None:
+        assert rec.paired == ([1, 2] if merged else [0, 0]), (rec.paired, ran)
+    prev = ops.tune('conv_pair', 1)
+    try:
+        rec2 = ops.record_conv_kernels()
+        with rec2 as ran2:
+            two_a, two_b = ops.conv2d_pair((pca, xa, dict(act=ops.ACT_RELU)), (pcb, xb, dict(act=ops.ACT_NONE)))
+        torch.cuda.synchronize()
+    finally:
+        ops.tune('conv_pair', prev)
+    assert ran2 == single and rec2.paired == [0, 0], (ran2, rec2.paired)
+    assert torch.equal(two_a, want_a) and torch.equal(two_b, want_b)
     close(got_a, torch.relu(F.conv2d(xa.cpu(), wa.cpu(), pca.bias.cpu(), padding=pa)), atol=3e-5, what='pair a vs torch')
     close(got_b, F.conv2d(xb.cpu(), wb.cpu(), pcb.bias.cpu(), padding=pb), atol=3e-5, what='pair b vs torch')

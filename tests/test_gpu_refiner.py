@@ -858,3 +858,37 @@ def test_branch_modes_are_bit_identical(golden_dir, model, n):
         for a, b in zip(outs['in order'], outs[name]):
             for x, y in zip(a, b):
                 assert torch.equal(x, y), name
+
+
+def test_merged_launches_of_a_batch_1_step(golden_dir):
+    """The layers scf_conv2d_pair runs as ONE launch in a bench.py step at batch 1 (iters 8), in launch order: the
+    feature | context encoder pair (modules.raft_encoder_pair), then per iteration corr_net | flow_net (MotionEncoder),
+    the flow | mask predictions and the delta-flow | mask encoders.  A heuristic change that stops a merged kernel from
+    running fails here instead of passing unnoticed (every pair is bit-identical to its two launches)."""
+    m = scflow_amd.build_refiner(scflow_amd.scflow_model_cfg(iters=8))
+    m.load_state_dict(scflow_amd.fill_state_dict(_shapes(golden_dir), seed=0), strict=True)
+    m = m.to(DEV)
+    d = {k: v.to(DEV) for k, v in scflow_amd.make_inputs(1, 256, 256, seed=1000).items()}
+    step = lambda: m.get_pose(d['render_images'], d['real_images'], d['ref_rotation'], d['ref_translation'],
+                              d['depth'], d['internel_k'], d['label'])
+    step()
+    rec = ops.record_conv_kernels()
+    with rec as ran:
+        step()
+    torch.cuda.synchronize()
+    merged = []
+    for i, p in enumerate(rec.paired):
+        if p == 1:
+            assert rec.paired[i + 1] == 2, (i, rec.paired)
+            merged.append((ran[i], ran[i + 1]))
+        else:
+            assert p == 0 or rec.paired[i - 1] == 1, (i, rec.paired)
+    wq = ('64->64 3x3/s1 @128x128 N2', 'winograd-q'), ('64->64 3x3/s1 @128x128 N1', 'winograd-q')
+    encoders = [(('3->64 7x7/s2 @128x128 N2', 'taps'), ('3->64 7x7/s2 @128x128 N1', 'taps'))] + [wq] * 4 + \
+               [(('96->128 1x1/s2 @32x32 N2', 'direct-dma'), ('96->128 1x1/s2 @32x32 N1', 'direct-dma'))]
+    iteration = [(('324->256 1x1/s1 @32x32 N1', 'direct-dma'), ('2->128 7x7/s1 @32x32 N1', 'taps')),
+                 (('256->192 3x3/s1 @32x32 N1', 'direct-dma'), ('128->64 3x3/s1 @32x32 N1', 'direct-dma')),
+                 (('256->2 3x3/s1 @32x32 N1', 'thin'), ('256->1 1x1/s1 @32x32 N1', 'thin')),
+                 (('2->128 7x7/s1 @32x32 N1', 'taps'), ('1->64 3x3/s1 @32x32 N1', 'taps')),
+                 (('128->64 3x3/s1 @32x32 N1', 'direct-dma'), ('64->32 3x3/s1 @32x32 N1', 'direct-dma'))]
+    assert merged == encoders + iteration * 8, merged
