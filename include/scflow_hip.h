@@ -55,7 +55,8 @@ enum {
  * SCF_ABI_MAJOR before its first call; structs additionally carry no size field,
  * so a mismatch must be refused, not worked around. */
 #define SCF_ABI_MAJOR 5
-#define SCF_VERSION (SCF_ABI_MAJOR * 100 + 2)   /* .1: label_mode is a bit set (SCF_POSE_*); .2: scf_conv2d_pair, overlap_* = 2 */
+#define SCF_VERSION (SCF_ABI_MAJOR * 100 + 3)   /* .1: label_mode is a bit set (SCF_POSE_*); .2: scf_conv2d_pair, overlap_* = 2;
+                                                  .3: scf_flow_corr_2d3d, scf_pnp_ransac, scf_pnp_workspace_bytes */
 int scf_version(void);
 const char* scf_error_string(int code);
 /* number of HIP devices visible (>=0) or SCF_ENODEVICE */
@@ -466,6 +467,58 @@ int scf_pose_error(const double* verts, int nv, const double* gt_r, const double
                    const double* pred_r, const double* pred_t, const double* K,
                    const int* sample_idx, int nsel, int symmetric, double* err3d, double* err2d,
                    scf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Flow -> 2-D/3-D correspondences.   replaces get_2d_3d_corr_by_fw_flow + cal_3d_2d_corr,
+ *                                    models/utils/pose.py:44-64, 182-200
+ * Per sample n, every pixel (x, y) with depth > 0 (and, when occ is not NULL, occ > occ_thresh;
+ * a NaN occlusion is not kept) is written out compacted in row-major order (torch.nonzero's order):
+ *   pts2d[n, i] = (x + flow[n,0,y,x], y + flow[n,1,y,x])              (the target-image point)
+ *   pts3d[n, i] = R0^-1 (K^-1 [x y 1]^T d - t0)                         (lift_2d_to_3d, as scf_reproject_flow)
+ *   conf[n, i]  = occ[n,y,x] (1 without occ);  count[n] = number of kept pixels.
+ * flow (N,2,H,W); depth, occ (N,H,W); K, R0 (N,3,3); t0 (N,3); outputs have capacity H*W per sample:
+ * pts2d (N,H*W,2), pts3d (N,H*W,3), conf (N,H*W), count (N) int32.  Entries >= count[n] are left untouched.
+ * --------------------------------------------------------------------------------- */
+int scf_flow_corr_2d3d(const float* flow, const float* depth, const float* occ, float occ_thresh,
+                       const float* K, const float* R0, const float* t0, int N, int H, int W,
+                       float* pts2d, float* pts3d, float* conf, int32_t* count, scf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
+ * Batched RANSAC-EPnP.               replaces sample_points + solve_pose_by_pnp (cv2.solvePnPRansac with
+ *                                    SOLVEPNP_EPNP), base_flow_refiner.py:49-71, pose.py:203-249
+ * Inputs: the outputs of scf_flow_corr_2d3d (capacity = points per sample; conf only read by TOPK), K (N,3,3),
+ * the reference pose R_ref (N,3,3), t_ref (N,3).  Per sample:
+ *   sampling   ALL: every point.  TOPK: the sample_num points of highest conf, ties to the lower index.
+ *              RANDOM: sample_num distinct indices of [0, count-1) chosen by a counter-based hash of
+ *              (seed, index) -- the reference's randperm(count - 1) quirk kept, its generator not reproduced.
+ *              Both keep every point when sample_num > count.
+ *   hypotheses `iterations` of them; hypothesis h takes 5 distinct points drawn by a hash of (seed, h) -- the
+ *              sample's position in the batch does not enter, so a sample gives the same bits alone or batched --
+ *              and solves EPnP on them (Lepetit et al.: centroid + PCA control points, 12x12 M^T M, the beta cases
+ *              N = 1..3 each refined by Gauss-Newton, lowest reprojection error kept; fp64).
+ *   scoring    inlier: projected depth > 0 and reprojection error < reproj_error pixels (NaN: outlier); the
+ *              hypothesis with the most inliers wins, ties to the lowest h; all hypotheses run (no early stop).
+ *   final      EPnP over every inlier of the winner, re-scored: inliers[n] = its inlier count.
+ *   failure    ok[n] = 0, R/t = the reference pose, inliers[n] = 0 when count < 4, fewer than 5 points remain,
+ *              the winner has fewer than 5 inliers, the inlier set is collinear or planar (smallest principal
+ *              variance <= 1e-8 of the largest), or anything is non-finite.  Otherwise ok[n] = 1.
+ * Outputs R (N,3,3), t (N,3) fp32; ok, inliers (N) int32.  workspace: scf_pnp_workspace_bytes(N, capacity, params)
+ * bytes of device memory (0 for ALL: workspace may be NULL).  One workgroup per sample (see pnp.hip for the layout).
+ * --------------------------------------------------------------------------------- */
+enum { SCF_PNP_SAMPLE_ALL = 0, SCF_PNP_SAMPLE_TOPK = 1, SCF_PNP_SAMPLE_RANDOM = 2 };
+typedef struct scf_pnp_params {
+  int32_t iterations;     /* hypotheses (iterationscount), > 0                      */
+  float reproj_error;     /* inlier threshold in pixels (reprojectionerror), >= 0   */
+  int32_t sample_mode;    /* SCF_PNP_SAMPLE_*                                        */
+  int32_t sample_num;     /* points kept by TOPK / RANDOM, > 0                       */
+  uint64_t seed;          /* hypothesis and RANDOM draws                             */
+} scf_pnp_params;
+/* bytes of workspace scf_pnp_ransac needs, or SCF_EINVAL for bad arguments */
+int64_t scf_pnp_workspace_bytes(int N, int capacity, const scf_pnp_params* params);
+int scf_pnp_ransac(const float* pts2d, const float* pts3d, const float* conf, const int32_t* count, int N,
+                   int capacity, const float* K, const float* R_ref, const float* t_ref,
+                   const scf_pnp_params* params, float* R, float* t, int32_t* ok, int32_t* inliers,
+                   void* workspace, scf_stream_t stream);
 
 /* filter_flow_by_mask (models/utils/flow.py:6-26), in place on flow (N,2,H,W): a vector is set
  * to invalid_num when both components are >= invalid_num or when mask (N,H,W), sampled

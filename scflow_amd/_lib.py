@@ -94,6 +94,15 @@ class FcDesc(C.Structure):
                 ('act', C.c_int32), ('slices', C.c_int32)]
 
 
+class PnpParams(C.Structure):
+    """mirror of ``scf_pnp_params`` (include/scflow_hip.h)."""
+    _fields_ = [('iterations', C.c_int32), ('reproj_error', C.c_float), ('sample_mode', C.c_int32),
+                ('sample_num', C.c_int32), ('seed', C.c_uint64)]
+
+
+PNP_SAMPLE_ALL, PNP_SAMPLE_TOPK, PNP_SAMPLE_RANDOM = 0, 1, 2
+
+
 class IterGN(C.Structure):
     """mirror of ``scf_iter_gn``."""
     _fields_ = [('gamma', _fp), ('beta', _fp), ('out', _fp),
@@ -194,6 +203,11 @@ SIGNATURES = {
                                   C.c_int, _fp]),
     'scf_reproject_flow': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int,
                                      C.c_int, C.c_float, _fp]),
+    'scf_flow_corr_2d3d': (C.c_int, [_fp, _fp, _fp, C.c_float, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                     _fp, _fp, _fp, _fp, _fp]),
+    'scf_pnp_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.POINTER(PnpParams)]),
+    'scf_pnp_ransac': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(PnpParams),
+                                 _fp, _fp, _fp, _fp, _fp, _fp]),
     'scf_unproject_depth': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_resize_bilinear': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),

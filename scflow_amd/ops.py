@@ -28,6 +28,7 @@ Tensor = torch.Tensor
 __all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scflow_iteration', 'side_stream_handle', 'pyramid_layout', 'untile_level', 'level_storage_shape', 'sepconv_gru', 'pack_conv_weight', 'pack_conv_weight_f16x3', 'set_conv_precision', 'set_conv_winograd', 'get_conv_winograd', 'pack_conv_weight_wino', 'pack_conv_weight_wino1d', 'pack_conv_weight_wino1d4',
            'get_conv_precision', 'set_conv_kslices', 'conv_kslices', 'conv_kslices_for', 'constant', 'clear_constants', 'register_conv_workspace', 'choose_kc', 'conv2d', 'conv2d_pair', 'corr_build', 'corr_lookup',
            'instance_norm', 'group_norm_relu', 'linear', 'fc_splitk', 'fc_slices', 'pose_update', 'reproject_flow',
+           'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
            'unproject_depth', 'linear_pair', 'resize_bilinear', 'convex_upsample', 'avgpool2x2', 'copy_channels',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_TANH', 'CONV_PLAIN', 'CONV_GRU_ZR',
            'CONV_GRU_Q']
@@ -1261,6 +1262,108 @@ def filter_flow_by_mask_(flow: Tensor, mask: Tensor, invalid_num: float = 400.,
                                                    float(invalid_num), int(align_corners), _stream()),
                'scf_filter_flow_by_mask')
     return flow
+
+
+def _mats(t: Tensor, n: int, shape: Tuple[int, ...], name: str) -> int:
+    if tuple(t.shape) != (n, *shape):
+        raise _lib.ScflowHipError(f'{name}: expected shape {(n, *shape)}, got {tuple(t.shape)}')
+    return _dense(t, name)
+
+
+def flow_corr_2d3d(flow: Tensor, depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor,
+                   occlusion: Optional[Tensor] = None, occ_thresh: float = 0.5):
+    """``get_2d_3d_corr_by_fw_flow`` (models/utils/pose.py:182-200) for the whole batch in one launch.
+
+    flow (N,2,H,W), depth (N,H,W), k / rot0 (N,3,3), trans0 (N,3), occlusion (N,H,W) or None ->
+    (pts2d (N,H*W,2), pts3d (N,H*W,3), conf (N,H*W), count (N,) int32): sample n's first count[n] rows are its
+    pixels with depth > 0 (and occlusion > occ_thresh) in row-major order; pts2d is the flow's target point, pts3d
+    the object-frame point, conf the occlusion value (1 without one).  Rows past count[n] are unspecified."""
+    if depth.dim() != 3:
+        raise _lib.ScflowHipError('flow_corr_2d3d: depth must be (N,H,W)')
+    n, h, w = depth.shape
+    if tuple(flow.shape) != (n, 2, h, w):
+        raise _lib.ScflowHipError(f'flow_corr_2d3d: flow must be {(n, 2, h, w)}, got {tuple(flow.shape)}')
+    if occlusion is not None and tuple(occlusion.shape) != (n, h, w):
+        raise _lib.ScflowHipError(f'flow_corr_2d3d: occlusion must be {(n, h, w)}, got {tuple(occlusion.shape)}')
+    dev = depth.device
+    pts2d = torch.empty((n, h * w, 2), dtype=torch.float32, device=dev)
+    pts3d = torch.empty((n, h * w, 3), dtype=torch.float32, device=dev)
+    conf = torch.empty((n, h * w), dtype=torch.float32, device=dev)
+    count = torch.empty((n,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().scf_flow_corr_2d3d(
+        _dense(flow, 'flow'), _dense(depth, 'depth'), _opt(occlusion, 'occlusion'), float(occ_thresh),
+        _mats(k, n, (3, 3), 'k'), _mats(rot0, n, (3, 3), 'rot0'), _mats(trans0, n, (3,), 'trans0'), n, h, w,
+        pts2d.data_ptr(), pts3d.data_ptr(), conf.data_ptr(), count.data_ptr(), _stream()), 'scf_flow_corr_2d3d')
+    return pts2d, pts3d, conf, count
+
+
+_PNP_MODES = {None: _lib.PNP_SAMPLE_ALL, 'topk': _lib.PNP_SAMPLE_TOPK, 'random': _lib.PNP_SAMPLE_RANDOM}
+
+
+def pnp_params(iterations: int = 100, reproj_error: float = 3.0, sample_mode: Optional[str] = None,
+               sample_num: int = 1000, seed: int = 0) -> '_lib.PnpParams':
+    """validated ``scf_pnp_params``: iterations > 0, a finite reproj_error >= 0 (pixels), sample_mode None / 'topk' /
+    'random' with sample_num > 0, seed in [0, 2^64)."""
+    if isinstance(iterations, bool) or int(iterations) != iterations or iterations <= 0:
+        raise _lib.ScflowHipError(f'pnp: iterations must be a positive integer, got {iterations!r}')
+    if not math.isfinite(float(reproj_error)) or float(reproj_error) < 0:
+        raise _lib.ScflowHipError(f'pnp: reproj_error must be finite and >= 0, got {reproj_error!r}')
+    if sample_mode not in _PNP_MODES:
+        raise _lib.ScflowHipError(f"pnp: sample_mode must be None, 'topk' or 'random', got {sample_mode!r}")
+    if sample_mode is not None and (int(sample_num) != sample_num or sample_num <= 0):
+        raise _lib.ScflowHipError(f'pnp: sample_num must be a positive integer, got {sample_num!r}')
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise _lib.ScflowHipError(f'pnp: seed must be an integer in [0, 2^64), got {seed!r}')
+    return _lib.PnpParams(int(iterations), float(reproj_error), _PNP_MODES[sample_mode],
+                          int(sample_num) if sample_mode is not None else 0, int(seed))
+
+
+def pnp_ransac(pts2d: Tensor, pts3d: Tensor, count: Tensor, k: Tensor, ref_rot: Tensor, ref_trans: Tensor,
+               conf: Optional[Tensor] = None, iterations: int = 100, reproj_error: float = 3.0,
+               sample_mode: Optional[str] = None, sample_num: int = 1000, seed: int = 0):
+    """batched RANSAC-EPnP (``scf_pnp_ransac``; include/scflow_hip.h states the contract).
+
+    pts2d (N,C,2), pts3d (N,C,3), conf (N,C) (read by sample_mode='topk'), count (N,) int32 -- the layout
+    ``flow_corr_2d3d`` writes -- plus k, ref_rot (N,3,3), ref_trans (N,3) -> (R (N,3,3), t (N,3), ok (N,) int32,
+    inliers (N,) int32).  A failed sample returns ok = 0 and the reference pose.  No host synchronisation."""
+    p = pnp_params(iterations, reproj_error, sample_mode, sample_num, seed)
+    if pts2d.dim() != 3 or pts2d.shape[2] != 2:
+        raise _lib.ScflowHipError('pnp_ransac: pts2d must be (N,C,2)')
+    n, cap = pts2d.shape[0], pts2d.shape[1]
+    if tuple(pts3d.shape) != (n, cap, 3):
+        raise _lib.ScflowHipError(f'pnp_ransac: pts3d must be {(n, cap, 3)}, got {tuple(pts3d.shape)}')
+    if conf is not None and tuple(conf.shape) != (n, cap):
+        raise _lib.ScflowHipError(f'pnp_ransac: conf must be {(n, cap)}, got {tuple(conf.shape)}')
+    if sample_mode == 'topk' and conf is None:
+        raise _lib.ScflowHipError("pnp_ransac: sample_mode='topk' needs conf")
+    if (not isinstance(count, torch.Tensor) or not count.is_cuda or count.dtype != torch.int32
+            or tuple(count.shape) != (n,) or not count.is_contiguous() or count.device != pts2d.device):
+        raise _lib.ScflowHipError(f'pnp_ransac: count must be a contiguous int32 GPU tensor of shape {(n,)}')
+    if n == 0 or cap == 0:
+        raise _lib.ScflowHipError('pnp_ransac: empty batch')
+    lib = _lib.load()
+    dev = pts2d.device
+    wsb = lib.scf_pnp_workspace_bytes(n, cap, C.byref(p))
+    _lib.check(min(int(wsb), 0), 'scf_pnp_workspace_bytes')
+    ws = torch.empty((max(int(wsb), 1),), dtype=torch.uint8, device=dev) if wsb > 0 else None
+    rot = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    trans = torch.empty((n, 3), dtype=torch.float32, device=dev)
+    ok = torch.empty((n,), dtype=torch.int32, device=dev)
+    inl = torch.empty((n,), dtype=torch.int32, device=dev)
+    _lib.check(lib.scf_pnp_ransac(
+        _dense(pts2d, 'pts2d'), _dense(pts3d, 'pts3d'), _opt(conf, 'conf'), count.data_ptr(), n, cap,
+        _mats(k, n, (3, 3), 'k'), _mats(ref_rot, n, (3, 3), 'ref_rot'), _mats(ref_trans, n, (3,), 'ref_trans'),
+        C.byref(p), rot.data_ptr(), trans.data_ptr(), ok.data_ptr(), inl.data_ptr(),
+        None if ws is None else ws.data_ptr(), _stream()), 'scf_pnp_ransac')
+    return rot, trans, ok, inl
+
+
+def pnp(flow: Tensor, depth: Tensor, k: Tensor, ref_rot: Tensor, ref_trans: Tensor,
+        occlusion: Optional[Tensor] = None, occ_thresh: float = 0.5, **ransac):
+    """pose from flow: ``flow_corr_2d3d`` then ``pnp_ransac`` (keyword arguments of the latter pass through)
+    -> (R, t, ok, inliers).  Two launches (three with sampling), no host synchronisation."""
+    pts2d, pts3d, conf, count = flow_corr_2d3d(flow, depth, k, ref_rot, ref_trans, occlusion, occ_thresh)
+    return pnp_ransac(pts2d, pts3d, count, k, ref_rot, ref_trans, conf=conf, **ransac)
 
 
 def unproject_depth(depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor) -> Tensor:

@@ -161,9 +161,15 @@ class SCFlowRefiner(HipModule):
 
 
 class _FlowRefinerBase(HipModule):
-    """feature extraction + ``get_flow`` of the pose-free RAFT refiners
-    (models/refiner/raft_refiner_flow_mask.py:88-133, raft_refiner_flow.py).  Their pose step
-    is cv2 RANSAC-PnP on the CPU (models/utils/pose.py:203-249): out of scope, raises."""
+    """feature extraction, ``get_flow`` and the pose step of the pose-free RAFT refiners
+    (models/refiner/raft_refiner_flow_mask.py:88-161, raft_refiner_flow.py, base_flow_refiner.py:99-154).
+
+    The reference's pose step is cv2 RANSAC-EPnP on the CPU (models/utils/pose.py:203-249).  Here it is the batched
+    HIP solver (``ops.pnp``: the same algorithm class, another sampler, no cv2 bit parity), selected explicitly with
+    ``test_cfg['solve_pose_mode'] = 'hip_ransac_epnp'``; the reference's own modes ('ransacpnp', the default, and
+    'progressive-x') raise ``NotImplementedError``, so the solver is never silently substituted for cv2.
+    ``test_cfg['solve_pose_param']`` takes iterationscount (100), reprojectionerror (3.0) and seed (0);
+    ``test_cfg['sample_points']`` (num, mode) and ``occ_thresh`` (0.5) act as in the reference."""
 
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int,
                  cxt_encoder: dict, encoder: dict, decoder: dict, test_cfg: Optional[dict] = None,
@@ -195,13 +201,101 @@ class _FlowRefinerBase(HipModule):
             init_flow = ops.constant((b, 2, h, w), 0.0, feat_real.device)
         return self.decoder(feat_render, feat_real, init_flow, h_feat, cxt_feat, _consume_state=True)
 
-    def solve_pose(self, *a, **k):
-        raise NotImplementedError('RANSAC-PnP (cv2) pose solve is outside the HIP hot path')
+    HIP_PNP_MODE = 'hip_ransac_epnp'
+    _has_occlusion = False
+
+    def _pnp_kwargs(self) -> dict:
+        mode = self.test_cfg.get('solve_pose_mode', 'ransacpnp')
+        if mode == 'ransacpnp':
+            raise NotImplementedError(
+                "solve_pose_mode 'ransacpnp' is cv2.solvePnPRansac on the CPU (models/utils/pose.py:203-249), which "
+                f"this package does not ship; set test_cfg['solve_pose_mode'] = '{self.HIP_PNP_MODE}' for the batched "
+                'HIP RANSAC-EPnP solver (same algorithm class, different sampler: not bit-equal to cv2)')
+        if mode != self.HIP_PNP_MODE:
+            raise NotImplementedError(f'solve_pose_mode {mode!r} is not implemented; the HIP solver is '
+                                      f"test_cfg['solve_pose_mode'] = '{self.HIP_PNP_MODE}'")
+        prm = self.test_cfg.get('solve_pose_param', {}) or {}
+        kw = dict(iterations=prm.get('iterationscount', 100), reproj_error=prm.get('reprojectionerror', 3.0),
+                  seed=prm.get('seed', 0))
+        sample = self.test_cfg.get('sample_points', None)
+        if sample is not None:
+            # base_flow_refiner.py:65-71: 'random', or top-k by confidence for any other mode
+            kw.update(sample_mode='random' if sample.get('mode', 'random') == 'random' else 'topk',
+                      sample_num=sample.get('num', 1000))
+        ops.pnp_params(**kw)                    # reject bad parameters before any launch
+        return kw
+
+    def solve_pose(self, batch_flow: Optional[Tensor] = None, rendered_depths: Optional[Tensor] = None,
+                   ref_rotations: Optional[Tensor] = None, ref_translations: Optional[Tensor] = None,
+                   internel_k: Optional[Tensor] = None, labels: Optional[Tensor] = None,
+                   per_img_patch_num=None, occlusion: Optional[Tensor] = None) -> Dict:
+        """base_flow_refiner.py:99-154 -> dict(rotations, translations, scores, labels), each a per-image list with
+        the samples whose solve failed dropped.  One launch sequence for the whole batch and ONE device-to-host
+        transfer (the ok flags); no per-sample synchronisation.  Without an occlusion map, top-k sampling sees a
+        confidence of 1 everywhere (the reference has no confidence there) and keeps the first points."""
+        kw = self._pnp_kwargs()
+        args = (batch_flow, rendered_depths, ref_rotations, ref_translations, internel_k, labels, per_img_patch_num)
+        if any(a is None for a in args):
+            raise TypeError('solve_pose needs batch_flow, rendered_depths, ref_rotations, ref_translations, '
+                            'internel_k, labels and per_img_patch_num')
+        occ = None if occlusion is None else occlusion.contiguous()
+        rot, trans, ok, _ = ops.pnp(batch_flow.contiguous(), rendered_depths.contiguous(), internel_k.contiguous(),
+                                    ref_rotations.contiguous(), ref_translations.contiguous(), occ,
+                                    self.test_cfg.get('occ_thresh', 0.5), **kw)
+        per = [int(v) for v in per_img_patch_num]
+        keep = ok.cpu().bool()                  # the one device -> host transfer
+        idx = torch.nonzero(keep).flatten()
+        kept = [int(k.sum()) for k in torch.split(keep, per)]
+        idx_dev = idx.to(rot.device, non_blocking=True)
+        scores = torch.ones_like(labels, dtype=torch.float32)
+        return {name: list(torch.split(t.index_select(0, idx_dev), kept))
+                for name, t in (('rotations', rot), ('translations', trans), ('scores', scores), ('labels', labels))}
+
+    @staticmethod
+    def _remap_pose(rotations, translations, img_metas):
+        """remap_pose_to_origin_resoluaion (models/utils/pose.py:264-310) for the 'adapt_intrinsic' pipeline: the
+        identity.  The other modes re-solve with cv2 EPnP in the reference: not implemented."""
+        for meta in img_metas or []:
+            mode = meta.get('geometry_transform_mode') if isinstance(meta, dict) else None
+            if mode != 'adapt_intrinsic':
+                raise NotImplementedError(f'pose remapping for geometry_transform_mode {mode!r} is not implemented '
+                                          "(only 'adapt_intrinsic', the identity)")
+        return rotations, translations
+
+    def forward_single_view(self, data: Dict, data_batch: Optional[Dict] = None, return_pose: bool = True):
+        """raft_refiner_flow_mask.py:135-161 / raft_refiner_flow.py:141-172: flow at the last iteration, then the
+        pose step.  return_pose=False returns (flow, occlusion, data) for the mask refiner, (flow, data) otherwise."""
+        iters = self.decoder.iters
+        self.decoder.iters = self.test_iter_num
+        try:
+            out = self.get_flow(data['rendered_images'], data['real_images'])
+        finally:
+            self.decoder.iters = iters
+        if self._has_occlusion:
+            batch_flow, batch_occ = out[0][-1], out[1][-1].squeeze(1)
+        else:
+            batch_flow, batch_occ = out[-1], None
+        if not return_pose:
+            return (batch_flow, batch_occ, data) if self._has_occlusion else (batch_flow, data)
+        results = self.solve_pose(batch_flow, data['rendered_depths'], data['ref_rotations'],
+                                  data['ref_translations'], data['internel_k'], data['labels'],
+                                  data['per_img_patch_num'], batch_occ)
+        img_metas = (data_batch or {}).get('img_metas') if isinstance(data_batch, dict) else None
+        results['rotations'], results['translations'] = self._remap_pose(results['rotations'],
+                                                                         results['translations'], img_metas)
+        return results
+
+    def forward(self, data, data_batch=None, return_loss=False):
+        if return_loss:
+            raise NotImplementedError('training is outside the hot path (SURVEY.md section 2)')
+        return self.forward_single_view(data, data_batch)
 
 
 @REFINERS.register_module()
 class RAFTRefinerFlowMask(_FlowRefinerBase):
-    """configs/refine_models/raft.py: RAFTDecoderMask -> (flows, occlusions)."""
+    """configs/refine_models/raft.py: RAFTDecoderMask -> (flows, occlusions); the pose step uses the last
+    occlusion map (confidence and occ_thresh mask)."""
+    _has_occlusion = True
 
 
 @REFINERS.register_module()
