@@ -520,6 +520,56 @@ int scf_pnp_ransac(const float* pts2d, const float* pts3d, const float* conf, co
                    const scf_pnp_params* params, float* R, float* t, int32_t* ok, int32_t* inliers,
                    void* workspace, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Mesh renderer.                     replaces Renderer.forward (models/utils/rendering.py, pytorch3d
+ *                                    MeshRasterizer + HardPhongShader) under the shipped configuration:
+ *                                    faces_per_pixel=1, blur_radius=0, hard blending, Phong, no mask pass.
+ * Added without a version bump (SCF_VERSION stays at .3): the presence of scf_render_mesh,
+ * scf_render_workspace_bytes and scf_render_pixel_coord marks the feature.  render.hip states the semantics
+ * in full; in short, per sample n with mesh m = labels[n]:
+ *   camera     OpenCV R (N,3,3), t (N,3), K (N,3,3): X_c = R X + t, u = fx X_c.x / X_c.z + cx (v likewise).
+ *   sampling   output column c samples u(c) = (W-1)/2 - (S-1)(W-2c-1)/(2S), S = min(H,W); rows likewise with H
+ *              (pytorch3d's flipped non-square NDC grid under cameras_from_opencv_projection); see
+ *              scf_render_pixel_coord.
+ *   coverage   all three screen barycentrics >= 0; faces of zero screen area or with every vertex at z <= 0 are
+ *              skipped, hits whose perspective-correct z <= 0 are discarded; no back-face culling.
+ *   depth      the hit is the lexicographic minimum of (z, face index); 1/z is linear in screen space.
+ *   outputs    zbuf (N,H,W) = z or -1; pix_to_face (N,H,W) int32 = face index within mesh m, or -1;
+ *              rgba (N,H,W,4) and / or rgb_nchw (N,3,H,W) = (rgb - norm_mean[c]) / norm_std[c]; either may be NULL.
+ *   shading    pytorch3d phong_shading + hard_rgb_blend in the object frame, perspective-correct barycentrics,
+ *              material colours 1, shininess 64; lights per default_lights / seperate_lights (render.hip).
+ * A label outside [0, num_classes) renders background (the kernels cannot raise; validate labels beforehand).
+ * The mesh store holds every class mesh concatenated: class k owns vertices [vert_offset[k], vert_offset[k+1])
+ * and faces [face_offset[k], face_offset[k+1]); face indices are local to the class.  max_faces >= the largest
+ * class's face count.  workspace: scf_render_workspace_bytes(N, max_faces) bytes of device memory.
+ * --------------------------------------------------------------------------------- */
+typedef struct scf_mesh_store {
+  const float* verts;          /* (V,3) object-frame positions                         */
+  const float* normals;        /* (V,3) vertex normals (need not be unit length)       */
+  const float* colors;         /* (V,3) vertex colours in [0,1]                         */
+  const int32_t* faces;        /* (F,3) vertex indices, local to the face's class       */
+  const int32_t* vert_offset;  /* (num_classes+1)                                       */
+  const int32_t* face_offset;  /* (num_classes+1)                                       */
+  int32_t num_classes;
+  int32_t max_faces;
+} scf_mesh_store;
+typedef struct scf_render_params {
+  int32_t H, W;                /* image size, 1..8192 each                             */
+  int32_t default_lights;      /* 1: pytorch3d PointLights colours; 0: ambient .8, diffuse .5, specular 1 */
+  int32_t seperate_lights;     /* 1: light at R (0, 0, max(zmin_n - 400, 0)) per sample */
+  float background[3];         /* RGB of uncovered pixels                              */
+  float norm_mean[3];          /* rgb_nchw = (rgb - norm_mean) / norm_std per channel  */
+  float norm_std[3];
+} scf_render_params;
+/* image-plane coordinate sampled by pixel `index` along an axis of `size` pixels when the other axis has `other`
+ * pixels (host function, no device involved) */
+double scf_render_pixel_coord(int index, int size, int other);
+/* bytes of workspace scf_render_mesh needs, or SCF_EINVAL for bad arguments */
+int64_t scf_render_workspace_bytes(int N, int max_faces);
+int scf_render_mesh(const scf_mesh_store* mesh, const int32_t* labels, const float* R, const float* t,
+                    const float* K, int N, const scf_render_params* params, float* zbuf, int32_t* pix_to_face,
+                    float* rgba, float* rgb_nchw, void* workspace, scf_stream_t stream);
+
 /* filter_flow_by_mask (models/utils/flow.py:6-26), in place on flow (N,2,H,W): a vector is set
  * to invalid_num when both components are >= invalid_num or when mask (N,H,W), sampled
  * bilinearly (zeros padding) at the vector's end point, is < 0.9.  The end point is normalised

@@ -21,3 +21,4 @@ from .metrics import (cal_epe, eval_pose_error, eval_rot_error,  # noqa: F401
 from .config import raft_model_cfg, scflow_model_cfg  # noqa: F401
 from .weights import fill_state_dict  # noqa: F401
 from .synthetic import make_inputs  # noqa: F401
+from .mesh import Fragments, Mesh, MeshRenderer, MeshStore, make_mesh, read_ply  # noqa: F401

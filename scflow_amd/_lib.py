@@ -103,6 +103,18 @@ class PnpParams(C.Structure):
 PNP_SAMPLE_ALL, PNP_SAMPLE_TOPK, PNP_SAMPLE_RANDOM = 0, 1, 2
 
 
+class MeshStore(C.Structure):
+    """mirror of ``scf_mesh_store`` (include/scflow_hip.h)."""
+    _fields_ = [('verts', _fp), ('normals', _fp), ('colors', _fp), ('faces', _fp), ('vert_offset', _fp),
+                ('face_offset', _fp), ('num_classes', C.c_int32), ('max_faces', C.c_int32)]
+
+
+class RenderParams(C.Structure):
+    """mirror of ``scf_render_params`` (include/scflow_hip.h)."""
+    _fields_ = [('H', C.c_int32), ('W', C.c_int32), ('default_lights', C.c_int32), ('seperate_lights', C.c_int32),
+                ('background', C.c_float * 3), ('norm_mean', C.c_float * 3), ('norm_std', C.c_float * 3)]
+
+
 class IterGN(C.Structure):
     """mirror of ``scf_iter_gn``."""
     _fields_ = [('gamma', _fp), ('beta', _fp), ('out', _fp),
@@ -208,6 +220,10 @@ SIGNATURES = {
     'scf_pnp_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.POINTER(PnpParams)]),
     'scf_pnp_ransac': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, _fp, _fp, _fp, C.POINTER(PnpParams),
                                  _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_render_pixel_coord': (C.c_double, [C.c_int, C.c_int, C.c_int]),
+    'scf_render_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
+    'scf_render_mesh': (C.c_int, [C.POINTER(MeshStore), _fp, _fp, _fp, _fp, C.c_int, C.POINTER(RenderParams),
+                                  _fp, _fp, _fp, _fp, _fp, _fp]),
     'scf_unproject_depth': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_resize_bilinear': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),

@@ -1366,6 +1366,62 @@ def pnp(flow: Tensor, depth: Tensor, k: Tensor, ref_rot: Tensor, ref_trans: Tens
     return pnp_ransac(pts2d, pts3d, count, k, ref_rot, ref_trans, conf=conf, **ransac)
 
 
+def render_pixel_coord(index: int, size: int, other: int) -> float:
+    """image-plane coordinate sampled by pixel ``index`` along an axis of ``size`` pixels when the other axis has
+    ``other`` (``scf_render_pixel_coord``, the kernels' own formula; a host call)."""
+    return float(_lib.load().scf_render_pixel_coord(int(index), int(size), int(other)))
+
+
+def render_mesh(mesh, labels: Tensor, rot: Tensor, trans: Tensor, k: Tensor, image_size: Tuple[int, int], *,
+                default_lights: bool = True, seperate_lights: bool = True,
+                background: Sequence[float] = (0.5, 0.5, 0.5), images: bool = True, pix_to_face: bool = True,
+                norm: Optional[Tuple[Sequence[float], Sequence[float]]] = None) -> dict:
+    """hard-rasterised, Phong-shaded render of each sample's mesh (``scf_render_mesh``; render.hip states the
+    semantics).  ``mesh`` is a ``mesh.DeviceMesh`` (``MeshStore.on(device)``), labels (N,) int GPU tensor selecting
+    the class mesh per sample (read on the device: no host synchronisation), rot / k (N,3,3), trans (N,3).
+    -> dict(zbuf (N,H,W): z or -1, pix_to_face (N,H,W) int32 or None, images (N,H,W,4) or None, rgb (N,3,H,W) =
+    (rgb - mean) / std or None, present when ``norm`` = (mean, std) is given)."""
+    h, w = int(image_size[0]), int(image_size[1])
+    n = rot.shape[0] if rot.dim() == 3 else -1
+    if n <= 0 or tuple(rot.shape) != (n, 3, 3):
+        raise _lib.ScflowHipError(f'render_mesh: rot must be (N,3,3) with N > 0, got {tuple(rot.shape)}')
+    if (not isinstance(labels, torch.Tensor) or not labels.is_cuda or tuple(labels.shape) != (n,)
+            or labels.dtype not in (torch.int32, torch.int64) or labels.device != rot.device):
+        raise _lib.ScflowHipError(f'render_mesh: labels must be an integer GPU tensor of shape {(n,)} on {rot.device}')
+    if not 0 < h <= 8192 or not 0 < w <= 8192:
+        raise _lib.ScflowHipError(f'render_mesh: image size {(h, w)} outside 1..8192')
+    dev = rot.device
+    lab = labels.to(torch.int32).contiguous()
+    for t, nm in ((mesh.verts, 'verts'), (mesh.normals, 'normals'), (mesh.colors, 'colors')):
+        _dense(t, nm)
+    for t in (mesh.faces, mesh.vert_offset, mesh.face_offset):
+        if t.device != dev or t.dtype != torch.int32 or not t.is_contiguous():
+            raise _lib.ScflowHipError(f'render_mesh: the mesh store must live on {dev} (MeshStore.on(device))')
+    store = _lib.MeshStore(mesh.verts.data_ptr(), mesh.normals.data_ptr(), mesh.colors.data_ptr(),
+                           mesh.faces.data_ptr(), mesh.vert_offset.data_ptr(), mesh.face_offset.data_ptr(),
+                           int(mesh.num_classes), int(mesh.max_faces))
+    mean, std = norm if norm is not None else ((0., 0., 0.), (1., 1., 1.))
+    if norm is not None and not all(math.isfinite(float(s)) and float(s) != 0 for s in std):
+        raise _lib.ScflowHipError(f'render_mesh: norm std must be finite and non-zero, got {std!r}')
+    f3 = C.c_float * 3
+    p = _lib.RenderParams(h, w, int(bool(default_lights)), int(bool(seperate_lights)), f3(*map(float, background)),
+                          f3(*map(float, mean)), f3(*map(float, std)))
+    lib = _lib.load()
+    wsb = int(lib.scf_render_workspace_bytes(n, int(mesh.max_faces)))
+    _lib.check(min(wsb, 0), 'scf_render_workspace_bytes')
+    ws = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    zbuf = torch.empty((n, h, w), dtype=torch.float32, device=dev)
+    p2f = torch.empty((n, h, w), dtype=torch.int32, device=dev) if pix_to_face else None
+    img = torch.empty((n, h, w, 4), dtype=torch.float32, device=dev) if images else None
+    rgb = torch.empty((n, 3, h, w), dtype=torch.float32, device=dev) if norm is not None else None
+    _lib.check(lib.scf_render_mesh(
+        C.byref(store), lab.data_ptr(), _mats(rot, n, (3, 3), 'rot'), _mats(trans, n, (3,), 'trans'),
+        _mats(k, n, (3, 3), 'k'), n, C.byref(p), zbuf.data_ptr(),
+        None if p2f is None else p2f.data_ptr(), None if img is None else img.data_ptr(),
+        None if rgb is None else rgb.data_ptr(), ws.data_ptr(), _stream()), 'scf_render_mesh')
+    return dict(zbuf=zbuf, pix_to_face=p2f, images=img, rgb=rgb)
+
+
 def unproject_depth(depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor) -> Tensor:
     n, h, w = depth.shape
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=depth.device)

@@ -4,10 +4,12 @@ Mirrors models/refiner/scflow_refiner.py:18-179 (+ base_refiner.py:17-64):
 same registry name, constructor keys (``configs/refine_models/scflow.py:16-113``
 applies unchanged), attribute names, ``extract_feat`` / ``get_pose`` /
 ``forward_single_pass`` signatures and return structure, same ``state_dict``
-keys.  Renderer, losses, data formatting and PnP re-mapping are outside the hot
-path: their config keys are accepted and ignored, and
-``forward_single_pass`` consumes an already formatted ``data`` dict (what
-``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).
+keys.  Losses and PnP re-mapping are outside the hot path:
+their config keys are accepted and ignored, and ``forward_single_pass`` consumes an
+already formatted ``data`` dict (what ``BaseRefiner.format_data_test`` produces,
+base_refiner.py:79-133).  The config's ``renderer`` dict is ignored too;
+``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
+and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
 from __future__ import annotations
 
@@ -23,8 +25,80 @@ from .registry import REFINERS, build_decoder, build_encoder
 Tensor = torch.Tensor
 
 
+def _as_mask_tensor(mask, device) -> Tensor:
+    """a gt mask as a bool tensor: tensors pass through, mmdet-style mask objects go through to_tensor."""
+    if isinstance(mask, torch.Tensor):
+        return mask.to(device=device, dtype=torch.bool)
+    return mask.to_tensor(dtype=torch.bool, device=device)
+
+
+class _RenderingRefiner:
+    """the renderer-driven data path of BaseRefiner (base_refiner.py:79-133, 205-218) on ``MeshRenderer``:
+    ``attach_renderer``, ``format_data_test`` and ``update_data``.  The constructor ignores the config's
+    ``renderer`` dict (its dataset paths need not exist where the model is built)."""
+
+    renderer = None
+
+    def attach_renderer(self, renderer):
+        """use ``renderer`` (a ``MeshRenderer``, or None to detach) for format_data_test / update_data and for
+        ``test_cfg['cycles'] > 1``; returns self."""
+        self.renderer = renderer
+        return self
+
+    def _need_renderer(self, what: str):
+        if self.renderer is None:
+            raise RuntimeError(f'{what} renders the mesh: attach a renderer first (attach_renderer(MeshRenderer(...)))')
+
+    def format_data_test(self, data_batch: Dict) -> Dict:
+        """base_refiner.py:79-133: concatenate the per-image lists, render every sample at its reference pose and
+        normalise the rendered RGB with ``img_metas[0]['img_norm_cfg']`` (the kernel writes it in NCHW, already
+        normalised).  ``gt_masks`` may be tensors or objects with ``to_tensor``."""
+        self._need_renderer('format_data_test')
+        real_images, annots, meta_infos = data_batch['img'], data_batch['annots'], data_batch['img_metas']
+        per_img_patch_num = [len(images) for images in real_images]
+        real_images = torch.cat(real_images)
+        ref_rotations = torch.cat(annots['ref_rotations'], dim=0)
+        ref_translations = torch.cat(annots['ref_translations'], dim=0)
+        labels = torch.cat(annots['labels'])
+        internel_k = torch.cat(annots['k'])
+        output = dict(real_images=real_images, labels=labels, internel_k=internel_k,
+                      ref_rotations=ref_rotations, ref_translations=ref_translations,
+                      per_img_patch_num=per_img_patch_num, meta_infos=meta_infos)
+        if 'transform_matrix' in annots:
+            output['transform_matrix'] = torch.cat(annots['transform_matrix'])
+        if 'ori_k' in annots:
+            output['ori_k'] = torch.cat([k[None].expand(n, 3, 3) for k, n in zip(annots['ori_k'], per_img_patch_num)])
+        norm = meta_infos[0]['img_norm_cfg']
+        # the reference's torch.Tensor(mean) / 255. (fp32), handed to the kernel as its per-channel constants
+        mean = (torch.tensor(norm['mean'], dtype=torch.float32) / 255.).tolist()
+        std = (torch.tensor(norm['std'], dtype=torch.float32) / 255.).tolist()
+        rgb, depth, mask = self.renderer.render_normalized(ref_rotations, ref_translations, internel_k, labels, mean, std)
+        output.update(rendered_images=rgb, rendered_depths=depth, rendered_masks=mask)
+        if 'depths' in annots:
+            output['real_depths'] = torch.cat(annots['depths'], dim=0)
+        if 'gt_rotations' in annots:
+            output['gt_rotations'] = torch.cat(annots['gt_rotations'], dim=0)
+            output['gt_translations'] = torch.cat(annots['gt_translations'], dim=0)
+        if 'gt_masks' in annots:
+            output['gt_masks'] = torch.cat([_as_mask_tensor(m, real_images.device) for m in annots['gt_masks']], dim=0)
+        return output
+
+    def update_data(self, update_rotations: Tensor, update_translations: Tensor, data: Dict) -> Dict:
+        """base_refiner.py:205-218: re-render at the updated pose.  As in the reference, the new rendered images are
+        NOT normalised with img_norm_cfg (format_data_test's are)."""
+        self._need_renderer('update_data')
+        data['ref_rotations'] = update_rotations
+        data['ref_translations'] = update_translations
+        rgb, depth, mask = self.renderer.render_normalized(update_rotations, update_translations, data['internel_k'],
+                                                           data['labels'])
+        data['rendered_images'] = rgb
+        data['rendered_depths'] = depth
+        data['rendered_masks'] = mask
+        return data
+
+
 @REFINERS.register_module()
-class SCFlowRefiner(HipModule):
+class SCFlowRefiner(_RenderingRefiner, HipModule):
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int,
                  cxt_encoder: dict, encoder: dict, decoder: dict, renderer: Optional[dict] = None,
                  pose_loss_cfg: Optional[dict] = None, flow_loss_cfg: Optional[dict] = None,
@@ -44,7 +118,8 @@ class SCFlowRefiner(HipModule):
             self.real_encoder = enc
         self.decoder = build_decoder(decoder)
         self.context = build_encoder(cxt_encoder)
-        self.renderer = None                    # pytorch3d renderer: out of scope
+        # the config's renderer dict points at dataset paths: it is not built here; attach_renderer() sets one
+        self.renderer = None
         self.max_flow = max_flow
         self.train_cfg = train_cfg or {}
         self.test_cfg = test_cfg or {}
@@ -153,14 +228,29 @@ class SCFlowRefiner(HipModule):
         if return_loss:
             raise NotImplementedError('training is outside the hot path (SURVEY.md section 2)')
         if self.test_cfg.get('cycles', 1) > 1:
-            # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data ->
-            # pytorch3d renderer): outside the hot path.  Refuse instead of silently running one cycle.
-            raise NotImplementedError("test_cfg['cycles'] > 1 needs the renderer between cycles (base_refiner.py:250-258); "
-                                      'render outside and call forward_single_pass / get_pose once per cycle')
+            # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
+            # Without an attached renderer, refuse instead of silently running one cycle.
+            if self.renderer is None:
+                raise NotImplementedError("test_cfg['cycles'] > 1 needs the renderer between cycles (base_refiner.py:250-258); "
+                                          'attach one with attach_renderer(MeshRenderer(...)), or render outside and call '
+                                          'forward_single_pass / get_pose once per cycle')
+            return self.forward_multiple_pass(data, data_batch)
         return self.forward_single_pass(data, data_batch)
 
+    def forward_multiple_pass(self, data: Dict, data_batch: Optional[Dict] = None) -> Dict:
+        """base_refiner.py:249-261: ``test_cfg['cycles']`` passes, re-rendering at each refined pose in between.  The
+        caller's dict is not modified (the reference updates it in place)."""
+        data = dict(data)
+        cycles = self.test_cfg.get('cycles', 1)
+        for i in range(cycles):
+            results = self.forward_single_pass(data, data_batch)
+            if i == cycles - 1:
+                break
+            data = self.update_data(torch.cat(results['rotations']), torch.cat(results['translations']), data)
+        return results
 
-class _FlowRefinerBase(HipModule):
+
+class _FlowRefinerBase(_RenderingRefiner, HipModule):
     """feature extraction, ``get_flow`` and the pose step of the pose-free RAFT refiners
     (models/refiner/raft_refiner_flow_mask.py:88-161, raft_refiner_flow.py, base_flow_refiner.py:99-154).
 
