@@ -488,14 +488,19 @@ int scf_flow_corr_2d3d(const float* flow, const float* depth, const float* occ, 
  *                                    SOLVEPNP_EPNP), base_flow_refiner.py:49-71, pose.py:203-249
  * Inputs: the outputs of scf_flow_corr_2d3d (capacity = points per sample; conf only read by TOPK), K (N,3,3),
  * the reference pose R_ref (N,3,3), t_ref (N,3).  Per sample:
- *   sampling   ALL: every point.  TOPK: the sample_num points of highest conf, ties to the lower index.
+ *   sampling   ALL: every point.  TOPK: the sample_num points of highest conf, ties to the lower index (-0.0 ties
+ *              with +0.0; NaN ranks above +inf); the kept indices are ascending.
  *              RANDOM: sample_num distinct indices of [0, count-1) chosen by a counter-based hash of
  *              (seed, index) -- the reference's randperm(count - 1) quirk kept, its generator not reproduced.
  *              Both keep every point when sample_num > count.
- *   hypotheses `iterations` of them; hypothesis h takes 5 distinct points drawn by a hash of (seed, h) -- the
+ *   hypotheses `iterations` of them; hypothesis h takes 5 distinct points of the m kept ones: draws a = 1..64
+ *              give index hash(seed, h, a) % m, a repeat is skipped, and a hypothesis with fewer than 5 distinct
+ *              points after 64 draws is invalid (hash: pnp_hash in pnp.hip, the splitmix64 finaliser) -- the
  *              sample's position in the batch does not enter, so a sample gives the same bits alone or batched --
- *              and solves EPnP on them (Lepetit et al.: centroid + PCA control points, 12x12 M^T M, the beta cases
- *              N = 1..3 each refined by Gauss-Newton, lowest reprojection error kept; fp64).
+ *              and solves EPnP on them (Lepetit et al.: control points at the centroid and at centroid +
+ *              sqrt(variance) along each principal axis, each axis oriented so that its largest-magnitude component
+ *              is positive; M over normalised camera coordinates K^-1 [u v 1]; 12x12 M^T M, the beta cases
+ *              N = 1..3 each refined by 5 Gauss-Newton steps, lowest summed reprojection distance kept; fp64).
  *   scoring    inlier: projected depth > 0 and reprojection error < reproj_error pixels (NaN: outlier); the
  *              hypothesis with the most inliers wins, ties to the lowest h; all hypotheses run (no early stop).
  *   final      EPnP over every inlier of the winner, re-scored: inliers[n] = its inlier count.

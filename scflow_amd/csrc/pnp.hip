@@ -148,10 +148,12 @@ extern "C" int scf_flow_corr_2d3d(const float* flow, const float* depth, const f
 }
 
 // ---------------------------------------------------------------------------------------------- sampling
-// order-preserving map of a float to uint32 (larger float -> larger key; NaN above +inf, as torch.topk ranks it)
+// order-preserving map of a float to uint32 (larger float -> larger key; NaN above +inf, as torch.topk ranks it).
+// -0.0 == +0.0 as floats, so both take +0.0's key: a tie between them goes to the lower index like any other.
 __device__ __forceinline__ uint32_t pnp_fkey(float f) {
   const uint32_t u = __float_as_uint(f);
   if (f != f) return 0xFFFFFFFFu;
+  if (f == 0.f) return 0x80000000u;
   return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
 }
 
@@ -316,6 +318,9 @@ __device__ bool lsq(const double* A, const double* b, double* x) {
 
 // control points of EPnP (Lepetit et al.): the centroid and the centroid + sqrt(eigenvalue) * axis for the three
 // principal axes of the points.  alpha'_k(p) = axis_k . (p - c0) / sqrt(eigenvalue_k), alpha_0 = 1 - sum alpha'.
+// Each axis is oriented so that its largest-magnitude component (the first of equal ones) is positive: the
+// least-squares null space over noisy points depends on that sign, and Jacobi's own sign is an accident of its
+// rotation order.
 struct EpnpCtl {
   double c0[3], ax[3][3], inv_s[3], cw[4][3];
 };
@@ -340,10 +345,14 @@ __device__ bool epnp_control(const double* m, EpnpCtl& c) {
   const double w[3] = {w0, w1, w2};
   for (int k = 0; k < 3; ++k) {
     const double sq = sqrt(w[k]);
+    int big = 0;
+    for (int i = 1; i < 3; ++i)
+      if (fabs(V[i * 3 + k]) > fabs(V[big * 3 + k])) big = i;
+    const double sgn = V[big * 3 + k] < 0 ? -1.0 : 1.0;
     c.inv_s[k] = 1.0 / sq;
     for (int i = 0; i < 3; ++i) {
-      c.ax[k][i] = V[i * 3 + k];
-      c.cw[k + 1][i] = c.c0[i] + sq * V[i * 3 + k];
+      c.ax[k][i] = sgn * V[i * 3 + k];
+      c.cw[k + 1][i] = c.c0[i] + sq * c.ax[k][i];
     }
   }
   for (int i = 0; i < 3; ++i) c.cw[0][i] = c.c0[i];
