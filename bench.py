@@ -1,7 +1,10 @@
 #!/usr/bin/env python
 """Benchmark of the SCFlow refinement hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--batch B]
+    python bench.py --gpus N --steps K --warmup W [--batch B] [--full]
+
+A plain run sets up, warms up, times the K steps, writes ``--dump-outputs`` if asked and prints the
+result line; everything measured beyond that takes runs of its own and comes with ``--full`` (below).
 
 ``--gpus N`` with N > 1 and no torchrun environment RE-LAUNCHES this script under
 ``python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1`` (one
@@ -26,14 +29,22 @@ elements is replaced by a fixed sample of its flattened values (positions drawn 
 ``numpy.random.default_rng(0)`` from the array's size, sorted), so that the files stay under
 64 MB in all.  Inputs and weights are seeded: the same arguments give the same inputs.
 
-Extra objects on the JSON line:
+Extra objects on the JSON line, from the timed steps themselves (every run):
   roofline      corr-lookup kernel: algorithmic bytes per launch (2904 B/query) /
                 average launch duration measured live with HIP events bound to each launch on the
                 launch stream inside the timed steps, against the 8 TB/s HBM3E peak.
+  roofline_corr_build  the correlation GEMM launch of every timed step, against the MFMA peak.
+and, with ``--full`` only (after the timed steps; ``--no-batch1`` / ``--no-config4`` /
+``--no-cpu-baseline`` drop single ones):
+  roofline_conv every convolution launch of three extra steps, timed per launch, by kernel family;
+                roofline_corr_build.standalone_level0_only: the level-0 GEMM launched on its own.
+  batch1        BASELINE configs[1]: one pair per step, eager and as one hipGraph.
   config4       BASELINE configs[4]: RAFTRefinerFlowMask, 480x640, 12 iterations, batch 8 -- the
                 lookup on a 933 MiB pyramid (larger than the 256 MiB Infinity Cache).
   cpu_baseline  the CPU oracle (oracle/, a port of the reference's torch path) timed on the
                 host cores on a bounded sample of the same workload (rank 0, N=1 only).
+  alt_direct / alt_precision  with ``--alt`` (which implies ``--full``): the step with the direct
+                kernels on every layer, and in the other convolution precision.
 """
 from __future__ import annotations
 
@@ -101,10 +112,14 @@ def parse_args(argv=None):
     ap.add_argument('--precision', choices=['f32', 'f16x3'], default='f32',
                     help='convolution arithmetic: exact fp32 MFMA, or split-fp16 3xMFMA '
                          '(fp32 accumulate, ~22 mantissa bits; see DESIGN.md)')
+    ap.add_argument('--full', action='store_true',
+                    help='after the headline steps, also run the measurements that take runs of their own: per-launch '
+                         'convolution timing (roofline_conv), the standalone correlation GEMM, batch1, config4 and '
+                         'cpu_baseline.  Off by default: a plain run does only what its headline figure needs')
     ap.add_argument('--alt', action='store_true',
                     help='also time the step with the direct kernels on every layer (alt_direct) and in the other '
                          'convolution precision (alt_precision: split-fp16, narrower than the reference\'s fp32 -- never a '
-                         'headline).  Off by default since r6: the two loops cost ~8 s of the default run')
+                         'headline).  Implies --full')
     ap.add_argument('--no-alt', action='store_true', help='(default since r6; kept so that old command lines still parse)')
     ap.add_argument('--no-cpu-baseline', action='store_true')
     ap.add_argument('--no-batch1', action='store_true')
@@ -125,7 +140,9 @@ def parse_args(argv=None):
                     help='launcher self-test (tests/test_bench_launcher.py): the step is a CPU '
                          'stand-in, backend gloo; the line is marked "standin": true and is not a '
                          'measurement')
-    return ap.parse_args(argv)
+    args = ap.parse_args(argv)
+    args.full = args.full or args.alt       # --alt alone still runs what it ran before: the alt loops beside the extras
+    return args
 
 
 # ------------------------------------------------------------------ launcher
@@ -565,7 +582,7 @@ def main():
     conv_launches, cb_us, cb_ev = None, None, []
     alt = None
     alt_direct = None
-    if not standin:
+    if not standin and args.full:
         # Secondary measurements: never allowed to take the headline line down with them.
         try:
             # the kernels that dominate the step by TIME are the fp32 MFMA convolutions: one extra
@@ -804,7 +821,7 @@ def main():
                             '(executed + saved flops) / conv time, for comparison with a per-iteration GRU'}
 
     # ---- config[1]: single pair latency (rank 0, informational) ----
-    if rank == 0 and world == 1 and not standin and not args.no_batch1:
+    if rank == 0 and world == 1 and not standin and args.full and not args.no_batch1:
         try:
             from scflow_amd.graph import GraphedRefiner
             b1 = make_batch(1, seed=5, device=device)
@@ -850,7 +867,7 @@ def main():
         except Exception as exc:      # pragma: no cover - informational block, never fatal
             print(f'[bench] batch-1 block failed: {exc!r}', file=sys.stderr)
 
-    if rank == 0 and world == 1 and not standin and not args.no_config4:
+    if rank == 0 and world == 1 and not standin and args.full and not args.no_config4:
         try:
             ops.set_conv_precision(args.precision)
             result['config4'] = config4_block(device, result.get('_pmc_config4'))
@@ -861,7 +878,7 @@ def main():
         result['alt_precision'] = alt
         if alt_direct:
             result['alt_direct'] = alt_direct
-    if rank == 0 and world == 1 and not standin and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and not standin and args.full and not args.no_cpu_baseline:
         try:
             result['cpu_baseline'] = cpu_baseline(sd, args.iters, pairs=args.batch)
         except Exception as exc:      # pragma: no cover

@@ -53,6 +53,17 @@ def test_bench_refuses_without_gpus():
     assert r.returncode == 2 and 'refusing' in r.stderr
 
 
+def test_secondary_measurements_are_opt_in():
+    """a plain run does only what its headline needs; batch1 / config4 / cpu_baseline / roofline_conv come with --full,
+    and --alt (whose loops always ran beside those) implies it."""
+    sys.path.insert(0, ROOT)
+    import bench
+    plain = bench.parse_args(['--gpus', '1', '--steps', '20', '--warmup', '5'])
+    assert not plain.full and not plain.alt
+    assert bench.parse_args(['--full']).full and not bench.parse_args(['--full']).alt
+    assert bench.parse_args(['--alt']).full
+
+
 def test_counter_summaries_are_bound_to_the_kernel_sources():
     """bench.py attaches profiles/lookup_pmc.json / *_mfma_pmc.json (separate rocprofv3 --pmc passes) only when they
     record the hashes of today's kernel sources (VERDICT r5 weak #7): no hashes -> stale; one changed file -> stale, named."""

@@ -4,10 +4,11 @@
 # Counter passes are their own runs (--pmc with --kernel-trace only, one counter per pass).
 set -u
 TAG=${1:-r2}
+ROOT=$(cd "$(dirname "$0")/.." && pwd)      # before the cd below: bench.py is called by absolute path
 OUT=$GRAFT_REPO_ROOT/gpurun_out/profiles_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-B="python $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --min-seconds 0.3 --min-warmup-seconds 0.1 --no-cpu-baseline --no-batch1 --no-alt"
+B="python $ROOT/bench.py --full --steps 3 --warmup 1 --min-seconds 0.3 --min-warmup-seconds 0.1 --no-cpu-baseline --no-batch1 --no-alt"
 # every profiler pass is time-bounded: a faulting child under rocprofv3 otherwise hangs until the box limit
 timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats_f32 -o f32 -- $B --precision f32 > $OUT/bench_f32.log 2>&1
 # (r6: no f16x3 pass any more -- the split-fp16 line is opt-in (bench.py --alt) and never a headline)

@@ -5,7 +5,7 @@
 #              the parity tests that carry a plan against the freshly recorded one
 #   measured   the tests that print [measured] lines (Winograd stress, GRU drift, configs[2]/[4]) with -s
 #   smoke      __graft_entry__.smoke()
-#   bench      python bench.py (defaults)
+#   bench      python bench.py --full (the headline line and every secondary measurement)
 #   profiles   tools/collect_profiles.sh <tag>, the counter summaries, the batch-32-only kernel trace, tools/lab/coissue
 #              (tools/publish_profiles.py <tag> then copies what is cited into profiles/)
 set -u
@@ -38,7 +38,7 @@ PY
     smoke)
       timeout 600 python __graft_entry__.py smoke 2>&1 | tail -3 | tee $OUT/smoke.log ;;
     bench)
-      timeout 900 python bench.py --top-layers 80 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
+      timeout 900 python bench.py --full --top-layers 80 > $OUT/bench.json 2> $OUT/bench.err; tail -c 1500 $OUT/bench.json; tail -3 $OUT/bench.err ;;
     profiles)      # rocprofv3 passes of bench.py (stats f32 / f16x3, FETCH, WRITE, SQ MFMA), summaries, batch-32-only trace, co-issue lab
       bash tools/collect_profiles.sh $TAG > $OUT/collect.log 2>&1; tail -2 $OUT/collect.log
       P=$R/gpurun_out/profiles_$TAG
