@@ -55,6 +55,9 @@ typedef struct scf_conv_log_entry {
   int32_t Cin, Cout, KH, KW, stride, Ho, Wo, N;
   int32_t mode;               /* SCF_CONV_*                                                        */
   int32_t paired;             /* scf_conv2d_pair: 0 = its own launch, 1 / 2 = first / second layer of one merged launch */
+  int32_t variant;            /* merged launches: the layer's captured instantiation (family-specific, ScfLaunchCap::variant:
+                                 K-split {NG 1 | 2} x {dword | x4 staging} = 0..3, thin-input channel blocks 1 / 2, thin-output
+                                 K * 100 + CO * 10 + unroll, quarter-domain 10 + x4, pair kernel 20 + x4); -1 otherwise */
 } scf_conv_log_entry;
 int scf_conv_log_enable(int capacity);
 /* measurement knobs (A/B runs of kernel variants from bench.py / tools): returns the previous value, or

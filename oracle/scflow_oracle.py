@@ -345,14 +345,16 @@ def scflow_decoder(feat_render: Tensor, feat_real: Tensor, h_feat: Tensor, cxt_f
 
 
 def extract_feat(render_images: Tensor, real_images: Tensor, sd: SD, *, h_channels=128,
-                 cxt_channels=128):
+                 cxt_channels=128, feat_kind: str = 'IN', cxt_kind: str = 'BN'):
     """refiner/scflow_refiner.py:88-110: shared IN encoder on real and rendered
     image (seperate_encoder=False -> same weights, base_refiner.py:36-39, key
     prefix 'render_encoder.'), BN context encoder on the rendered image, split
-    -> tanh / relu."""
-    real = raft_encoder(real_images, sd, 'real_encoder.', 'IN')
-    rend = raft_encoder(render_images, sd, 'render_encoder.', 'IN')
-    cxt = raft_encoder(render_images, sd, 'context.', 'BN')
+    -> tanh / relu.  ``feat_kind`` / ``cxt_kind``: the encoders' ``norm_cfg`` types
+    ('IN', 'BN'; 'SyncBN' is BatchNorm at inference)."""
+    fk, ck = ('BN' if k == 'SyncBN' else k for k in (feat_kind, cxt_kind))
+    real = raft_encoder(real_images, sd, 'real_encoder.', fk)
+    rend = raft_encoder(render_images, sd, 'render_encoder.', fk)
+    cxt = raft_encoder(render_images, sd, 'context.', ck)
     h, c = torch.split(cxt, [h_channels, cxt_channels], dim=1)
     return rend, real, torch.tanh(h), torch.relu(c)
 
@@ -361,11 +363,13 @@ def get_pose(render_images: Tensor, real_images: Tensor, ref_rotation: Tensor,
              ref_translation: Tensor, depth: Tensor, internel_k: Tensor, label: Tensor,
              sd: SD, *, iters: int = 8, init_flow: Tensor | None = None,
              mask_flow: bool = False, mask_corr: bool = False,
-             depth_transform: str = 'exp', label_mode: int = 0, radius: int = 4):
+             depth_transform: str = 'exp', label_mode: int = 0, radius: int = 4,
+             feat_kind: str = 'IN', cxt_kind: str = 'BN'):
     """refiner/scflow_refiner.py:112-142 ``SCFlowRefiner.get_pose``
     (invalid_flow_num = 0 at inference, :142); ``mask_flow`` / ``mask_corr``: the decoder's
-    constructor switches (scflow_decoder.py:199-205, both False in configs/refine_models/scflow.py)."""
-    fr, fl, h, c = extract_feat(render_images, real_images, sd)
+    constructor switches (scflow_decoder.py:199-205, both False in configs/refine_models/scflow.py);
+    ``feat_kind`` / ``cxt_kind``: the encoders' norm kinds (``extract_feat``)."""
+    fr, fl, h, c = extract_feat(render_images, real_images, sd, feat_kind=feat_kind, cxt_kind=cxt_kind)
     if init_flow is None:
         n, _, H, W = real_images.shape
         init_flow = torch.zeros((n, 2, H, W), dtype=torch.float32)

@@ -76,7 +76,7 @@ class GruPass(C.Structure):
 
 class ConvLogEntry(C.Structure):
     """mirror of ``scf_conv_log_entry`` (include/scflow_hip_prof.h)."""
-    _fields_ = [(n, C.c_int32) for n in ('kernel', 'Cin', 'Cout', 'KH', 'KW', 'stride', 'Ho', 'Wo', 'N', 'mode', 'paired')]
+    _fields_ = [(n, C.c_int32) for n in ('kernel', 'Cin', 'Cout', 'KH', 'KW', 'stride', 'Ho', 'Wo', 'N', 'mode', 'paired', 'variant')]
 
 
 KERNEL_NAMES = {1: 'thin', 2: 'taps', 3: 'winograd', 4: 'winograd F(2,5)', 5: 'f16x3', 6: 'direct-dma',

@@ -726,7 +726,7 @@ extern "C" int scf_conv_log_read(scf_conv_log_entry* out, int max_entries) {
   return n;
 }
 
-static void conv_log_push(const scf_conv_desc* d, int which, int paired);
+static void conv_log_push(const scf_conv_desc* d, int which, int paired, int variant = -1);
 extern "C" int scf_conv2d(const scf_conv_desc* d, scf_stream_t stream) {
   ConvReq r;
   const int rc = conv2d_walk(d, stream, r);
@@ -734,7 +734,7 @@ extern "C" int scf_conv2d(const scf_conv_desc* d, scf_stream_t stream) {
   return rc;
 }
 
-static void conv_log_push(const scf_conv_desc* d, int which, int paired) {
+static void conv_log_push(const scf_conv_desc* d, int which, int paired, int variant) {
   if (g_log_cap.load(std::memory_order_relaxed) <= 0) return;
   std::lock_guard<std::mutex> lk(g_log_mu);
   if ((int)g_log.size() >= g_log_cap.load()) return;
@@ -742,7 +742,7 @@ static void conv_log_push(const scf_conv_desc* d, int which, int paired) {
   e.kernel = which; e.Cin = d->C0 + d->C1; e.Cout = d->Cout; e.KH = d->KH; e.KW = d->KW; e.stride = d->stride;
   e.Ho = (d->H + 2 * d->pad_h - d->KH) / d->stride + 1;
   e.Wo = (d->W + 2 * d->pad_w - d->KW) / d->stride + 1;
-  e.N = d->N; e.mode = d->mode; e.paired = paired;
+  e.N = d->N; e.mode = d->mode; e.paired = paired; e.variant = variant;
   g_log.push_back(e);
 }
 
@@ -816,8 +816,8 @@ extern "C" int scf_conv2d_pair(const scf_conv_desc* a, const scf_conv_desc* b, s
     if (launch && pays) {
       const int rc = swap ? launch(cb, ca, scf_stream(stream)) : launch(ca, cb, scf_stream(stream));
       if (rc == SCF_OK) {
-        conv_log_push(a, fa, 1);
-        conv_log_push(b, fb, 2);
+        conv_log_push(a, fa, 1, ca.variant);
+        conv_log_push(b, fb, 2, cb.variant);
         return SCF_OK;
       }
       if (rc != SCF_EUNSUPPORTED) return rc;

@@ -267,14 +267,21 @@ class RAFTEncoder(HipModule):
                           act_split=head_split)
 
 
+def encoder_pair_supported(fe: 'RAFTEncoder', ce: 'RAFTEncoder') -> bool:
+    """``raft_encoder_pair`` walks an InstanceNorm feature encoder and a BatchNorm context encoder of the same layer geometry;
+    other norm kinds run the two encoders one after the other."""
+    return (fe.kind == 'IN' and ce.kind == 'BN' and fe.stem_stride == ce.stem_stride and fe.in_channels == ce.in_channels
+            and fe.res_layers == ce.res_layers)
+
+
 def raft_encoder_pair(fe: 'RAFTEncoder', xf: Tensor, ce: 'RAFTEncoder', xc: Tensor, out_c: Optional[Tensor] = None,
                       head_act: int = ACT_NONE, head_act2: int = ACT_NONE, head_split: int = 0) -> Tuple[Tensor, Tensor]:
     """the feature encoder (InstanceNorm) on ``xf`` and the context encoder (BatchNorm, folded) on ``xc`` -- two independent
     passes over layers of identical geometry -- walked TOGETHER, every pair of convolutions through ``ops.conv2d_pair``: at
     batch 1-4 the context encoder's launches ride in the feature encoder's wherever both grids fit the chip (r6; before: one
     after the other, or side by side on a second stream).  Same kernels per layer as the two separate passes, same bits."""
-    if fe.kind != 'IN' or ce.kind != 'BN':
-        raise ValueError('raft_encoder_pair: (InstanceNorm feature encoder, BatchNorm context encoder)')
+    if not encoder_pair_supported(fe, ce):
+        raise ValueError('raft_encoder_pair: (InstanceNorm feature encoder, BatchNorm context encoder) of one layer geometry')
     pf, pc = fe.packed, ce.packed
     yf, yc = ops.conv2d_pair((pf['stem'], xf), (pc['stem'], xc, dict(act=ACT_RELU)))
     ops.instance_norm(yf, relu=True, out=yf)

@@ -630,13 +630,31 @@ def conv2d(pc: PackedConv, x0: Tensor, x1: Optional[Tensor] = None, out: Optiona
     return out
 
 
+def _pair_operand(layer):
+    """(descriptor, output, joined input or None) of one layer of ``conv2d_pair``.  Two input segments whose boundary no kernel
+    takes are joined first, as ``conv2d`` does on SCF_EUNSUPPORTED (the pair's fallback would otherwise refuse the layer): asked
+    of the library for layers that pass an ``x1`` only -- the refiner's pairs never do.  The caller holds the joined tensor until
+    the launch is enqueued: freed earlier, its memory could become the other layer's output."""
+    pc, x0 = layer[0], layer[1]
+    kw = dict(layer[2]) if len(layer) > 2 else {}
+    d, out = conv2d(pc, x0, _launch=False, **kw)
+    if kw.get('x1') is not None and kw.get('kslices', 1) <= 1:
+        info = (C.c_int32 * 4)()
+        if _lib.load().scf_conv2d_query(C.byref(d), info) == -2:
+            x0, kw['x1'], kw['out'] = torch.cat([x0, kw['x1']], 1), None, out
+            d, out = conv2d(pc, x0, _launch=False, **kw)
+            return d, out, x0
+    return d, out, None
+
+
 def conv2d_pair(a, b):
     """two INDEPENDENT convolutions, ``a`` and ``b`` = ``(PackedConv, x0[, kwargs of conv2d])``, through ``scf_conv2d_pair``: ONE
     launch where both fall to the same small-grid kernel instantiation and fit the chip together, else one after the other.
     Returns the two outputs (bit-identical to two ``conv2d`` calls either way)."""
-    da, oa = conv2d(a[0], a[1], _launch=False, **(a[2] if len(a) > 2 else {}))
-    db, ob = conv2d(b[0], b[1], _launch=False, **(b[2] if len(b) > 2 else {}))
+    da, oa, ja = _pair_operand(a)
+    db, ob, jb = _pair_operand(b)
     _lib.check(_lib.load().scf_conv2d_pair(C.byref(da), C.byref(db), _stream()), 'scf_conv2d_pair')
+    del ja, jb          # the joined inputs (if any) lived until the launch was enqueued on this stream
     return oa, ob
 
 
@@ -871,12 +889,13 @@ class record_conv_kernels:
     (``scf_conv_log_*`` of scflow_hip_prof.h).  Tag = ``'<Cin>-><Cout> <KH>x<KW>/s<stride> @<Ho>x<Wo> N<N>'``
     (the tag ``conv_timing`` uses), family = one of ``_lib.KERNEL_NAMES``' values.  Parity tests assert with
     it that the kernel they name really ran (the choice depends on grid size and device).  The recorder's ``paired`` lists,
-    launch by launch, how ``scf_conv2d_pair`` ran it: 0 = its own launch, 1 / 2 = first / second layer of one merged launch."""
+    launch by launch, how ``scf_conv2d_pair`` ran it: 0 = its own launch, 1 / 2 = first / second layer of one merged launch;
+    ``variants`` the instantiation a merged launch ran each of its layers with (``scf_conv_log_entry.variant``, -1 otherwise)."""
 
     _active = False      # the library keeps ONE process-wide log: a nested recorder would clear the outer one's records
 
     def __init__(self, capacity: int = 1 << 16) -> None:
-        self.capacity, self.ran, self.paired = capacity, [], []
+        self.capacity, self.ran, self.paired, self.variants = capacity, [], [], []
 
     def __enter__(self):
         if record_conv_kernels._active:
@@ -896,6 +915,7 @@ class record_conv_kernels:
             self.ran.append((f'{e.Cin}->{e.Cout} {e.KH}x{e.KW}/s{e.stride} @{e.Ho}x{e.Wo} N{e.N}',
                              _lib.KERNEL_NAMES.get(e.kernel, str(e.kernel))))
             self.paired.append(e.paired)
+            self.variants.append(e.variant)
         return False
 
 

@@ -18,7 +18,7 @@ from typing import Dict, Optional, Tuple, Union
 import torch
 
 from . import ops
-from .modules import HipModule, raft_encoder_pair
+from .modules import HipModule, encoder_pair_supported, raft_encoder_pair
 from .ops import ACT_RELU, ACT_TANH, small_work
 from .registry import REFINERS, build_decoder, build_encoder
 
@@ -156,8 +156,9 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         rend = render_images.contiguous()
         ov_ctx = small_work(n, H, W, 'context')
         fork = ops.fork_point() if ov_ctx else None     # the context encoder may start from here
-        if not self.seperate_encoder and ops.branch_mode(n, H, W, 'context') == 2 and ops._CONV_EVENTS is None:
-            # r6: the context encoder's launches ride in the feature encoder's (modules.raft_encoder_pair)
+        if (not self.seperate_encoder and ops.branch_mode(n, H, W, 'context') == 2 and ops._CONV_EVENTS is None
+                and encoder_pair_supported(self.render_encoder, self.context)):
+            # r6: the context encoder's launches ride in the feature encoder's (modules.raft_encoder_pair; IN | BN encoders)
             both = torch.empty((2 * n, 3, H, W), dtype=torch.float32, device=dev)
             ops.copy_channels(rend, both[:n])
             ops.copy_channels(real_images.contiguous(), both[n:])

@@ -892,3 +892,50 @@ def test_merged_launches_of_a_batch_1_step(golden_dir):
                  (('2->128 7x7/s1 @32x32 N1', 'taps'), ('1->64 3x3/s1 @32x32 N1', 'taps')),
                  (('128->64 3x3/s1 @32x32 N1', 'direct-dma'), ('64->32 3x3/s1 @32x32 N1', 'direct-dma'))]
     assert merged == encoders + iteration * 8, merged
+
+
+@pytest.mark.parametrize('n', [1, 5])
+@pytest.mark.parametrize('feat_kind,cxt_kind', [('IN', 'BN'), ('BN', 'BN'), ('IN', 'IN'), ('BN', 'IN'), ('SyncBN', 'BN')])
+def test_encoder_norm_kinds_vs_oracle(feat_kind, cxt_kind, n):
+    """every (feature, context) encoder norm kind RAFTEncoder accepts, at batch 1 (where the default IN | BN encoders are walked
+    together, modules.raft_encoder_pair) and batch 5 (one after the other): extract_feat's four outputs and a 2-iteration get_pose
+    against the oracle with the same kinds.  Other kinds than IN | BN take the sequential path at every batch size."""
+    cfg = scflow_amd.scflow_model_cfg(iters=2)
+    cfg['encoder']['norm_cfg'] = dict(type=feat_kind)
+    cfg['cxt_encoder']['norm_cfg'] = dict(type=cxt_kind)
+    m = scflow_amd.build_refiner(cfg)
+    sd = scflow_amd.fill_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, seed=0)
+    m.load_state_dict(sd, strict=True)
+    m = m.to(DEV)
+    inp = scflow_amd.make_inputs(n, 256, 256, seed=140 + n)
+    d = {k: v.to(DEV) for k, v in inp.items()}
+    kinds = dict(feat_kind=feat_kind, cxt_kind=cxt_kind)
+    with torch.no_grad():
+        want_f = oracle.extract_feat(inp['render_images'], inp['real_images'], sd, **kinds)
+        want = oracle.get_pose(inp['render_images'], inp['real_images'], inp['ref_rotation'], inp['ref_translation'],
+                               inp['depth'], inp['internel_k'], inp['label'], sd, iters=2, **kinds)
+    got_f = m.extract_feat(d['render_images'], d['real_images'])
+    got_f = [t.clone() for t in got_f]
+    # encoder tolerances of test_full_refiner_golden: an InstanceNorm encoder's outputs 9e-5, a BatchNorm encoder's 2.5e-5
+    fa, ca = (9e-5 if k == 'IN' else 2.5e-5 for k in (feat_kind, cxt_kind))
+    for nm, g_, w_, tol in zip(('feat_render', 'feat_real', 'h_feat', 'cxt_feat'), got_f, want_f, (fa, fa, ca, ca)):
+        close(g_, w_, atol=tol, what=f'{feat_kind} | {cxt_kind}, N={n}: {nm}')
+    if (feat_kind, cxt_kind) == ('IN', 'BN') and n == 1:
+        keep = set(ops.PAIR_BRANCHES)
+        ops.PAIR_BRANCHES = keep - {'context'}          # the same encoders one after the other: the same bits
+        try:
+            seq = m.extract_feat(d['render_images'], d['real_images'])
+        finally:
+            ops.PAIR_BRANCHES = keep
+        for a, b in zip(got_f, seq):
+            assert torch.equal(a, b)
+    got = m.get_pose(d['render_images'], d['real_images'], d['ref_rotation'], d['ref_translation'], d['depth'],
+                     d['internel_k'], d['label'])
+    valid = inp['depth'] > 0
+    for it in range(2):
+        epe_pose = oracle.end_point_error(got[0][it].cpu(), want[0][it], valid)
+        epe_pred = oracle.end_point_error(got[1][it].cpu(), want[1][it])
+        assert epe_pose <= 1e-3, f'iter {it}: EPE(flow_from_pose) {epe_pose:.2e}'
+        assert epe_pred <= 1e-3, f'iter {it}: EPE(flow_from_pred) {epe_pred:.2e}'
+    close(got[2][-1], want[2][-1], atol=2e-5, what='final rotation')
+    close(got[3][-1], want[3][-1], atol=1e-2, rtol=2e-5, what='final translation (mm)')
