@@ -79,7 +79,18 @@ __device__ __forceinline__ int scf_xcd_remap(int b, int nblk) {
 // sigmoid / tanh on the hardware transcendental units (v_exp_f32, v_rcp_f32: ~1 ulp each) for the
 // fused convolution epilogues: ~6 vector instructions instead of ~35 for the libm expansions --
 // vector issue slots are the scarce resource next to a co-resident wave's MFMA stream.
-// |error| <= ~3e-7 (sigmoid, relative) / ~1.5e-7 (tanh, absolute).
+// ABSOLUTE error, any v (inf and NaN included: sigmoid(+-inf) = 1 / 0, tanh(+-inf) = +-1, NaN -> NaN): |error| <= 3e-7
+// (sigmoid) / 1.5e-7 (tanh), asserted through every fused epilogue that uses them against float64 on a dense sweep of exact
+// pre-activations (tests/test_gpu_gru.py); measured on the MI355X 9.2e-8 / 1.2e-7.  0 <= sigmoid <= 1 and |tanh| <= 1
+// hold exactly, tanh is odd bit for bit, both are monotone within those bounds.
+// The RELATIVE error is not bounded by a constant (measured):
+//   sigmoid, v >= 0: 1.4e-7.  v < 0: grows with |v| (__expf(x) = exp2(x * log2e) with the product rounded to fp32, so
+//     ~ |v| * 1.44 * 2^-24): 1.3e-7 on [-1, 0), 3.0e-7 on [-5, -1), 9.8e-7 on [-20, -5), 1.5e-6 down to -87; below
+//     v ~ -87.3 the result would be a denormal and is 0.
+//   tanh: 1 - t cancels near 0: 1.3e-7 for |v| >= 1, 1.5e-6 on [1e-2, 1), 1.6e-4 on [1e-4, 1e-2), 1.7e-2 on
+//     [1e-6, 1e-4), and the result is 0 for |v| < ~1.5e-8, where t rounds to 1 (libm's tanhf returns v there).
+// The GRU blend (1 - z) h + z q needs the absolute figures only.  The libm forms below (scf_apply_act) meet the same
+// absolute bounds (measured 8.7e-8 / 6.3e-8); one pre-activation differs between the two forms by up to 1.3e-7.
 __device__ __forceinline__ float scf_fast_sigmoid(float v) {
   return __builtin_amdgcn_rcpf(1.f + __expf(-v));
 }
