@@ -575,6 +575,57 @@ int scf_render_mesh(const scf_mesh_store* mesh, const int32_t* labels, const flo
                     const float* K, int N, const scf_render_params* params, float* zbuf, int32_t* pix_to_face,
                     float* rgba, float* rgb_nchw, void* workspace, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Object patches from full frames.   replaces the val_pipeline of configs/refine_datasets/ycbv_*.py (ComputeBbox,
+ *                                    Crop, Resize(keep_ratio=True), Pad, RemapPose(keep_intrinsic=False), Normalize),
+ *                                    which the reference runs on the CPU through cv2 / mmcv.
+ * Added without a version bump (SCF_VERSION stays at .3), as the renderer's entries were: the presence of
+ * scf_patch_workspace_bytes, scf_patch_boxes and scf_patch_extract marks the feature.  patch.hip states the
+ * semantics in full; in short, per object n:
+ *   box        min / max of u = p.x / (p.z + 1e-8), v likewise, p = K (R X + t), over every vertex_stride-th vertex
+ *              of class labels[n] (fp32).  Invalid: label outside [0, num_classes), empty class, any p.z <= 0.
+ *   crop       Crop's rectangle from the box (aspect_ratio / keep_ratio, size_ratio, min_expand, clip_border) in fp64,
+ *              truncated toward zero, ends inclusive; pixels outside the frame are crop_pad_val.  With crop_in
+ *              (N,4) int32 the caller's rectangles (x1, y1, x2, y2) are used instead and mesh, labels, R, t may be
+ *              NULL (the reference's crop_bbox_field when a detector box is at hand).
+ *   resize     s = resize / max(ph, pw); OpenCV's generic 8-bit INTER_LINEAR (11-bit fixed-point coefficients).
+ *   pad        to (out_h, out_w) with pad_val, centred when center != 0.
+ *   intrinsics transform_matrix = P S C, k = transform_matrix K, fp64 rounded once; poses pass through.
+ *   normalize  out (N,3,out_h,out_w) = (float(v) - mean[c]) * float(1.0 / std[c]), c the output channel; the frame is
+ *              read as BGR and to_rgb swaps channels 0 and 2.  crop_pad_val / pad_val are in the frame's channel order.
+ * An invalid object gets an all-pad_val patch, valid = 0, a zero rectangle, scale 1, an identity transform_matrix and
+ * k = K (the kernels cannot raise).  scf_patch_boxes writes box (N,4) fp32 (the projected box
+ * (x1, y1, x2, y2); may be NULL; zeros for an invalid object or with crop_in), crop (N,4) int32, scale (N), transform_matrix (N,3,3),
+ * k (N,3,3), valid (N) int32 and one record per object into workspace (scf_patch_workspace_bytes(N) bytes of device
+ * memory); scf_patch_extract reads those records on the device, so nothing passes through the host.  frames is
+ * (F,frame_h,frame_w,3) uint8, frame_index (N) int32 selects each object's frame (outside [0, F): all-pad_val patch).
+ * --------------------------------------------------------------------------------- */
+typedef struct scf_patch_params {
+  double aspect_ratio;           /* Crop aspect_ratio (> 0), read when keep_ratio == 0                */
+  double size_ratio;             /* Crop size_range, both ends (> 0)                                  */
+  double min_expand;             /* Crop min_expand (>= 0)                                            */
+  int32_t out_h, out_w;          /* Pad size, 1..8192 each                                            */
+  int32_t resize;                /* Resize img_scale: longer side of the resized patch, 1..min(out_h, out_w) */
+  int32_t vertex_stride;         /* the box takes every vertex_stride-th vertex (>= 1)                */
+  int32_t keep_ratio;            /* Crop keep_ratio                                                   */
+  int32_t clip_border;           /* Crop clip_border                                                  */
+  int32_t fix_clip_border_quirk; /* 0: lower edge y2 + bh/2 under clip_border, as the reference; 1: yc + bh/2 */
+  int32_t center;                /* Pad center                                                        */
+  int32_t to_rgb;                /* Normalize to_rgb                                                  */
+  int32_t crop_pad_val[3];       /* Crop pad_val, 0..255, frame channel order                         */
+  int32_t pad_val[3];            /* Pad pad_val['img'], 0..255, frame channel order                   */
+  float mean[3];                 /* Normalize mean / std in grey levels, output channel order; std != 0 */
+  float std[3];
+} scf_patch_params;
+/* bytes of workspace (the per-object records) scf_patch_boxes writes and scf_patch_extract reads, or SCF_EINVAL */
+int64_t scf_patch_workspace_bytes(int N);
+int scf_patch_boxes(const scf_mesh_store* mesh, const int32_t* labels, const float* R, const float* t,
+                    const float* K, const int32_t* crop_in, int N, int frame_h, int frame_w,
+                    const scf_patch_params* params, float* box, int32_t* crop, float* scale, float* transform_matrix,
+                    float* k, int32_t* valid, void* workspace, scf_stream_t stream);
+int scf_patch_extract(const uint8_t* frames, int F, int frame_h, int frame_w, const int32_t* frame_index, int N,
+                      const void* workspace, const scf_patch_params* params, float* out, scf_stream_t stream);
+
 /* filter_flow_by_mask (models/utils/flow.py:6-26), in place on flow (N,2,H,W): a vector is set
  * to invalid_num when both components are >= invalid_num or when mask (N,H,W), sampled
  * bilinearly (zeros padding) at the vector's end point, is < 0.9.  The end point is normalised

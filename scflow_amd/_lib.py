@@ -115,6 +115,15 @@ class RenderParams(C.Structure):
                 ('background', C.c_float * 3), ('norm_mean', C.c_float * 3), ('norm_std', C.c_float * 3)]
 
 
+class PatchParams(C.Structure):
+    """mirror of ``scf_patch_params`` (include/scflow_hip.h)."""
+    _fields_ = [('aspect_ratio', C.c_double), ('size_ratio', C.c_double), ('min_expand', C.c_double),
+                ('out_h', C.c_int32), ('out_w', C.c_int32), ('resize', C.c_int32), ('vertex_stride', C.c_int32),
+                ('keep_ratio', C.c_int32), ('clip_border', C.c_int32), ('fix_clip_border_quirk', C.c_int32),
+                ('center', C.c_int32), ('to_rgb', C.c_int32), ('crop_pad_val', C.c_int32 * 3),
+                ('pad_val', C.c_int32 * 3), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
+
+
 class IterGN(C.Structure):
     """mirror of ``scf_iter_gn``."""
     _fields_ = [('gamma', _fp), ('beta', _fp), ('out', _fp),
@@ -224,6 +233,11 @@ SIGNATURES = {
     'scf_render_workspace_bytes': (C.c_int64, [C.c_int, C.c_int]),
     'scf_render_mesh': (C.c_int, [C.POINTER(MeshStore), _fp, _fp, _fp, _fp, C.c_int, C.POINTER(RenderParams),
                                   _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_patch_workspace_bytes': (C.c_int64, [C.c_int]),
+    'scf_patch_boxes': (C.c_int, [C.POINTER(MeshStore), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                  C.POINTER(PatchParams), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_patch_extract': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.POINTER(PatchParams), _fp,
+                                    _fp]),
     'scf_unproject_depth': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_resize_bilinear': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),

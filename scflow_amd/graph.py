@@ -14,11 +14,11 @@ buffers the graph reads) and calls the instance without arguments: no copies, on
 """
 from __future__ import annotations
 
-from typing import Dict, Optional
+from typing import Dict, Optional, Sequence
 
 import torch
 
-__all__ = ['GraphedRefiner']
+__all__ = ['GraphedRefiner', 'GraphedPatches']
 
 _INPUTS = ('render_images', 'real_images', 'ref_rotation', 'ref_translation', 'depth',
            'internel_k', 'label')
@@ -69,5 +69,47 @@ class GraphedRefiner:
                     dst.copy_(src, non_blocking=True)
             for dsts, srcs in groups.values():
                 torch._foreach_copy_(dsts, srcs)
+        self.graph.replay()
+        return self.static_out
+
+
+_PATCH_INPUTS = ('frames', 'ref_rotations', 'ref_translations', 'k', 'labels')
+
+
+class GraphedPatches:
+    """hipGraph capture of one ``PatchPipeline`` call (scflow_amd/patches.py): the label conversion, the box launch and
+    the patch launch, a straight chain on one stream with no parallel branch.  ``example`` holds frames,
+    ref_rotations, ref_translations, k and labels; ``per_img_patch_num`` (a host list) is fixed per instance.  Write
+    new inputs into ``static_in[name]`` (or pass them) and call: the returned ``data_batch`` is persistent and is
+    overwritten by the next call."""
+
+    def __init__(self, pipeline, example: Dict[str, torch.Tensor], per_img_patch_num: Sequence[int], warmup: int = 1) -> None:
+        if warmup < 1:
+            # the eager pass uploads the mesh store and the frame index: neither may happen in the graph
+            raise ValueError('GraphedPatches needs at least one eager warm-up pass (warmup >= 1)')
+        self.pipeline = pipeline
+        self.counts = [int(n) for n in per_img_patch_num]
+        self.static_in = {k: example[k].clone().contiguous() for k in _PATCH_INPUTS}
+        cs = torch.cuda.Stream()
+        cs.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(cs):
+            for _ in range(warmup):
+                self._run()
+        torch.cuda.current_stream().wait_stream(cs)
+        torch.cuda.synchronize()
+        self.graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(self.graph, stream=cs):
+            self.static_out = self._run()
+        torch.cuda.synchronize()
+
+    def _run(self):
+        s = self.static_in
+        return self.pipeline(s['frames'], self.counts, s['ref_rotations'], s['ref_translations'], s['k'], s['labels'])
+
+    def __call__(self, inputs: Optional[Dict[str, torch.Tensor]] = None):
+        if inputs is not None:
+            for k in _PATCH_INPUTS:
+                if k in inputs and inputs[k] is not self.static_in[k]:
+                    self.static_in[k].copy_(inputs[k], non_blocking=True)
         self.graph.replay()
         return self.static_out

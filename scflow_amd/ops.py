@@ -1442,6 +1442,136 @@ def render_mesh(mesh, labels: Tensor, rot: Tensor, trans: Tensor, k: Tensor, ima
     return dict(zbuf=zbuf, pix_to_face=p2f, images=img, rgb=rgb)
 
 
+def _triple(v, name: str) -> Tuple[float, float, float]:
+    vals = tuple(float(x) for x in v) if isinstance(v, (list, tuple)) or hasattr(v, '__len__') else (float(v),) * 3
+    if len(vals) != 3:
+        raise _lib.ScflowHipError(f'{name}: expected a scalar or three values, got {v!r}')
+    return vals
+
+
+def patch_params(out_size: Tuple[int, int] = (256, 256), resize: int = 256, *, size_ratio: float = 1.1,
+                 aspect_ratio: float = 1.0, keep_ratio: bool = False, min_expand: float = 0.0,
+                 clip_border: bool = False, fix_clip_border_quirk: bool = False, center: bool = True,
+                 crop_pad_val=128, pad_val=128, mean=(0., 0., 0.), std=(255., 255., 255.), to_rgb: bool = True,
+                 vertex_stride: int = 1) -> '_lib.PatchParams':
+    """``scf_patch_params`` from the pipeline's settings (the defaults are the shipped val_pipeline).  The values
+    are checked here so that a bad one is named; the C entries refuse them too (``SCF_EINVAL``)."""
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if not 0 < oh <= 8192 or not 0 < ow <= 8192:
+        raise _lib.ScflowHipError(f'patch_params: out_size {(oh, ow)} outside 1..8192')
+    if not 0 < int(resize) <= min(oh, ow):
+        raise _lib.ScflowHipError(f'patch_params: resize={resize} must be in 1..min(out_size) = {min(oh, ow)}')
+    if int(vertex_stride) < 1:
+        raise _lib.ScflowHipError(f'patch_params: vertex_stride={vertex_stride} must be >= 1')
+    for nm, v, ok in (('size_ratio', size_ratio, float(size_ratio) > 0), ('aspect_ratio', aspect_ratio, float(aspect_ratio) > 0),
+                      ('min_expand', min_expand, float(min_expand) >= 0)):
+        if not (ok and math.isfinite(float(v))):
+            raise _lib.ScflowHipError(f'patch_params: {nm}={v!r} out of range')
+    cp, pv, mn, sd = (_triple(crop_pad_val, 'crop_pad_val'), _triple(pad_val, 'pad_val'), _triple(mean, 'mean'),
+                      _triple(std, 'std'))
+    for nm, v in (('crop_pad_val', cp), ('pad_val', pv)):
+        if not all(x == int(x) and 0 <= x <= 255 for x in v):
+            raise _lib.ScflowHipError(f'patch_params: {nm}={v!r} must be integers in 0..255')
+    if not all(math.isfinite(x) for x in mn) or not all(math.isfinite(x) and x != 0 for x in sd):
+        raise _lib.ScflowHipError(f'patch_params: mean {mn!r} / std {sd!r} must be finite, std non-zero')
+    i3, f3 = C.c_int32 * 3, C.c_float * 3
+    return _lib.PatchParams(float(aspect_ratio), float(size_ratio), float(min_expand), oh, ow, int(resize),
+                            int(vertex_stride), int(bool(keep_ratio)), int(bool(clip_border)),
+                            int(bool(fix_clip_border_quirk)), int(bool(center)), int(bool(to_rgb)),
+                            i3(*map(int, cp)), i3(*map(int, pv)), f3(*mn), f3(*sd))
+
+
+def _int_vec(t: Tensor, shape: Tuple[int, ...], dev, name: str) -> Tensor:
+    """an integer GPU tensor of ``shape`` as contiguous int32 (converted on the device: no host synchronisation)."""
+    if (not isinstance(t, torch.Tensor) or not t.is_cuda or tuple(t.shape) != shape
+            or t.dtype not in (torch.int32, torch.int64) or t.device != dev):
+        raise _lib.ScflowHipError(f'{name} must be an int32 / int64 GPU tensor of shape {shape} on {dev}')
+    return t.to(torch.int32).contiguous()
+
+
+def patch_boxes(mesh, labels: Optional[Tensor], rot: Optional[Tensor], trans: Optional[Tensor], k: Tensor,
+                frame_size: Tuple[int, int], params: '_lib.PatchParams', crop_rects: Optional[Tensor] = None) -> dict:
+    """crop rectangle, resize scale, padding and intrinsics of every object (``scf_patch_boxes``; patch.hip states
+    the semantics).  ``mesh`` is a ``mesh.DeviceMesh``, labels (N,) int GPU tensor (read on the device), rot / k
+    (N,3,3), trans (N,3), frame_size (Hf, Wf).  With ``crop_rects`` (N,4) int GPU tensor of (x1, y1, x2, y2) the
+    caller's rectangles replace the box and the crop rule, and mesh / labels / rot / trans may be None.
+    -> dict(box (N,4) the projected fp32 box, crop (N,4) int32, scale (N), transform_matrix (N,3,3), k (N,3,3), valid (N) int32, records: the
+    workspace ``extract_patches`` reads).  No host synchronisation."""
+    n = k.shape[0] if isinstance(k, torch.Tensor) and k.dim() == 3 else -1
+    if n <= 0:
+        raise _lib.ScflowHipError('patch_boxes: k must be (N,3,3) with N > 0')
+    hf, wf = int(frame_size[0]), int(frame_size[1])
+    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
+        raise _lib.ScflowHipError(f'patch_boxes: frame size {(hf, wf)} outside 1..16384')
+    kp = _mats(k, n, (3, 3), 'k')
+    dev = k.device
+    store, lab, rp, tp, cin = None, None, None, None, None
+    if crop_rects is not None:
+        cin = _int_vec(crop_rects, (n, 4), dev, 'patch_boxes: crop_rects')
+    else:
+        if mesh is None or labels is None or rot is None or trans is None:
+            raise _lib.ScflowHipError('patch_boxes: mesh, labels, rot and trans are needed without crop_rects')
+        lab = _int_vec(labels, (n,), dev, 'patch_boxes: labels')
+        rp, tp = _mats(rot, n, (3, 3), 'rot'), _mats(trans, n, (3,), 'trans')
+        _dense(mesh.verts, 'verts')
+        if mesh.vert_offset.device != dev or mesh.vert_offset.dtype != torch.int32 or not mesh.vert_offset.is_contiguous():
+            raise _lib.ScflowHipError(f'patch_boxes: the mesh store must live on {dev} (MeshStore.on(device))')
+        store = _lib.MeshStore(mesh.verts.data_ptr(), mesh.normals.data_ptr(), mesh.colors.data_ptr(),
+                               mesh.faces.data_ptr(), mesh.vert_offset.data_ptr(), mesh.face_offset.data_ptr(),
+                               int(mesh.num_classes), int(mesh.max_faces))
+    lib = _lib.load()
+    wsb = int(lib.scf_patch_workspace_bytes(n))
+    _lib.check(min(wsb, 0), 'scf_patch_workspace_bytes')
+    rec = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    box = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    crop = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    scale = torch.empty((n,), dtype=torch.float32, device=dev)
+    tm = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    kout = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    valid = torch.empty((n,), dtype=torch.int32, device=dev)
+    _lib.check(lib.scf_patch_boxes(
+        None if store is None else C.byref(store), None if lab is None else lab.data_ptr(), rp, tp, kp,
+        None if cin is None else cin.data_ptr(), n, hf, wf, C.byref(params), box.data_ptr(), crop.data_ptr(), scale.data_ptr(),
+        tm.data_ptr(), kout.data_ptr(), valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes')
+    return dict(box=box, crop=crop, scale=scale, transform_matrix=tm, k=kout, valid=valid, records=rec)
+
+
+def extract_patches(frames: Tensor, frame_index: Tensor, records: Tensor, params: '_lib.PatchParams',
+                    out: Optional[Tensor] = None) -> Tensor:
+    """crop, resize, pad and normalise every object's patch (``scf_patch_extract``).  frames (F,Hf,Wf,3) uint8 GPU
+    tensor (BGR, as cv2 loads them), frame_index (N,) int GPU tensor, ``records`` from ``patch_boxes``.
+    -> (N,3,out_h,out_w) float32.  No host synchronisation."""
+    if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4
+            or frames.shape[3] != 3 or frames.shape[0] < 1):
+        raise _lib.ScflowHipError('extract_patches: frames must be a (F,Hf,Wf,3) uint8 tensor on the GPU '
+                                  '(HIP path only, no CPU fallback)')
+    if frames.device.index != _cur_dev():
+        raise _lib.ScflowHipError(f'extract_patches: frames live on cuda:{frames.device.index} but the current device '
+                                  f'is cuda:{_cur_dev()}: wrap the call in torch.cuda.device(tensor.device)')
+    if not frames.is_contiguous():
+        raise _lib.ScflowHipError('extract_patches: expected contiguous frames')
+    f, hf, wf = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
+        raise _lib.ScflowHipError(f'extract_patches: frame size {(hf, wf)} outside 1..16384')
+    dev = frames.device
+    if not isinstance(frame_index, torch.Tensor) or frame_index.dim() != 1 or frame_index.shape[0] < 1:
+        raise _lib.ScflowHipError('extract_patches: frame_index must be (N,) with N > 0')
+    n = int(frame_index.shape[0])
+    fidx = _int_vec(frame_index, (n,), dev, 'extract_patches: frame_index')
+    lib = _lib.load()
+    if (not isinstance(records, torch.Tensor) or records.device != dev or records.dtype != torch.uint8
+            or not records.is_contiguous() or records.numel() != int(lib.scf_patch_workspace_bytes(n))):
+        raise _lib.ScflowHipError('extract_patches: records must be the workspace patch_boxes returned for the same N')
+    shape = (n, 3, int(params.out_h), int(params.out_w))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.device != dev:
+        raise _lib.ScflowHipError(f'extract_patches: out must be {shape} on {dev}')
+    _lib.check(lib.scf_patch_extract(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), n, records.data_ptr(),
+                                     C.byref(params), _dense(out, 'out'), _stream()), 'scf_patch_extract')
+    return out
+
+
 def unproject_depth(depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor) -> Tensor:
     n, h, w = depth.shape
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=depth.device)
