@@ -255,7 +255,11 @@ __global__ __launch_bounds__(256) void filter_flow_by_mask_kernel(float* __restr
       if (yb && xa) acc += m[y1 * W + x0] * sw;
       if (yb && xb) acc += m[y1 * W + x1] * se;
     }
-    if (acc < 0.9f || both) {
+    // a non-finite sample coordinate (NaN / +-inf flow, or a finite one whose (x + f) * 2 overflows): every bilinear
+    // weight of grid_sample is inf - inf = NaN, so the sampled value is NaN and `NaN < 0.9` does not fire -- the vector is
+    // kept unless both components are >= invalid_num.  (A huge FINITE coordinate samples padding: 0 < 0.9, invalid.)
+    const bool sampled = fabsf(ix) <= 3.402823466e38f && fabsf(iy) <= 3.402823466e38f;
+    if ((sampled && acc < 0.9f) || both) {
       f[0] = invalid_num;
       f[HW] = invalid_num;
     }
