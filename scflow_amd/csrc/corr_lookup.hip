@@ -32,7 +32,7 @@
 //             Zero padding = zero-filled staging + switched-off lanes: only in-map bytes move.
 //   small   : a level whose whole map fits in the footprint is staged whole (one DMA per query
 //             and 64 map elements); out-of-map rows are redirected to a shared zero row at
-//             read-back, out-of-map columns are clamped and lose their weights.
+//             read-back, out-of-map columns are clamped reads whose values are replaced by zero.
 //   emit    : lane = (query, half); per-lane row addresses + immediate column offsets for both
 //             layouts; bilinear weights are per (query, level) constants; each half-wave
 //             writes 32 consecutive queries of one channel = one full 128-B line, write-through.
@@ -216,37 +216,33 @@ __device__ __forceinline__ void lookup_emit(const lds_cfp_t (&rowp)[2 * R + 2], 
   const int cnt = ((part + 1) * D + NP - 1) / NP - i0;
   const unsigned lane_off2 = lane_off + (unsigned)((size_t)i0 * D * cs);
   // small: column validity (xfirst = map column of window column i0)
-  auto column = [&](int it, float (&col)[FW], float& cv) {
+  auto column = [&](int it, float (&col)[FW]) {
     if constexpr (SMALL) {
       const int xx = flat_x ? 0 : xfirst + it;
       const bool cok = (unsigned)xx < (unsigned)lw;
       const int xs = cok ? xx : 0;
-      cv = cok ? 1.f : 0.f;
+      // an out-of-map column contributes a zero VALUE (like the footprint route's padding and grid_sample, which skips
+      // the tap), not a zero weight: 0 * inf would turn an inf / NaN in map column 0 into NaN for every window that
+      // hangs over the map's left or right edge
 #pragma unroll
-      for (int r = 0; r < FW; ++r) col[r] = rowp[r][xs];
+      for (int r = 0; r < FW; ++r) { const float v = rowp[r][xs]; col[r] = cok ? v : 0.f; }
     } else {
-      cv = 1.f;
 #pragma unroll
       for (int r = 0; r < FW; ++r) col[r] = rowp[r][it];      // immediate offsets
     }
   };
   float col[2][FW];
-  float cva, cvb;
-  column(0, col[0], cva);
+  column(0, col[0]);
 #pragma unroll
   for (int it = 0; it < NI; ++it) {
     float (&cA)[FW] = col[it & 1];
     float (&cB)[FW] = col[(it & 1) ^ 1];
-    column(it + 1, cB, cvb);
-    float w0 = nw, w1 = ne, w2 = sw, w3 = se;
-    if constexpr (SMALL) {       // out-of-map columns: clamped reads, zero weights
-      w0 = nw * cva; w2 = sw * cva; w1 = ne * cvb; w3 = se * cvb;
-    }
+    column(it + 1, cB);
     if (qvalid && it < cnt) {
       char* oc = obase + (size_t)(it * D) * cs;      // wave-uniform channel base (SGPRs)
 #pragma unroll
       for (int j = 0; j < D; ++j) {
-        const float v = lk_blend(cA[j], cB[j], cA[j + 1], cB[j + 1], w0, w1, w2, w3);
+        const float v = lk_blend(cA[j], cB[j], cA[j + 1], cB[j + 1], nw, ne, sw, se);
         // a RUNNING scalar base (opaque to the optimiser: it would otherwise precompute all 81
         // channel bases and spill them): one s_add_u32 / s_addc_u32 per store
         asm volatile("" : "+s"(oc));
@@ -254,7 +250,6 @@ __device__ __forceinline__ void lookup_emit(const lds_cfp_t (&rowp)[2 * R + 2], 
         oc += cs;
       }
     }
-    cva = cvb;
   }
 }
 
@@ -795,6 +790,9 @@ int scf_lookup_store_set(int v) {
   return g_lookup_store.exchange(v);
 }
 
+// The route conditions below (generic / one group / pipelined / several groups per block, and which levels are staged whole)
+// are restated in tests/test_corr_host.py (lookup_route, level_kinds): tests/test_gpu_corr.py asserts from that model
+// that each shape reaches the kernel it names.  Change the two together.
 static int lookup_launch(const float* const* levels, const float* flow, float* out, int N, int h, int w,
                          int r, int L, unsigned tiled_levels, scf_stream_t stream) {
   if (!levels || !flow || !out || N <= 0 || h <= 0 || w <= 0 || L <= 0 || r < 1) return SCF_EINVAL;
