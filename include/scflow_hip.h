@@ -654,6 +654,65 @@ int scf_cal_epe(const float* flow_tgt, const float* flow_pred, const float* mask
                 float* mean, float* ratios, float* total_mean, float* total_ratios, void* workspace,
                 scf_stream_t stream);
 
+/* Forward values of the supervised losses (models/loss/sequence_loss.py, point_matching_loss.py) for all T iterations
+ * of a prediction sequence.  No gradients.  Every sequence is a HOST array of T device pointers, T <= 256 (32 travel
+ * per launch; longer sequences take several launches inside the call).  Sums are accumulated in fp64 in a fixed
+ * order and rounded to fp32 once; there are no atomics, so results are bitwise reproducible.
+ *
+ * scf_seq_pixel_loss: SequenceLoss over RAFTLoss for up to two flow sequences (flow_a, flow_b: (N,2,H,W) each, NULL =
+ * none) and over L1Loss for one mask sequence (mask_seq: (N,H,W) each, NULL = none) against gt_flow (N,2,H,W) and the
+ * optional valid (N,H,W), which are read once per pixel:
+ *   mag = sqrt(gx*gx + gy*gy) (three fp32 roundings),  v = (valid >= 0.5) && (mag < max_flow)   [mag < max_flow alone]
+ *   flow value_i = loss_weight * (float)sum(v*|px-gx| + v*|py-gy|) / ((float)count(v) + eps)    (NaN * 0 stays NaN)
+ *   mask value_i = ((float)sum|m - occ| / (float)(N*H*W)) * loss_weight,   occ = mask_gt (N,H,W), or, when mask_gt is
+ *                  NULL, (gx + gy < max_flow).  gt_flow may be NULL when only a mask sequence against mask_gt is given.
+ * The derived occ compares the SUM of the two channels, not the magnitude, and the mask loss ignores valid: both are the
+ * reference's (scflow_refiner.py:230, sequence_loss.py:35-37), restated as they are.
+ * loss_weight, eps, gamma: HOST arrays of 3 (rows flow_a, flow_b, mask_seq; eps[2] is unused).
+ * per_iter (3,T): the values above, 0 in the rows of absent sequences; totals (3): sum_i (float)(gamma^(T-1-i)) *
+ * value_i, added in fp32 in ascending i from 0.
+ * workspace: scf_seq_pixel_loss_workspace_bytes(N, H, W, T) bytes of device memory. */
+int64_t scf_seq_pixel_loss_workspace_bytes(int N, int H, int W, int T);
+int scf_seq_pixel_loss(const float* gt_flow, const float* valid, const float* mask_gt, const float* const* flow_a,
+                       const float* const* flow_b, const float* const* mask_seq, int T, int N, int H, int W,
+                       float max_flow, const float* loss_weight, const float* eps, const double* gamma,
+                       float* per_iter, float* totals, void* workspace, scf_stream_t stream);
+
+/* scf_point_matching_loss: PointMatchingLoss (SCF_PM_FULL), DisentanglePointMatchingLoss (SCF_PM_DISENTANGLE) and
+ * RotPointMatchingLoss (SCF_PM_ROT; pred_t, gt_t, scale_factors unused).
+ * Points: verts (total,3) holds num_groups point sets, set g = rows [offsets[g], offsets[g+1]); sample n uses set
+ * group[n] (its class for class meshes -- the layout of scf_mesh_store -- or n for per-sample point lists).
+ * labels (N) index symmetric (num_classes; != 0: each ground-truth-posed point is compared with its squared-L2 NEAREST
+ * predicted-posed point, lowest index on exact ties, whatever loss_type is) and diameter (num_classes).
+ * A group or label outside its table makes that sample's value NaN and reads nothing.
+ *   t' = (t.xy * s if SCF_PM_SCALE_XY,  t.z * s * scale_depth_factor if SCF_PM_SCALE_DEPTH else t.z * scale_depth_factor)
+ *   FULL         mean_p |(R_pred p + t_pred') - (R_gt p + t_gt')|
+ *   DISENTANGLE  mean_p |(R_pred p + t_gt') - (R_gt p + t_gt')| + the translation term mean_p |(R_gt p + t_pred') -
+ *                (R_gt p + t_gt')|, or with SCF_PM_DISENTANGLE_Z the depth term (t_gt'.xy, t_pred'.z) plus the xy term
+ *                (t_pred'.xy, t_gt'.z), each built per point as written
+ *   ROT          mean_p |R_pred p - R_gt p|
+ * | | is the L1 (loss_type 1) or L2 (2) norm.  loss_i (T,N) = that / diameter[label]; per_iter (T) = loss_weight *
+ * (sum_n loss_i in sample order [/ N for SCF_PM_REDUCE_MEAN]); total (1) = sum_i (float)(gamma^(T-1-i)) * per_iter_i.
+ * nn_idx (T,N,max_points) int32 or NULL: the index compared with each point (its own for non-symmetric classes);
+ * entries past a sample's point count are left untouched.  max_points >= the largest point set in use.
+ * workspace: scf_point_matching_workspace_bytes(N, T, max_points) bytes of device memory. */
+#define SCF_PM_FULL 0
+#define SCF_PM_DISENTANGLE 1
+#define SCF_PM_ROT 2
+#define SCF_PM_DISENTANGLE_Z 1
+#define SCF_PM_SCALE_XY 2
+#define SCF_PM_SCALE_DEPTH 4
+#define SCF_PM_REDUCE_MEAN 0
+#define SCF_PM_REDUCE_SUM 1
+int64_t scf_point_matching_workspace_bytes(int N, int T, int max_points);
+int scf_point_matching_loss(const float* verts, const int32_t* offsets, int num_groups, const int32_t* group,
+                            const int32_t* labels, int num_classes, const int32_t* symmetric, const float* diameter,
+                            const float* const* pred_r, const float* const* pred_t, int T, const float* gt_r,
+                            const float* gt_t, const float* scale_factors, int N, int max_points, int mode,
+                            int loss_type, int flags, float scale_depth_factor, int reduction, float loss_weight,
+                            double gamma, float* loss_i, float* per_iter, float* total, int32_t* nn_idx,
+                            void* workspace, scf_stream_t stream);
+
 /* object-frame points of every pixel (dense cal_3d_2d_corr): pts (N,3,H,W), 0 where
  * depth <= 0.  Test/diagnostic entry; scf_reproject_flow recomputes them on the fly. */
 int scf_unproject_depth(const float* depth, const float* K, const float* R0, const float* t0,

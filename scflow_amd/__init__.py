@@ -18,7 +18,9 @@ from .refiner import RAFTRefinerFlow, RAFTRefinerFlowMask, SCFlowRefiner  # noqa
 from .metrics import (cal_epe, eval_pose_error, eval_rot_error,  # noqa: F401
                       eval_tran_error, filter_flow_by_mask,
                       get_flow_from_delta_pose_and_depth)
-from .config import raft_model_cfg, scflow_model_cfg  # noqa: F401
+from .losses import (LOSSES, DisentanglePointMatchingLoss, L1Loss, PointMatchingLoss, RAFTLoss,  # noqa: F401
+                     RotPointMatchingLoss, SequenceLoss, build_loss)
+from .config import raft_loss_cfgs, raft_model_cfg, scflow_loss_cfgs, scflow_model_cfg  # noqa: F401
 from .weights import fill_state_dict  # noqa: F401
 from .synthetic import make_inputs  # noqa: F401
 from .mesh import Fragments, Mesh, MeshRenderer, MeshStore, make_mesh, read_ply  # noqa: F401

@@ -9,7 +9,7 @@ from __future__ import annotations
 
 import copy
 
-__all__ = ['scflow_model_cfg', 'raft_model_cfg']
+__all__ = ['scflow_model_cfg', 'raft_model_cfg', 'scflow_loss_cfgs', 'raft_loss_cfgs']
 
 _MODEL = dict(
     type='SCFlowRefiner',
@@ -81,3 +81,41 @@ def raft_model_cfg(iters: int = 12) -> dict:
     cfg['decoder']['iters'] = iters
     cfg['test_cfg'] = dict(iters=iters)
     return cfg
+
+
+# configs/refine_models/scflow.py:5-14: YCB-V symmetry types (1-based class keys; the losses test key MEMBERSHIP) and
+# mesh diameters in mm
+YCBV_SYMMETRY_TYPES = {
+    'cls_13': {'z': 0},
+    'cls_16': {'x': 180, 'y': 180, 'z': 90},
+    'cls_19': {'y': 180},
+    'cls_20': {'x': 180},
+    'cls_21': {'x': 180, 'y': 90, 'z': 180},
+}
+YCBV_MESH_DIAMETER = [172.16, 269.58, 198.38, 120.66, 199.79, 90.17, 142.58, 114.39, 129.73,
+                      198.40, 263.60, 260.76, 162.27, 126.86, 230.44, 237.30, 204.11, 121.46,
+                      183.08, 231.39, 102.92]
+
+
+def scflow_loss_cfgs(mesh_path=None) -> dict:
+    """configs/refine_models/scflow.py:75-104 as data: ``dict(flow_loss_cfg=, pose_loss_cfg=, mask_loss_cfg=)`` to
+    update a model dict with.  ``mesh_path`` defaults to the reference's 'data/ycbv/models_eval'; it is read at the
+    first ``loss()`` call, not when the model is built."""
+    return dict(
+        flow_loss_cfg=dict(type='SequenceLoss', gamma=0.8,
+                           loss_func_cfg=dict(type='RAFTLoss', loss_weight=.1, max_flow=400.)),
+        pose_loss_cfg=dict(type='SequenceLoss', gamma=0.8,
+                           loss_func_cfg=dict(type='DisentanglePointMatchingLoss',
+                                              symmetry_types=copy.deepcopy(YCBV_SYMMETRY_TYPES),
+                                              mesh_diameter=list(YCBV_MESH_DIAMETER),
+                                              mesh_path='data/ycbv/models_eval' if mesh_path is None else mesh_path,
+                                              loss_type='l1', disentangle_z=True, loss_weight=10.0)),
+        mask_loss_cfg=dict(type='SequenceLoss', gamma=0.8, loss_func_cfg=dict(type='L1Loss', loss_weight=10.)))
+
+
+def raft_loss_cfgs() -> dict:
+    """configs/refine_models/raft.py:49-65 as data: ``dict(flow_loss_cfg=, occlusion_loss_cfg=)``."""
+    return dict(
+        flow_loss_cfg=dict(type='SequenceLoss', gamma=0.8,
+                           loss_func_cfg=dict(type='RAFTLoss', loss_weight=1.0, max_flow=400.)),
+        occlusion_loss_cfg=dict(type='SequenceLoss', gamma=0.8, loss_func_cfg=dict(type='L1Loss', loss_weight=100.)))

@@ -4,15 +4,18 @@ Mirrors models/refiner/scflow_refiner.py:18-179 (+ base_refiner.py:17-64):
 same registry name, constructor keys (``configs/refine_models/scflow.py:16-113``
 applies unchanged), attribute names, ``extract_feat`` / ``get_pose`` /
 ``forward_single_pass`` signatures and return structure, same ``state_dict``
-keys.  Losses and PnP re-mapping are outside the hot path:
-their config keys are accepted and ignored, and ``forward_single_pass`` consumes an
-already formatted ``data`` dict (what ``BaseRefiner.format_data_test`` produces,
-base_refiner.py:79-133).  The config's ``renderer`` dict is ignored too;
+keys.  PnP re-mapping is outside the hot path, and
+``forward_single_pass`` consumes an already formatted ``data`` dict (what
+``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).  The loss
+configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
+``loss()`` returns the forward VALUES the reference trains against -- no autograd, no
+``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
 from __future__ import annotations
 
+from collections import OrderedDict
 from typing import Dict, Optional, Tuple, Union
 
 import torch
@@ -96,6 +99,123 @@ class _RenderingRefiner:
         data['rendered_masks'] = mask
         return data
 
+    # ------------------------------------------------------------------ supervised loss values (no autograd)
+    render_augmentations = None
+    _loss_cfgs: Dict[str, Optional[dict]] = {}
+
+    def _build_loss_funcs(self) -> None:
+        """build ``<name>_loss_func`` from the stored config dicts, once, at the first ``loss()`` call -- the constructor
+        accepts opaque dicts and mesh paths that do not exist where the model is built."""
+        if self.__dict__.get('_loss_built'):
+            return
+        from .losses import build_loss
+        built = {}
+        for attr, (key, cfg) in self._loss_cfgs.items():
+            if not isinstance(cfg, dict) or 'type' not in cfg:
+                raise ValueError(f"loss(): {key} is {cfg!r}; it must be a loss config such as dict(type='SequenceLoss', "
+                                 "gamma=0.8, loss_func_cfg=dict(type='RAFTLoss', ...))")
+            if cfg['type'] == 'SequenceLoss' and 'loss_func_cfg' not in cfg:
+                raise ValueError(f"loss(): {key} = {cfg!r} has no 'loss_func_cfg': the model was built from an opaque "
+                                 'loss config (scflow_amd.config keeps them opaque); give the full dict, e.g. '
+                                 'scflow_amd.config.scflow_loss_cfgs()')
+            built[attr] = build_loss(cfg)
+        for attr, func in built.items():
+            self.__dict__[attr] = func
+        self.__dict__['_loss_built'] = True
+
+    def format_data_train_sup(self, data_batch: Dict) -> Dict:
+        """base_refiner.py:136-191 on the attached ``MeshRenderer``: concatenate the per-image lists, render every sample
+        at its reference pose, normalise the rendered RGB.  The ``init_*_error`` statistics (``torch.std_mean``,
+        biased) are computed when the annotations carry them.  ``render_augmentations`` (kornia) are not implemented."""
+        if self.render_augmentations is not None:
+            raise NotImplementedError('render_augmentations (kornia augmentation of the rendered images, '
+                                      'base_refiner.py:43-64, 159-160) are not implemented')
+        self._need_renderer('format_data_train_sup')
+        real_images, annots, meta_infos = data_batch['img'], data_batch['annots'], data_batch['img_metas']
+        real_images = torch.cat(real_images)
+        ref_rotations = torch.cat(annots['ref_rotations'], dim=0)
+        ref_translations = torch.cat(annots['ref_translations'], dim=0)
+        gt_rotations = torch.cat(annots['gt_rotations'], dim=0)
+        gt_translations = torch.cat(annots['gt_translations'], dim=0)
+        labels, internel_k = torch.cat(annots['labels']), torch.cat(annots['k'])
+        norm = meta_infos[0]['img_norm_cfg']
+        mean = (torch.tensor(norm['mean'], dtype=torch.float32) / 255.).tolist()
+        std = (torch.tensor(norm['std'], dtype=torch.float32) / 255.).tolist()
+        rgb, depth, mask = self.renderer.render_normalized(ref_rotations, ref_translations, internel_k, labels, mean, std)
+        output = dict(ref_rotations=ref_rotations, ref_translations=ref_translations, gt_rotations=gt_rotations,
+                      gt_translations=gt_translations, labels=labels, internel_k=internel_k, rendered_images=rgb,
+                      real_images=real_images, rendered_masks=mask, rendered_depths=depth)
+        for name in ('add', 'rot', 'trans'):
+            if f'init_{name}_error' in annots:
+                err = annots[f'init_{name}_error']
+                err = torch.cat([e.reshape(-1) for e in err]) if isinstance(err, (list, tuple)) else err
+                sd, mn = torch.std_mean(err, unbiased=False)
+                output[f'init_{name}_error_mean'], output[f'init_{name}_error_std'] = mn, sd
+        if 'gt_masks' in annots:
+            output['gt_masks'] = torch.cat([_as_mask_tensor(m, real_images.device) for m in annots['gt_masks']], dim=0)
+        return output
+
+    @staticmethod
+    def _scale_factors(data: Dict, data_batch: Optional[Dict], device) -> Optional[Tensor]:
+        """scflow_refiner.py:213-216: the per-sample image scale (first column of every ``img_meta['scale_factor']``), or
+        ``data['scale_factors']`` when the caller formatted the data itself."""
+        if 'scale_factors' in data:
+            return data['scale_factors']
+        metas = (data_batch or {}).get('img_metas') if isinstance(data_batch, dict) else None
+        if not metas or any('scale_factor' not in m for m in metas):
+            return None
+        first_column = []
+        for meta in metas:                      # one row of (w, h, w, h) scales per sample of the image
+            first_column += [float(row[0]) for row in torch.as_tensor(meta['scale_factor']).reshape(-1, 4)]
+        return torch.tensor(first_column, dtype=torch.float32, device=device)
+
+    def _supervision(self, data: Dict, by_mask: bool):
+        """the ground-truth flow the losses are taken against: re-projection of the rendered depth from the reference to
+        the ground-truth pose, ``max_flow`` where there is none, optionally filtered by the ground-truth mask."""
+        from .metrics import filter_flow_by_mask, get_flow_from_delta_pose_and_depth
+        gt_flow = get_flow_from_delta_pose_and_depth(data['ref_rotations'], data['ref_translations'],
+                                                     data['gt_rotations'], data['gt_translations'],
+                                                     data['rendered_depths'], data['internel_k'],
+                                                     invalid_num=self.max_flow)
+        if by_mask:
+            gt_flow = filter_flow_by_mask(gt_flow, data['gt_masks'], invalid_num=self.max_flow)
+        return gt_flow
+
+    def _pixel_losses(self, gt_flow, valid, flow_funcs, flow_seqs, mask_func, mask_seq):
+        """SequenceLoss values of up to two flow sequences and the mask sequence.  One fused launch when every loss is a
+        ``SequenceLoss`` over ``RAFTLoss`` / ``L1Loss`` with the refiner's ``max_flow``; else one call per loss with the
+        occlusion target built as the reference builds it (the SUM of the two channels < max_flow,
+        scflow_refiner.py:230 -- not the magnitude)."""
+        from . import losses as L
+        fusable = all(type(f) is L.SequenceLoss and type(f.loss_func) is L.RAFTLoss
+                      and float(f.loss_func.max_flow) == float(self.max_flow) for f in flow_funcs)
+        fusable = fusable and (mask_func is None or (type(mask_func) is L.SequenceLoss and type(mask_func.loss_func) is L.L1Loss))
+        if fusable:
+            fl = list(flow_funcs) + [None] * (2 - len(flow_funcs))
+            sq = list(flow_seqs) + [None] * (2 - len(flow_seqs))
+            get = lambda f, name, default: default if f is None else getattr(f.loss_func, name)
+            per_iter, totals = L.seq_pixel_loss(
+                gt_flow, valid, flow_a=sq[0], flow_b=sq[1], masks=mask_seq, max_flow=self.max_flow,
+                loss_weight=(get(fl[0], 'loss_weight', 1.), get(fl[1], 'loss_weight', 1.), get(mask_func, 'loss_weight', 1.)),
+                eps=(get(fl[0], 'eps', 0.), get(fl[1], 'eps', 0.), 0.),
+                gamma=tuple(1. if f is None else f.gamma for f in (fl[0], fl[1], mask_func)))
+            out = [(totals[i], list(per_iter[i].unbind(0))) for i in range(len(flow_funcs))]
+            return out, (None if mask_func is None else (totals[2], list(per_iter[2].unbind(0))))
+        out = [f(seq, gt_flow=gt_flow, valid=valid) for f, seq in zip(flow_funcs, flow_seqs)]
+        mask_out = None
+        if mask_func is not None:
+            occluded_target = (gt_flow[:, 0] + gt_flow[:, 1] < self.max_flow).float()       # channel SUM, not magnitude
+            mask_out = mask_func([m[:, 0] if m.dim() == 4 else m for m in mask_seq], gt_mask=occluded_target, valid=valid)
+        return out, mask_out
+
+    @staticmethod
+    def _log_vars(named) -> 'OrderedDict':
+        """[(key, 0-dim GPU tensor)] -> OrderedDict of Python floats through ONE device-to-host transfer of one packed
+        vector (the reference issues one ``.item()`` per entry)."""
+        from .losses import to_host
+        host = to_host(torch.stack([v.reshape(()).to(torch.float32) for _, v in named]))
+        return OrderedDict((k, float(x)) for (k, _), x in zip(named, host))
+
 
 @REFINERS.register_module()
 class SCFlowRefiner(_RenderingRefiner, HipModule):
@@ -128,6 +248,10 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         assert self.cxt_channels == self.decoder.cxt_channels
         assert self.h_channels + self.cxt_channels == self.context.out_channels
         self.filter_invalid_flow = filter_invalid_flow
+        self.render_augmentations = render_augmentations
+        # built at the first loss() call (_build_loss_funcs): attribute -> (constructor key, config as given)
+        self._loss_cfgs = dict(pose_loss_func=('pose_loss_cfg', pose_loss_cfg), flow_loss_func=('flow_loss_cfg', flow_loss_cfg),
+                               mask_loss_func=('mask_loss_cfg', mask_loss_cfg))
         self.test_by_flow = self.test_cfg.get('by_flow', False)
         self.test_iter_num = self.test_cfg.get('iters', self.decoder.iters)
         self.eval()
@@ -225,6 +349,45 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                     labels=torch.split(labels, per_img),
                     scores=torch.split(torch.ones_like(labels, dtype=torch.float32), per_img))
 
+    # ------------------------------------------------------------------ loss values
+    def loss(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """scflow_refiner.py:184-258 -> (loss, None, log_vars, seq_rotations, seq_translations): the forward VALUES of the
+        pose, flow and mask sequence losses of ``decoder.iters`` iterations and their sum.  **No autograd**: ``loss`` is a
+        0-dim GPU tensor with no graph behind it.  ``log_imgs`` is None (visualisation is out of scope).  ``log_vars``
+        has the reference's keys in the reference's order (the ``init_add_*`` pair only when the data carries it) and
+        reaches the host in one transfer.  ``data``: an already formatted dict (``format_data_train_sup``'s), the only
+        way to call this without an attached renderer; it needs ``gt_masks`` when ``filter_invalid_flow`` is set."""
+        from . import losses as L
+        self._build_loss_funcs()
+        if data is None:
+            data = self.format_data_train_sup(data_batch)
+        labels, valid = data['labels'], data['rendered_masks']
+        outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
+                             data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
+        flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
+        gt_flow = self._supervision(data, self.filter_invalid_flow)
+        pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
+        if pose_is_flow:
+            (flow_out, pose_out), mask_out = self._pixel_losses(
+                gt_flow, valid, [self.flow_loss_func, self.pose_loss_func], [flow_from_pred, flow_from_pose],
+                self.mask_loss_func, sequence_masks)
+        else:
+            pose_out = self.pose_loss_func(seq_rotations, seq_translations, gt_r=data['gt_rotations'],
+                                           gt_t=data['gt_translations'], labels=labels,
+                                           scale_factors=self._scale_factors(data, data_batch, gt_flow.device))
+            (flow_out,), mask_out = self._pixel_losses(gt_flow, valid, [self.flow_loss_func], [flow_from_pred],
+                                                       self.mask_loss_func, sequence_masks)
+        (loss_pose, seq_pose), (loss_flow, seq_flow), (loss_mask, seq_mask) = pose_out, flow_out, mask_out
+        loss = loss_pose + loss_flow + loss_mask
+        named = []
+        if 'init_add_error_mean' in data:
+            named += [('init_add_mean', data['init_add_error_mean']), ('init_add_std', data['init_add_error_std'])]
+        for i in range(len(seq_flow)):
+            named += [(f'seq_{i}_pose_loss', seq_pose[i]), (f'seq_{i}_flow_loss', seq_flow[i]),
+                      (f'seq_{i}_mask_loss', seq_mask[i])]
+        named += [('loss_mask', loss_mask), ('loss_flow', loss_flow), ('loss_pose', loss_pose), ('loss', loss)]
+        return loss, None, self._log_vars(named), seq_rotations, seq_translations
+
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:
             raise NotImplementedError('training is outside the hot path (SURVEY.md section 2)')
@@ -264,7 +427,10 @@ class _FlowRefinerBase(_RenderingRefiner, HipModule):
 
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int,
                  cxt_encoder: dict, encoder: dict, decoder: dict, test_cfg: Optional[dict] = None,
-                 **ignored) -> None:
+                 max_flow: float = 400., render_augmentations: Optional[list] = None,
+                 filter_invalid_flow_by_mask: bool = True, filter_invalid_flow_by_depth: bool = False,
+                 filter_invalid_flow: Optional[bool] = None, flow_loss_cfg: Optional[dict] = None,
+                 occlusion_loss_cfg: Optional[dict] = None, loss_cfg: Optional[dict] = None, **ignored) -> None:
         super().__init__()
         self.seperate_encoder = seperate_encoder
         if seperate_encoder:
@@ -279,9 +445,21 @@ class _FlowRefinerBase(_RenderingRefiner, HipModule):
         self.h_channels, self.cxt_channels = h_channels, cxt_channels
         self.test_cfg = test_cfg or {}
         self.test_iter_num = self.test_cfg.get('iters', self.decoder.iters)
+        self.max_flow = max_flow
+        self.render_augmentations = render_augmentations
+        self.filter_invalid_flow_by_mask = filter_invalid_flow_by_mask
+        self.filter_invalid_flow_by_depth = filter_invalid_flow_by_depth
+        # raft_refiner_flow.py:192 reads `filter_invalid_flow`; it follows filter_invalid_flow_by_mask unless given
+        self.filter_invalid_flow = filter_invalid_flow_by_mask if filter_invalid_flow is None else filter_invalid_flow
+        self._loss_cfgs = self._loss_config(flow_loss_cfg, occlusion_loss_cfg, loss_cfg)
         self.eval()
 
     extract_feat = SCFlowRefiner.extract_feat
+
+    def _no_depth_filter(self):
+        if self.filter_invalid_flow_by_depth:
+            raise NotImplementedError('filter_invalid_flow_by_depth (filter_flow_by_depth on a rendering at the '
+                                      'ground-truth pose, raft_refiner_flow_mask.py:189-191) is not implemented')
 
     def get_flow(self, render_images: Tensor, real_images: Tensor,
                  init_flow: Optional[Tensor] = None):
@@ -388,7 +566,51 @@ class RAFTRefinerFlowMask(_FlowRefinerBase):
     occlusion map (confidence and occ_thresh mask)."""
     _has_occlusion = True
 
+    @staticmethod
+    def _loss_config(flow_loss_cfg, occlusion_loss_cfg, loss_cfg):
+        return dict(flow_loss_func=('flow_loss_cfg', flow_loss_cfg),
+                    occlusion_loss_func=('occlusion_loss_cfg', occlusion_loss_cfg))
+
+    def loss(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """raft_refiner_flow_mask.py:169-222 -> (loss, None, log_vars): the forward VALUES of the flow and the occlusion
+        sequence losses (keys ``seq_<i>_flow_loss``, ``seq_<i>_occ_loss``, ``loss_occ``, ``loss_flow``, ``loss``).  **No
+        autograd.**  ``data``: an already formatted dict, as for ``SCFlowRefiner.loss``."""
+        self._no_depth_filter()
+        self._build_loss_funcs()
+        if data is None:
+            data = self.format_data_train_sup(data_batch)
+        sequence_flow, sequence_occlusion = self.get_flow(data['rendered_images'], data['real_images'])
+        gt_flow = self._supervision(data, self.filter_invalid_flow_by_mask)
+        ((loss_flow, seq_flow),), (loss_occ, seq_occ) = self._pixel_losses(
+            gt_flow, data['rendered_masks'], [self.flow_loss_func], [sequence_flow], self.occlusion_loss_func,
+            sequence_occlusion)
+        loss = loss_flow + loss_occ
+        named = []
+        for i in range(len(seq_flow)):
+            named += [(f'seq_{i}_flow_loss', seq_flow[i]), (f'seq_{i}_occ_loss', seq_occ[i])]
+        named += [('loss_occ', loss_occ), ('loss_flow', loss_flow), ('loss', loss)]
+        return loss, None, self._log_vars(named)
+
 
 @REFINERS.register_module()
 class RAFTRefinerFlow(_FlowRefinerBase):
     """RAFTDecoder -> flows."""
+
+    @staticmethod
+    def _loss_config(flow_loss_cfg, occlusion_loss_cfg, loss_cfg):
+        # raft_refiner_flow.py:40 names its one loss `loss_cfg`; `flow_loss_cfg` is taken in its place
+        return dict(loss_func=('loss_cfg', loss_cfg if loss_cfg is not None else flow_loss_cfg))
+
+    def loss(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """raft_refiner_flow.py:177-212 -> (loss, None, log_vars): the forward VALUES of the flow sequence loss (keys
+        ``seq_<i>_loss``, ``loss``).  **No autograd.**  ``data``: an already formatted dict."""
+        self._no_depth_filter()
+        self._build_loss_funcs()
+        if data is None:
+            data = self.format_data_train_sup(data_batch)
+        sequence_flow = self.get_flow(data['rendered_images'], data['real_images'])
+        gt_flow = self._supervision(data, self.filter_invalid_flow)
+        ((loss, seq_loss),), _ = self._pixel_losses(gt_flow, data['rendered_masks'], [self.loss_func], [sequence_flow],
+                                                    None, None)
+        named = [(f'seq_{i}_loss', v) for i, v in enumerate(seq_loss)] + [('loss', loss)]
+        return loss, None, self._log_vars(named)
