@@ -377,6 +377,13 @@ int scf_scflow_iteration(const scf_scflow_iter* iter, scf_stream_t stream);
  * --------------------------------------------------------------------------------- */
 int scf_instance_norm(const float* x, const float* res, float* out, int64_t planes,
                       int HW, float eps, int relu, scf_stream_t stream);
+/* The tail of a residual block whose shortcut is normalised too (resnet.py:88-94 with a downsample branch):
+ * out = relu?( IN(x) + IN(r) ), bit for bit scf_instance_norm(r -> r) followed by scf_instance_norm(x, res = r -> out),
+ * in ONE pass over x and r for 16-byte-aligned planes of up to 16384 floats with HW % 4 == 0.  Other planes run those two
+ * launches, which normalise r in place: the contents of r after the call are unspecified.  out may alias x or r.
+ * Added without a version bump (SCF_VERSION stays at .3), as the renderer's entries were: its presence marks the feature. */
+int scf_instance_norm_res_norm(const float* x, float* r, float* out, int64_t planes,
+                               int HW, float eps, int relu, scf_stream_t stream);
 
 /* GroupNorm(G, eps, affine) + ReLU on (N, C, HW).     replaces pose_head.py:151-159 */
 int scf_group_norm_relu(const float* x, const float* gamma, const float* beta, float* out,

@@ -219,6 +219,7 @@ SIGNATURES = {
                                       C.c_int64, _fp, _fp, _fp]),
     'scf_scflow_iteration': (C.c_int, [C.POINTER(ScflowIter), _fp]),
     'scf_instance_norm': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int, _fp]),
+    'scf_instance_norm_res_norm': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, C.c_int, _fp]),
     'scf_group_norm_relu': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, _fp]),
     'scf_conv_workspace': (C.c_int, [_fp, _fp, C.c_int64]),

@@ -126,12 +126,20 @@ __device__ __forceinline__ void wait_vmcnt_le(int n) { scf_wait_vmcnt_le(n); }
 //         double buffer, so a block's serial chain of "one memory round trip per chunk" is 1 / NG as long -- the
 //         split of K across more waves of the SAME block (the partial sums already meet in LDS at the end), for
 //         grids with at most one block per CU (batch 1: a launch was 8 ... 16 such round trips whatever it computed).
+// SH    : (pixel-split tiles, 3x3 / stride 2 / pad 1, 8-channel chunks) the block also computes the 1x1 / stride-2 / pad-0
+//         SHORTCUT `q` of a down-sampling residual block from the same staged patch: input pixel (2y, 2x) of the shortcut IS the
+//         centre tap of the 3x3 window.  Per chunk the shortcut's two weight rows (lane halves h = 0, 1) x BM channels ride behind
+//         the patch in the same buffer, the centre-tap step issues a second set of MFMAs into a second accumulator set, and the
+//         block ends with a second epilogue from q's own fields.  The shortcut's k order is the one of its stand-alone launch
+//         (channel pairs in ascending order, one accumulator per fragment): its output has the same bits, and p's own sequence
+//         of MFMAs per accumulator is untouched.
 // The kernel's body as a function of (its arguments, its block index, its grid size): conv_dma_kernel runs it with the launch's
 // own blockIdx / gridDim, conv_dma_pair_kernel (r6, below) runs TWO independent layers' grids in one launch.
-template <int WM, int WN, int NST = 2, bool KSP = false, bool PX4 = false, int NG = 1>
-__device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int nblk) {
+template <int WM, int WN, int NST = 2, bool KSP = false, bool PX4 = false, int NG = 1, bool SH = false>
+__device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int nblk, const ConvK& q) {
   extern __shared__ __attribute__((aligned(16))) float lds_all[];
   static_assert(!KSP || (WM == 1 && WN == 1), "K-split tile is one 32x32 fragment");
+  static_assert(!SH || (!KSP && NST == 2 && NG == 1), "shared-input form: pixel-split tiles, double buffer");
   static_assert(NG == 1 || (KSP && NST == 2), "wave groups: K-split tile, double buffer");
   constexpr int BM = WM * 32;
   constexpr int NFRAG = KSP ? 1 : WN * 4;
@@ -180,7 +188,8 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
   const int NIT = T * G;               // (tap, group) steps per chunk, 4 k-steps each
   const int WF4 = NIT * 2 * BM;        // weight float4 per chunk
   const int PE = KC * PHW;             // patch floats per chunk
-  const int bufsz = WF4 * 4 + PE;      // floats per buffer (multiple of 4)
+  const int WS4 = SH ? 2 * BM : 0;     // shared-input form: the shortcut's weight float4 per chunk, behind the patch
+  const int bufsz = WF4 * 4 + PE + WS4 * 4;      // floats per buffer (multiple of 4)
   float* const lds = lds_all + grp * (NST * bufsz);      // this wave group's ring
 
   // weights: float4 e = tid + 256u of the chunk's [NIT*2 rows][BM] slab out of [rows][Mld4]
@@ -208,8 +217,24 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
     for (int u = 0; u < WU; ++u)
       bdma_slot<true>(wrs, woff[u], wl0 + u * 4096, wrem - u * 256);
   };
+  // shared-input form: the shortcut's [2 rows][BM] slab of the chunk's 8 channels out of q's [8-channel group][h][Mld4] packing
+  // (a 1x1 packing is linear in the 8-channel groups whatever its own chunk size), one cell per thread
+  unsigned soff = SCF_DMA_OOB;
+  if constexpr (SH) {
+    const int row = tid / BM, m = tid - row * BM;
+    if (tid < WS4 && m0 + m < q.Mld4) soff = (unsigned)((row * q.Mld4 + m) * 16);
+  }
+  auto stage_s = [&](int chunk, int b) {
+    if constexpr (SH) {
+      const scf_rsrc_t srs = make_rsrc(q.wp4 + (long long)chunk * 2 * q.Mld4 * 4 + (long long)m0 * 4,
+                                       (unsigned)((q.Mld4 + min(BM, q.Mld4 - m0)) * 16));
+      int srem = WS4 - wave * 64;
+      asm volatile("" : "+s"(srem));
+      bdma_slot<true>(srs, soff, lds_addr(lds + b * bufsz + WF4 * 4 + PE) + wave * 1024, srem);
+    }
+  };
   CTRACE(1);
-  if (grp < nch) stage_w(cb + grp, 0);
+  if (grp < nch) { stage_w(cb + grp, 0); stage_s(cb + grp, 0); }
   __builtin_amdgcn_sched_barrier(0);
 
   // ---- gather table: LDS patch float e = tid + 256u <-> (group g, half h, py, px, s) ----
@@ -262,6 +287,15 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
   f32x16 acc2;                         // K-split tile: second accumulator (odd steps of this wave)
 #pragma unroll
   for (int r = 0; r < 16; ++r) acc2[r] = 0.f;
+  f32x16 accs[SH ? WM : 1][SH ? WN : 1];      // shared-input form: the shortcut's accumulators
+  if constexpr (SH) {
+#pragma unroll
+    for (int i = 0; i < WM; ++i)
+#pragma unroll
+      for (int j = 0; j < WN; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) accs[i][j][r] = 0.f;
+  }
 
   // GRU launches: the pre-activation term (`res`: the hoisted context part) goes into the
   // accumulators NOW, while the first chunks are still on their way, instead of being read in
@@ -317,6 +351,7 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
   };
   auto stage = [&](int chunk, int b) {   // weights first (chunk 0: already out), then the patch
     stage_w(chunk, b);
+    stage_s(chunk, b);
     stage_p(chunk, b);
   };
 
@@ -442,6 +477,31 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
     // Steady state without conditions around the loads: with a conditional load the compiler's
     // wait-count insertion falls back to lgkmcnt(0) at the join, i.e. it waits for the operands it
     // has just requested for the NEXT step before starting this step's MFMAs.
+    if constexpr (SH) {
+      // nine steps (3x3 taps, one 8-channel group), written out: step 4 is the centre tap, whose B operands are the
+      // shortcut's input pixels -- its MFMAs follow that step's own, on the operands already in registers
+      f32x4 as[WM];
+      const f32x4* ws = reinterpret_cast<const f32x4*>(pl) + (PE >> 2) + half * BM + l32;
+#pragma unroll
+      for (int i = 0; i < WM; ++i) as[i] = ws[i * 32];
+      load(a[0], b[0], 0);
+#pragma unroll
+      for (int it = 0; it < 9; ++it) {
+        if (it + 1 < 9) load(a[(it + 1) & 1], b[(it + 1) & 1], it + 1);
+        mma(a[it & 1], b[it & 1]);
+        if (it == 4) {
+#pragma unroll
+          for (int s = 0; s < 4; ++s)
+#pragma unroll
+            for (int i = 0; i < WM; ++i)
+#pragma unroll
+              for (int j = 0; j < WN; ++j)
+                accs[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(as[i][s], b[0][j][s], accs[i][j], 0, 0, 0);
+        }
+      }
+      CTRACE(7 + chunk * 4);
+      continue;
+    }
     load(a[0], b[0], 0);
     int it = 0;
     for (; it + 2 < NITc; it += 2) {
@@ -505,12 +565,22 @@ __device__ __forceinline__ void conv_dma_body(ConvK p, const int bid, const int 
     pix[j] = pok ? lin : -1;
   }
   if (!CLAB(2)) scf_conv_epilogue_tile<WM, WN>(p, epi, acc, m0, half, pix, use_div);
+  if constexpr (SH) {                  // the shortcut: same pixels and channel fragments, its own bias / fold / act / out
+    const ConvEpi epis = scf_conv_epi(q, n);
+    scf_conv_epilogue_tile<WM, WN>(q, epis, accs, m0, half, pix, q.out_div != 1.0f);
+  }
   CTRACE(3);
 }
 
 template <int WM, int WN, int NST = 2, bool KSP = false, bool PX4 = false, int NG = 1>
 __global__ __launch_bounds__(256 * NG, (KSP || NST > 2) ? 1 : 2) void conv_dma_kernel(ConvK p) {
-  conv_dma_body<WM, WN, NST, KSP, PX4, NG>(p, (int)blockIdx.x, (int)gridDim.x);
+  conv_dma_body<WM, WN, NST, KSP, PX4, NG>(p, (int)blockIdx.x, (int)gridDim.x, p);
+}
+
+// a 3x3 / stride-2 layer p and the 1x1 / stride-2 shortcut q that reads the same input, in p's grid (SH above)
+template <int WM, int WN, bool PX4>
+__global__ __launch_bounds__(256, 2) void conv_dma_shared_kernel(ConvK p, ConvK q) {
+  conv_dma_body<WM, WN, 2, false, PX4, 1, true>(p, (int)blockIdx.x, (int)gridDim.x, q);
 }
 
 // r6: TWO independent small-grid layers in ONE launch (blocks [0, nba) run layer a, the rest layer b; K-split tile only).
@@ -520,8 +590,8 @@ __global__ __launch_bounds__(256 * NG, (KSP || NST > 2) ? 1 : 2) void conv_dma_k
 // the same arithmetic per layer (a block cannot tell which launch form it runs in: bit-identical outputs).
 template <bool PX4, int NG>
 __global__ __launch_bounds__(256 * NG, 1) void conv_dma_pair_kernel(ConvK pa, ConvK pb, int nba) {
-  if ((int)blockIdx.x < nba) conv_dma_body<1, 1, 2, true, PX4, NG>(pa, (int)blockIdx.x, nba);
-  else conv_dma_body<1, 1, 2, true, PX4, NG>(pb, (int)blockIdx.x - nba, (int)gridDim.x - nba);
+  if ((int)blockIdx.x < nba) conv_dma_body<1, 1, 2, true, PX4, NG>(pa, (int)blockIdx.x, nba, pa);
+  else conv_dma_body<1, 1, 2, true, PX4, NG>(pb, (int)blockIdx.x - nba, (int)gridDim.x - nba, pb);
 }
 
 #define SCF_DMA_LDS_DEEP (144 * 1024)  // tiny grids (one block per CU): 32-channel chunks of 3x3 layers
@@ -745,6 +815,7 @@ int scf_conv_dma_dispatch(ConvK k, int N, bool dry_run, int* info, hipStream_t s
   if (cap) {                // r6: hand the launch back instead of issuing it (scf_conv2d_pair)
     cap->k = k; cap->nblk = (int)nblk; cap->ldsb = ldsb;
     cap->variant = ksp ? (ngroups == 2 ? 2 : 0) + (px4 ? 1 : 0) : -1;      // K-split tile: {NG 1 | 2} x {dword | x4 patch staging}
+    cap->WM = ksp ? 0 : WM; cap->WN = ksp ? 0 : WN; cap->px4 = px4 ? 1 : 0;   // pixel-split tile (scf_conv_dma_shared_launch)
     return SCF_OK;
   }
   if (dry_run) return SCF_OK;
@@ -762,13 +833,60 @@ int scf_conv_dma_dispatch(ConvK k, int N, bool dry_run, int* info, hipStream_t s
 }
 
 
+// The first block of a down-sampling residual stage: `a` = the captured pixel-split launch of its 3x3 / stride-2 / pad-1 layer, kb = the
+// planned 1x1 / stride-2 / pad-0 shortcut on the same input.  One launch of a's grid computes both (conv_dma_body, SH).
+// SCF_EUNSUPPORTED: not that form, or the shortcut's weight cells do not fit behind a's stages -- the caller launches the two layers.
+template <int WM, int WN, bool PX4>
+static int launch_dma_shared(const ConvK& ka, const ConvK& kb, int nblk, size_t lds_bytes, hipStream_t st) {
+  if (lds_bytes > 64 * 1024) {
+    static std::atomic<unsigned long long> raised{0};
+    int dev = 0;
+    if (hipGetDevice(&dev) != hipSuccess) return SCF_ELAUNCH;
+    const unsigned long long bit = 1ull << (dev & 63);
+    if (!(raised.load(std::memory_order_relaxed) & bit)) {
+      if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_dma_shared_kernel<WM, WN, PX4>),
+                              hipFuncAttributeMaxDynamicSharedMemorySize, SCF_DMA_LDS_MAX) != hipSuccess)
+        return SCF_ELAUNCH;
+      raised.fetch_or(bit, std::memory_order_relaxed);
+    }
+  }
+  scf_launch((conv_dma_shared_kernel<WM, WN, PX4>), dim3((unsigned)nblk), dim3(256), lds_bytes, st, ka, kb);
+  return scf_launch_status();
+}
+
+int scf_conv_dma_shared_launch(const ScfLaunchCap& a, const ConvK& kb, hipStream_t st) {
+  const ConvK& ka = a.k;
+  if (a.WM <= 0 || a.nblk <= 0 || !ka.wp4 || !kb.wp4) return SCF_EUNSUPPORTED;
+  // the form: one input tensor, 3x3 / s2 / pad 1 in 8-channel chunks beside 1x1 / s2 / pad 0, the same output channels and map
+  if (ka.in0 != kb.in0 || ka.in1 || kb.in1 || ka.in0_ns != kb.in0_ns || ka.Cin != kb.Cin || ka.H != kb.H || ka.W != kb.W ||
+      ka.Cout != kb.Cout || ka.Ho != kb.Ho || ka.Wo != kb.Wo)
+    return SCF_EUNSUPPORTED;
+  if (ka.KH != 3 || ka.KW != 3 || ka.stride != 2 || ka.pad_h != 1 || ka.pad_w != 1 || ka.G4 != 1 || (ka.Cin & 7) != 0 ||
+      kb.T != 1 || kb.pad_h != 0 || kb.pad_w != 0 || !(kb.stride == 2 || kb.in_step == 2))
+    return SCF_EUNSUPPORTED;
+  // plain / affine epilogues into row-major planes, no K slices
+  if (ka.kslices > 1 || kb.kslices > 1 || ka.out_tile || kb.out_tile || ka.mode != SCF_CONV_PLAIN || kb.mode != SCF_CONV_PLAIN ||
+      kb.Mld4 != ka.Mld4)
+    return SCF_EUNSUPPORTED;
+  const size_t ldsb = a.ldsb + (size_t)2 * (2 * a.WM * 32) * 16;      // two buffers, [2 rows][BM] float4 each
+  if (ldsb > SCF_DMA_LDS_MAX) return SCF_EUNSUPPORTED;
+#define SCF_CASE(M, Nn)                                                                             \
+  if (a.WM == M && a.WN == Nn)                                                                      \
+    return a.px4 ? launch_dma_shared<M, Nn, true>(ka, kb, a.nblk, ldsb, st) : launch_dma_shared<M, Nn, false>(ka, kb, a.nblk, ldsb, st);
+  // (nine taps of a (2,2) or (3,1) tile's weights and its stride-2 patch never fit two buffers in half a CU's LDS: the dispatch
+  // above gives a 3x3 / s2 layer in 8-channel chunks the (2,1) or the (1,1) tile)
+  SCF_CASE(2, 1) SCF_CASE(1, 1)
+#undef SCF_CASE
+  return SCF_EUNSUPPORTED;
+}
+
 // r6: a K-split layer and a THIN-INPUT layer (conv_taps_body, WM = 1) in one launch: the motion encoder's corr_net.0 (1x1 324 -> 256) and
 // flow_net.0 (7x7 2 -> 128) read different tensors and feed different branches.  The thin-input blocks use the first four waves.
 template <bool PX4, int NG>
 __global__ __launch_bounds__(256 * NG, 1) void conv_dma_taps_pair_kernel(ConvK pa, ConvK pb, const float* __restrict__ wtb, int Kpb, int PWpb,
                                                                          int nba) {
   if ((int)blockIdx.x < nba) {
-    conv_dma_body<1, 1, 2, true, PX4, NG>(pa, (int)blockIdx.x, nba);
+    conv_dma_body<1, 1, 2, true, PX4, NG>(pa, (int)blockIdx.x, nba, pa);
   } else {
     if (NG > 1 && threadIdx.x >= 256) return;      // (whole waves: the body's barriers count the waves that are still alive)
     conv_taps_body<1>(pb, wtb, Kpb, PWpb, (int)blockIdx.x - nba, (int)gridDim.x - nba);

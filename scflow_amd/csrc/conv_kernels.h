@@ -407,6 +407,7 @@ struct ScfLaunchCap {
   int nblk = 0;
   size_t ldsb = 0;
   int variant = -1;           // kernel instantiation id (family-specific); -1 = not pairable (pixel-split tiles, persistent, ...)
+  int WM = 0, WN = 0, px4 = 0; // LDS-DMA pixel-split tile (WM > 0) and its patch staging: scf_conv_dma_shared_launch
   const float* wt = nullptr;  // taps: the packing
   int Kp = 0, PWp = 0;        // taps
   alignas(8) unsigned char aux[96] = {};      // Winograd: the kernel's second argument (WinoK)
@@ -429,3 +430,4 @@ int scf_conv_thin_pair_launch(const ScfLaunchCap& a, const ScfLaunchCap& b, hipS
 int scf_conv_dma_dispatch(ConvK k, int N, bool dry_run, int* info, hipStream_t st, ScfLaunchCap* cap = nullptr);
 int scf_conv_dma_pair_launch(const ScfLaunchCap& a, const ScfLaunchCap& b, hipStream_t st);
 int scf_conv_dma_taps_pair_launch(const ScfLaunchCap& dma, const ScfLaunchCap& taps, hipStream_t st);      // K-split layer | thin-input layer
+int scf_conv_dma_shared_launch(const ScfLaunchCap& c3, const ConvK& shortcut, hipStream_t st);      // 3x3 / s2 layer + the 1x1 / s2 shortcut on its input

@@ -773,10 +773,39 @@ static bool capture(const scf_conv_desc* d, scf_stream_t stream, ScfLaunchCap* c
 
 typedef int (*PairLaunch)(const ScfLaunchCap&, const ScfLaunchCap&, hipStream_t);
 
+// the first block of a down-sampling residual stage: a = its 3x3 / stride-2 / pad-1 layer, b = the 1x1 / stride-2 / pad-0 shortcut,
+// both reading ONE tensor
+static bool shared_input_form(const scf_conv_desc* a, const scf_conv_desc* b) {
+  return a->in0 == b->in0 && a->C1 == 0 && b->C1 == 0 && a->C0 == b->C0 && a->N == b->N && a->H == b->H && a->W == b->W &&
+         a->in0_nstride == b->in0_nstride && a->KH == 3 && a->KW == 3 && a->stride == 2 && a->pad_h == 1 && a->pad_w == 1 &&
+         b->KH == 1 && b->KW == 1 && b->stride == 2 && b->pad_h == 0 && b->pad_w == 0;
+}
+
 extern "C" int scf_conv2d_pair(const scf_conv_desc* a, const scf_conv_desc* b, scf_stream_t stream) {
   if (!a || !b) return SCF_EINVAL;
   ScfLaunchCap ca, cb;
   int fa = 0, fb = 0;
+  if (shared_input_form(a, b)) {
+    // where the 3x3 layer takes a full-grid pixel-split tile of the LDS-DMA kernel, its blocks compute the shortcut too, from the
+    // patch they have staged anyway (conv_dma.hip, SH); the shortcut keeps the bits of its own launch.  On small grids (K-split
+    // tile), with another family, or with scf_tune(SCF_TUNE_CONV_PAIR, 1): the two launches
+    if (g_pair_mode.load(std::memory_order_relaxed) != 1) {
+      ConvReq ra, rb;
+      ra.cap = &ca; rb.cap = &cb;
+      if (conv2d_walk(a, stream, ra) == SCF_OK && ra.which == SCF_KERNEL_DMA && ca.WM > 0 &&
+          conv2d_walk(b, stream, rb) == SCF_OK && rb.which == SCF_KERNEL_DMA) {
+        const int rc = scf_conv_dma_shared_launch(ca, cb.k, scf_stream(stream));
+        if (rc == SCF_OK) {
+          conv_log_push(a, SCF_KERNEL_DMA, 1);
+          conv_log_push(b, SCF_KERNEL_DMA, 2);
+          return SCF_OK;
+        }
+        if (rc != SCF_EUNSUPPORTED) return rc;
+      }
+    }
+    const int r1 = scf_conv2d(a, stream);
+    return r1 != SCF_OK ? r1 : scf_conv2d(b, stream);
+  }
   // scf_tune(SCF_TUNE_CONV_PAIR, 1): never one launch
   if (g_pair_mode.load(std::memory_order_relaxed) != 1 && capture(a, stream, &ca, &fa) && capture(b, stream, &cb, &fb)) {
     // one launch while both grids are resident together: past that the merged launch is a second round of blocks and loses

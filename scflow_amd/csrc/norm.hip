@@ -135,6 +135,116 @@ extern "C" int scf_instance_norm(const float* x, const float* res, float* out, i
   return scf_launch_status();
 }
 
+// two sums over an NT-thread workgroup at once: each in block_sum's order, one pair of barriers for both
+template <int NT>
+__device__ __forceinline__ void block_sum2(float& a, float& b, float* red) {
+  a = wave_sum(a);
+  b = wave_sum(b);
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __syncthreads();
+  if (lane == 0) {
+    red[wave] = a;
+    red[NT / 64 + wave] = b;
+  }
+  __syncthreads();
+  float s = 0.f, t = 0.f;
+#pragma unroll
+  for (int w = 0; w < NT / 64; w += 4) {
+    s += (red[w] + red[w + 1]) + (red[w + 2] + red[w + 3]);
+    t += (red[NT / 64 + w] + red[NT / 64 + w + 1]) + (red[NT / 64 + w + 2] + red[NT / 64 + w + 3]);
+  }
+  a = s;
+  b = t;
+}
+
+// ---------------------------------------------------------------------------------
+// The tail of a down-sampling block (resnet.py:88-94 with a shortcut): out = relu?(IN(x) + IN(r)) with BOTH planes in
+// registers -- the shortcut's own normalisation pass (one read and one write of r) is gone.  Same bits as
+// instance_norm_kernel<VEC4>(r -> r) followed by instance_norm_kernel<VEC4>(x, res = r): the same partial sums in the same
+// order, IN(r) rounded to fp32 where the two-pass form stores it, and no multiply-add contraction except the one
+// instance_norm_kernel compiles to -- its sum of squares is fma(a, a, b * b) in the VEC4 = 4 / 16 forms and plain multiplies
+// and adds in the VEC4 = 1 form; its (v - mean) * rstd and + res are separate operations in all of them.  Contraction is
+// therefore switched off here and that one fma is written out (tests/test_gpu_downsample_block.py compares the bits).
+// ---------------------------------------------------------------------------------
+template <int VEC4>
+__device__ __forceinline__ float sum_sq4(float a, float b, float c, float d) {
+#pragma clang fp contract(off)
+  if constexpr (VEC4 == 1) return (a * a + b * b) + (c * c + d * d);
+  else return __builtin_fmaf(a, a, b * b) + __builtin_fmaf(c, c, d * d);
+}
+
+template <int VEC4>
+__global__ __launch_bounds__(256) void instance_norm_res_norm_kernel(const float* x, const float* r,   // either may alias out
+                                                                     float* out, int HW, float eps, int relu) {
+#pragma clang fp contract(off)
+  constexpr int NT = 256;
+  __shared__ float red[2 * NT / 64];
+  const long long pl = blockIdx.x;
+  const float4* xp = reinterpret_cast<const float4*>(x + pl * HW);
+  const float4* rp = reinterpret_cast<const float4*>(r + pl * HW);
+  const int n4 = HW >> 2;
+  float4 v[VEC4], u[VEC4];
+#pragma unroll
+  for (int i = 0; i < VEC4; ++i) {
+    const int idx = i * NT + threadIdx.x;
+    v[i] = idx < n4 ? xp[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+    u[i] = idx < n4 ? rp[idx] : make_float4(0.f, 0.f, 0.f, 0.f);
+  }
+  float sx = 0.f, sr = 0.f;
+#pragma unroll
+  for (int i = 0; i < VEC4; ++i) {
+    sx += (v[i].x + v[i].y) + (v[i].z + v[i].w);
+    sr += (u[i].x + u[i].y) + (u[i].z + u[i].w);
+  }
+  block_sum2<NT>(sx, sr, red);
+  const float mx = sx / (float)HW, mr = sr / (float)HW;
+  float qx = 0.f, qr = 0.f;
+#pragma unroll
+  for (int i = 0; i < VEC4; ++i) {
+    const int idx = i * NT + threadIdx.x;
+    if (idx < n4) {
+      qx += sum_sq4<VEC4>(v[i].x - mx, v[i].y - mx, v[i].z - mx, v[i].w - mx);
+      qr += sum_sq4<VEC4>(u[i].x - mr, u[i].y - mr, u[i].z - mr, u[i].w - mr);
+    }
+  }
+  block_sum2<NT>(qx, qr, red);
+  const float rsx = 1.0f / sqrtf(qx / (float)HW + eps), rsr = 1.0f / sqrtf(qr / (float)HW + eps);
+  float4* op = reinterpret_cast<float4*>(out + pl * HW);
+#pragma unroll
+  for (int i = 0; i < VEC4; ++i) {
+    const int idx = i * NT + threadIdx.x;
+    if (idx < n4) {
+      float4 o;
+      o.x = (v[i].x - mx) * rsx + (u[i].x - mr) * rsr;
+      o.y = (v[i].y - mx) * rsx + (u[i].y - mr) * rsr;
+      o.z = (v[i].z - mx) * rsx + (u[i].z - mr) * rsr;
+      o.w = (v[i].w - mx) * rsx + (u[i].w - mr) * rsr;
+      if (relu) {
+        o.x = fmaxf(o.x, 0.f); o.y = fmaxf(o.y, 0.f); o.z = fmaxf(o.z, 0.f); o.w = fmaxf(o.w, 0.f);
+      }
+      scf_store4<(SCF_ST_SC1 & 2) != 0>(reinterpret_cast<float*>(op + idx), o.x, o.y, o.z, o.w);
+    }
+  }
+}
+
+extern "C" int scf_instance_norm_res_norm(const float* x, float* r, float* out, int64_t planes, int HW, float eps,
+                                          int relu, scf_stream_t stream) {
+  if (!x || !r || !out || planes <= 0 || HW <= 0) return SCF_EINVAL;
+  if (planes > 0x7fffffffLL) return SCF_EUNSUPPORTED;
+  const bool vec = (HW % 4 == 0) && ((((uintptr_t)x | (uintptr_t)out | (uintptr_t)r) & 15) == 0);
+  const int n4 = HW / 4;
+  if (!vec || n4 > 4096) {      // planes beyond two register sets: the two passes, IN(r) in place
+    const int rc = scf_instance_norm(r, nullptr, r, planes, HW, eps, 0, stream);
+    return rc != SCF_OK ? rc : scf_instance_norm(x, r, out, planes, HW, eps, relu, stream);
+  }
+  hipStream_t st = scf_stream(stream);
+  const dim3 grid((unsigned)planes), blk(256);
+  if (n4 <= 256) scf_launch(instance_norm_res_norm_kernel<1>, grid, blk, 0, st, x, (const float*)r, out, HW, eps, relu);
+  else if (n4 <= 1024) scf_launch(instance_norm_res_norm_kernel<4>, grid, blk, 0, st, x, (const float*)r, out, HW, eps, relu);
+  else scf_launch(instance_norm_res_norm_kernel<16>, grid, blk, 0, st, x, (const float*)r, out, HW, eps, relu);
+  return scf_launch_status();
+}
+
 // ---------------------------------------------------------------------------------
 // GroupNorm(G, eps) with affine + ReLU: pose_head.py:151-159 (norm_cfg GN, 32 groups).
 // Channels of a group are contiguous in NCHW, so a group is one contiguous run of

@@ -191,19 +191,22 @@ class _BasicBlock(HipModule):
         """resnet.py:67-94.  BN (eval) is folded into the conv epilogue; IN needs the
         whole plane, so it is its own kernel (residual add + ReLU fused there)."""
         p = self.packed
+        # a block with a shortcut convolution hands both layers that read x to ops.conv2d_pair: on full grids the blocks of a
+        # 3x3 / s2 conv1 compute the 1x1 / s2 shortcut from the patch they stage anyway (conv_dma.hip, shared-input form)
         if self.kind == 'BN':
-            y = ops.conv2d(p['c1'], x, act=ACT_RELU)
-            idt = ops.conv2d(p['ds'], x) if 'ds' in p else x
+            if 'ds' in p:
+                y, idt = ops.conv2d_pair((p['c1'], x, dict(act=ACT_RELU)), (p['ds'], x))
+            else:
+                y, idt = ops.conv2d(p['c1'], x, act=ACT_RELU), x
             return ops.conv2d(p['c2'], y, res=idt, act=ACT_RELU)
-        y = ops.conv2d(p['c1'], x)
+        if 'ds' in p:
+            y, idt = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
+        else:
+            y, idt = ops.conv2d(p['c1'], x), x
         ops.instance_norm(y, relu=True, out=y)
         y2 = ops.conv2d(p['c2'], y)
-        if 'ds' in p:
-            idt = ops.conv2d(p['ds'], x)
-            ops.instance_norm(idt, out=idt)
-        else:
-            idt = x
-        return ops.instance_norm(y2, res=idt, relu=True, out=y2)
+        # (the shortcut's own normalisation rides in the block's final pass)
+        return ops.instance_norm(y2, res=idt, relu=True, out=y2, res_norm='ds' in p)
 
 
 @ENCODERS.register_module()
@@ -292,11 +295,10 @@ def raft_encoder_pair(fe: 'RAFTEncoder', xf: Tensor, ce: 'RAFTEncoder', xc: Tens
             ops.instance_norm(tf_, relu=True, out=tf_)
             if 'ds' in qf:
                 if_, ic_ = ops.conv2d_pair((qf['ds'], yf), (qc['ds'], yc))
-                ops.instance_norm(if_, out=if_)
             else:
                 if_, ic_ = yf, yc
             uf_, yc = ops.conv2d_pair((qf['c2'], tf_), (qc['c2'], tc_, dict(res=ic_, act=ACT_RELU)))
-            yf = ops.instance_norm(uf_, res=if_, relu=True, out=uf_)
+            yf = ops.instance_norm(uf_, res=if_, relu=True, out=uf_, res_norm='ds' in qf)
     return ops.conv2d_pair((pf['head'], yf), (pc['head'], yc, dict(out=out_c, act=head_act, act2=head_act2,
                                                                   act_split=head_split)))
 

@@ -1140,11 +1140,20 @@ def lookup_timing_read():
 
 # ------------------------------------------------------------- norms etc.
 def instance_norm(x: Tensor, res: Optional[Tensor] = None, relu: bool = False,
-                  out: Optional[Tensor] = None, eps: float = 1e-5) -> Tensor:
+                  out: Optional[Tensor] = None, eps: float = 1e-5, res_norm: bool = False) -> Tensor:
+    """``relu?(IN(x) + res?)``.  ``res_norm``: ``res`` is normalised too, ``relu?(IN(x) + IN(res))`` -- the tail of a residual
+    block with a shortcut convolution, one pass over both for planes of up to 128 x 128 (``scf_instance_norm_res_norm``); the
+    bits are those of ``instance_norm(res, out=res)`` followed by ``instance_norm(x, res=res)``, and ``res`` is scratch."""
     px = _dense(x, 'x')
     n, c, h, w = x.shape
     if out is None:
         out = torch.empty_like(x)
+    if res_norm:
+        if res is None or res.shape != x.shape:
+            raise ValueError('instance_norm(res_norm=True): res of the shape of x')
+        _lib.check(_lib.load().scf_instance_norm_res_norm(px, _dense(res, 'res'), _dense(out, 'out'), n * c, h * w, eps,
+                                                          int(relu), _stream()), 'scf_instance_norm_res_norm')
+        return out
     _lib.check(_lib.load().scf_instance_norm(px, _opt(res, 'res'), _dense(out, 'out'), n * c,
                                              h * w, eps, int(relu), _stream()),
                'scf_instance_norm')
