@@ -633,6 +633,67 @@ int scf_patch_boxes(const scf_mesh_store* mesh, const int32_t* labels, const flo
 int scf_patch_extract(const uint8_t* frames, int F, int frame_h, int frame_w, const int32_t* frame_index, int N,
                       const void* workspace, const scf_patch_params* params, float* out, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Train patches.                     replaces the train_pipeline of configs/refine_datasets/ycbv_real.py (LoadMasks,
+ *                                    PoseJitter, ComputeBbox, Crop(size_range=(lo, hi)), RandomHSV, RandomNoise,
+ *                                    RandomSmooth, Resize, Pad, RemapPose(keep_intrinsic=False), Normalize).
+ * Added without a version bump (SCF_VERSION stays at .3): the presence of scf_pose_jitter, scf_patch_boxes_train,
+ * scf_patch_extract_train, scf_patch_train_workspace_bytes and scf_patch_train_route marks the feature.
+ * patch_train.hip states the semantics in full (cv2 parity is not claimed); in short:
+ *   random     counter-based: every draw is hash(seed, sample_id, stream, counter) (splitmix64 finaliser), sample_id =
+ *              id_base + n or sample_ids[n] (int64, device; may be NULL): an object's draws do not depend on its batch.
+ *   jitter     up to max_tries tries of dR = Rx(a2) Ry(a1) Rz(a0) (degrees, N(jitter_angle)), noise N(jitter_x/y/z), in
+ *              fp64; R_ref = dR R_gt, t_ref = t_gt + noise; a try is rejected when its rotation error (degrees),
+ *              |noise| or ADD / diameter exceeds its limit (a negative limit = none).  No accepted try, a label outside
+ *              the mesh store, or an empty class under add_limit: the gt pose, errors 0, ok = 0.  mesh may be NULL
+ *              without add_limit (add_error is then NaN); diameters is (num_classes) fp32 on the device.
+ *              rot_error holds |noise| and trans_error the angle, as the reference's init_rot_error /
+ *              init_trans_error do, unless fix_error_swap_quirk is set.
+ *   boxes      scf_patch_boxes with size_ratio drawn per object from size_range; also draws the colour augmentation
+ *              and writes draws (N,8) fp64 = (size_ratio, h gain, s gain, v gain, sigma, k, hsv on, noise on).
+ *              workspace: scf_patch_train_workspace_bytes(N) bytes; its first scf_patch_workspace_bytes(N) bytes are
+ *              the records scf_patch_extract reads.
+ *   extract    scf_patch_extract with RandomHSV, RandomNoise and RandomSmooth applied to the crop patch before the
+ *              resize, and the object's mask: masks (N,frame_h,frame_w) uint8, nonzero = object, cropped with fill 0,
+ *              resized to nearest, padded with mask_pad_val -> mask_out (N,out_h,out_w) bytes 0 / 1.  masks and
+ *              mask_out are both NULL or both given.
+ *   route      scf_patch_train_route(ph, pw, new_h, new_w, k) = 0 when an object of that crop size, resized size and
+ *              smoothing kernel runs from LDS, 1 when its threads read the frame directly (same bits), SCF_EINVAL
+ *              for bad arguments.  A host function: the kernel's own formula.
+ * --------------------------------------------------------------------------------- */
+typedef struct scf_patch_aug_params {
+  uint64_t seed;
+  double jitter_angle[2];        /* PoseJitter jitter_angle_dis: mean, std in degrees (std >= 0)       */
+  double jitter_x[2], jitter_y[2], jitter_z[2];
+  double angle_limit;            /* degrees; negative: none                                            */
+  double translation_limit;      /* negative: none                                                     */
+  double add_limit;              /* in diameters; negative: none                                       */
+  double size_range[2];          /* Crop size_range, 0 < lo <= hi                                      */
+  double hsv_ratio[3];           /* RandomHSV h_ratio, s_ratio, v_ratio, each in [0, 1)                */
+  double hsv_p, noise_p, smooth_p; /* the transforms' p in [0, 1]; 0 switches one off                  */
+  double noise_ratio;            /* RandomNoise noise_ratio (>= 0)                                     */
+  int32_t max_tries;             /* 1..4096                                                            */
+  int32_t max_kernel_size;       /* RandomSmooth max_kernel_size, 1..15: k is drawn from the reference's list
+                                    {1, 3, .., 2 (max_kernel_size / 2) + 1}, so an even value also draws
+                                    max_kernel_size + 1 (4 gives {1, 3, 5}; color_transform.py:125)     */
+  int32_t fix_error_swap_quirk;  /* 0: rot_error / trans_error swapped, as the reference; 1: as named  */
+  int32_t mask_pad_val;          /* Pad pad_val['mask']: 0 or not                                      */
+} scf_patch_aug_params;
+int scf_pose_jitter(const scf_mesh_store* mesh, const float* diameters, const int32_t* labels, const float* R_gt,
+                    const float* t_gt, int N, int vertex_stride, const scf_patch_aug_params* aug, int64_t id_base,
+                    const int64_t* sample_ids, float* R_ref, float* t_ref, float* add_error, float* rot_error,
+                    float* trans_error, int32_t* ok, int32_t* tries, scf_stream_t stream);
+int64_t scf_patch_train_workspace_bytes(int N);
+int scf_patch_train_route(int ph, int pw, int new_h, int new_w, int k);
+int scf_patch_boxes_train(const scf_mesh_store* mesh, const int32_t* labels, const float* R, const float* t,
+                          const float* K, const int32_t* crop_in, int N, int frame_h, int frame_w,
+                          const scf_patch_params* params, const scf_patch_aug_params* aug, int64_t id_base,
+                          const int64_t* sample_ids, double* draws, float* box, int32_t* crop, float* scale,
+                          float* transform_matrix, float* k, int32_t* valid, void* workspace, scf_stream_t stream);
+int scf_patch_extract_train(const uint8_t* frames, int F, int frame_h, int frame_w, const int32_t* frame_index,
+                            const uint8_t* masks, int N, const void* workspace, const scf_patch_params* params,
+                            const scf_patch_aug_params* aug, float* out, uint8_t* mask_out, scf_stream_t stream);
+
 /* filter_flow_by_mask (models/utils/flow.py:6-26), in place on flow (N,2,H,W): a vector is set
  * to invalid_num when both components are >= invalid_num or when mask (N,H,W), sampled
  * bilinearly (zeros padding) at the vector's end point, is < 0.9.  The end point is normalised

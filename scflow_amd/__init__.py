@@ -24,4 +24,4 @@ from .config import raft_loss_cfgs, raft_model_cfg, scflow_loss_cfgs, scflow_mod
 from .weights import fill_state_dict  # noqa: F401
 from .synthetic import make_inputs  # noqa: F401
 from .mesh import Fragments, Mesh, MeshRenderer, MeshStore, make_mesh, read_ply  # noqa: F401
-from .patches import PatchPipeline  # noqa: F401
+from .patches import PatchPipeline, TrainPatchPipeline  # noqa: F401

@@ -124,6 +124,16 @@ class PatchParams(C.Structure):
                 ('pad_val', C.c_int32 * 3), ('mean', C.c_float * 3), ('std', C.c_float * 3)]
 
 
+class PatchAugParams(C.Structure):
+    """mirror of ``scf_patch_aug_params`` (include/scflow_hip.h)."""
+    _fields_ = [('seed', C.c_uint64), ('jitter_angle', C.c_double * 2), ('jitter_x', C.c_double * 2),
+                ('jitter_y', C.c_double * 2), ('jitter_z', C.c_double * 2), ('angle_limit', C.c_double),
+                ('translation_limit', C.c_double), ('add_limit', C.c_double), ('size_range', C.c_double * 2),
+                ('hsv_ratio', C.c_double * 3), ('hsv_p', C.c_double), ('noise_p', C.c_double), ('smooth_p', C.c_double),
+                ('noise_ratio', C.c_double), ('max_tries', C.c_int32), ('max_kernel_size', C.c_int32),
+                ('fix_error_swap_quirk', C.c_int32), ('mask_pad_val', C.c_int32)]
+
+
 class IterGN(C.Structure):
     """mirror of ``scf_iter_gn``."""
     _fields_ = [('gamma', _fp), ('beta', _fp), ('out', _fp),
@@ -247,6 +257,15 @@ SIGNATURES = {
                                   C.POINTER(PatchParams), _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
     'scf_patch_extract': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, C.c_int, _fp, C.POINTER(PatchParams), _fp,
                                     _fp]),
+    'scf_pose_jitter': (C.c_int, [C.POINTER(MeshStore), _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.POINTER(PatchAugParams),
+                                  C.c_int64, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_patch_train_workspace_bytes': (C.c_int64, [C.c_int]),
+    'scf_patch_train_route': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_patch_boxes_train': (C.c_int, [C.POINTER(MeshStore), _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int,
+                                        C.POINTER(PatchParams), C.POINTER(PatchAugParams), C.c_int64, _fp, _fp, _fp, _fp,
+                                        _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_patch_extract_train': (C.c_int, [_fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_int, _fp, C.POINTER(PatchParams),
+                                          C.POINTER(PatchAugParams), _fp, _fp, _fp]),
     'scf_unproject_depth': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_resize_bilinear': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),

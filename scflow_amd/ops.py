@@ -1581,6 +1581,223 @@ def extract_patches(frames: Tensor, frame_index: Tensor, records: Tensor, params
     return out
 
 
+def patch_aug_params(*, seed: int = 0, jitter_angle_dis=(0., 15.), jitter_x_dis=(0., 15.), jitter_y_dis=(0., 15.),
+                     jitter_z_dis=(0., 50.), angle_limit: Optional[float] = 45., translation_limit: Optional[float] = 200.,
+                     add_limit: Optional[float] = 1., max_tries: int = 64, size_range=(1.0, 1.25), h_ratio: float = 0.2,
+                     s_ratio: float = 0.5, v_ratio: float = 0.5, hsv_p: float = 1.0, noise_ratio: float = 0.1,
+                     noise_p: float = 1.0, max_kernel_size: float = 5, smooth_p: float = 1.0,
+                     fix_error_swap_quirk: bool = False, mask_pad_val: int = 0) -> '_lib.PatchAugParams':
+    """``scf_patch_aug_params`` from the train pipeline's settings (the defaults are the shipped train_pipeline of
+    ycbv_real.py).  A limit of None is not applied; a ``p`` of 0 switches its transform off.  The values are checked here
+    so that a bad one is named; the C entries refuse them too (``SCF_EINVAL``)."""
+    if int(seed) != seed or not 0 <= seed < 2 ** 64:
+        raise _lib.ScflowHipError(f'patch_aug_params: seed must be an integer in [0, 2^64), got {seed!r}')
+    pairs = []
+    for nm, v in (('jitter_angle_dis', jitter_angle_dis), ('jitter_x_dis', jitter_x_dis), ('jitter_y_dis', jitter_y_dis),
+                  ('jitter_z_dis', jitter_z_dis)):
+        if not isinstance(v, (list, tuple)) or len(v) != 2 or not all(math.isfinite(float(x)) for x in v) or float(v[1]) < 0:
+            raise _lib.ScflowHipError(f'patch_aug_params: {nm}={v!r} must be (mean, std >= 0)')
+        pairs.append((float(v[0]), float(v[1])))
+    limits = []
+    for nm, v in (('angle_limit', angle_limit), ('translation_limit', translation_limit), ('add_limit', add_limit)):
+        if v is not None and not (math.isfinite(float(v)) and float(v) >= 0):
+            raise _lib.ScflowHipError(f'patch_aug_params: {nm}={v!r} must be None or finite and >= 0')
+        limits.append(-1.0 if v is None else float(v))
+    lo, hi = (float(x) for x in size_range)
+    if not (0 < lo <= hi and math.isfinite(hi)):
+        raise _lib.ScflowHipError(f'patch_aug_params: size_range={size_range!r} needs 0 < lo <= hi')
+    for nm, v in (('h_ratio', h_ratio), ('s_ratio', s_ratio), ('v_ratio', v_ratio)):
+        if not 0 <= float(v) < 1:
+            raise _lib.ScflowHipError(f'patch_aug_params: {nm}={v!r} must be in [0, 1) (a gain must stay positive)')
+    for nm, v in (('hsv_p', hsv_p), ('noise_p', noise_p), ('smooth_p', smooth_p)):
+        if not 0 <= float(v) <= 1:
+            raise _lib.ScflowHipError(f'patch_aug_params: {nm}={v!r} must be in [0, 1]')
+    if not (math.isfinite(float(noise_ratio)) and float(noise_ratio) >= 0):
+        raise _lib.ScflowHipError(f'patch_aug_params: noise_ratio={noise_ratio!r} must be finite and >= 0')
+    if isinstance(max_tries, bool) or int(max_tries) != max_tries or not 1 <= max_tries <= 4096:
+        raise _lib.ScflowHipError(f'patch_aug_params: max_tries={max_tries!r} must be an integer in 1..4096')
+    # the reference truncates it (int(5.) = 5) and draws k from [2 i + 1 for i in range(max_kernel_size // 2 + 1)]: an even
+    # value also draws max_kernel_size + 1
+    if not 1 <= int(max_kernel_size) <= 15:
+        raise _lib.ScflowHipError(f'patch_aug_params: max_kernel_size={max_kernel_size!r} must be in 1..15')
+    d2, d3 = C.c_double * 2, C.c_double * 3
+    return _lib.PatchAugParams(int(seed), d2(*pairs[0]), d2(*pairs[1]), d2(*pairs[2]), d2(*pairs[3]), limits[0], limits[1],
+                               limits[2], d2(lo, hi), d3(float(h_ratio), float(s_ratio), float(v_ratio)), float(hsv_p),
+                               float(noise_p), float(smooth_p), float(noise_ratio), int(max_tries), int(max_kernel_size),
+                               int(bool(fix_error_swap_quirk)), int(bool(mask_pad_val)))
+
+
+def _mesh_store(mesh, dev, what: str) -> '_lib.MeshStore':
+    _dense(mesh.verts, 'verts')
+    if mesh.vert_offset.device != dev or mesh.vert_offset.dtype != torch.int32 or not mesh.vert_offset.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: the mesh store must live on {dev} (MeshStore.on(device))')
+    return _lib.MeshStore(mesh.verts.data_ptr(), mesh.normals.data_ptr(), mesh.colors.data_ptr(), mesh.faces.data_ptr(),
+                          mesh.vert_offset.data_ptr(), mesh.face_offset.data_ptr(), int(mesh.num_classes),
+                          int(mesh.max_faces))
+
+
+def _sample_ids(sample_ids: Optional[Tensor], n: int, dev, what: str) -> Optional[int]:
+    if sample_ids is None:
+        return None
+    if (not isinstance(sample_ids, torch.Tensor) or not sample_ids.is_cuda or sample_ids.dtype != torch.int64
+            or tuple(sample_ids.shape) != (n,) or not sample_ids.is_contiguous() or sample_ids.device != dev):
+        raise _lib.ScflowHipError(f'{what}: sample_ids must be a contiguous int64 GPU tensor of shape {(n,)} on {dev}')
+    return sample_ids.data_ptr()
+
+
+def _id_base(id_base: int, what: str) -> int:
+    if isinstance(id_base, bool) or int(id_base) != id_base or not 0 <= id_base < 2 ** 62:
+        raise _lib.ScflowHipError(f'{what}: id_base must be an integer in [0, 2^62), got {id_base!r}')
+    return int(id_base)
+
+
+def pose_jitter(mesh, diameters: Optional[Tensor], labels: Optional[Tensor], gt_rot: Tensor, gt_trans: Tensor,
+                aug: '_lib.PatchAugParams', *, vertex_stride: int = 1, id_base: int = 0,
+                sample_ids: Optional[Tensor] = None) -> dict:
+    """PoseJitter for a batch (``scf_pose_jitter``; patch_train.hip states the semantics).  ``mesh`` is a
+    ``mesh.DeviceMesh`` with ``diameters`` (num_classes,) float32 and ``labels`` (N,) int on the GPU, or all three None
+    when ``aug`` has no add_limit; gt_rot (N,3,3), gt_trans (N,3).
+    -> dict(rot (N,3,3), trans (N,3), add_error, rot_error, trans_error (N) float32, ok, tries (N) int32).
+    No host synchronisation."""
+    n = gt_rot.shape[0] if isinstance(gt_rot, torch.Tensor) and gt_rot.dim() == 3 else -1
+    if n <= 0:
+        raise _lib.ScflowHipError('pose_jitter: gt_rot must be (N,3,3) with N > 0')
+    if int(vertex_stride) < 1:
+        raise _lib.ScflowHipError(f'pose_jitter: vertex_stride={vertex_stride} must be >= 1')
+    if mesh is None and aug.add_limit >= 0:
+        raise _lib.ScflowHipError('pose_jitter: add_limit needs the mesh store and the diameters')
+    rp, tp = _mats(gt_rot, n, (3, 3), 'gt_rot'), _mats(gt_trans, n, (3,), 'gt_trans')
+    dev = gt_rot.device
+    store, lab, dp = None, None, None
+    if mesh is not None:
+        if diameters is None or labels is None:
+            raise _lib.ScflowHipError('pose_jitter: a mesh needs diameters and labels')
+        store = _mesh_store(mesh, dev, 'pose_jitter')
+        if tuple(diameters.shape) != (int(mesh.num_classes),) or diameters.device != dev:
+            raise _lib.ScflowHipError(f'pose_jitter: diameters must be ({int(mesh.num_classes)},) float32 on {dev}')
+        dp = _dense(diameters, 'diameters')
+        lab = _int_vec(labels, (n,), dev, 'pose_jitter: labels')
+    sid = _sample_ids(sample_ids, n, dev, 'pose_jitter')
+    f32 = lambda *shape: torch.empty(shape, dtype=torch.float32, device=dev)
+    out = dict(rot=f32(n, 3, 3), trans=f32(n, 3), add_error=f32(n), rot_error=f32(n), trans_error=f32(n),
+               ok=torch.empty((n,), dtype=torch.int32, device=dev), tries=torch.empty((n,), dtype=torch.int32, device=dev))
+    _lib.check(_lib.load().scf_pose_jitter(
+        None if store is None else C.byref(store), dp, None if lab is None else lab.data_ptr(), rp, tp, n,
+        int(vertex_stride), C.byref(aug), _id_base(id_base, 'pose_jitter'), sid, out['rot'].data_ptr(),
+        out['trans'].data_ptr(), out['add_error'].data_ptr(), out['rot_error'].data_ptr(), out['trans_error'].data_ptr(),
+        out['ok'].data_ptr(), out['tries'].data_ptr(), _stream()), 'scf_pose_jitter')
+    return out
+
+
+def patch_train_route(ph: int, pw: int, new_h: int, new_w: int, k: int) -> str:
+    """the route ``extract_patches_train`` takes for an object with a ``ph x pw`` crop patch resized to
+    ``new_h x new_w`` under a ``k x k`` smoothing kernel: 'lds' or 'direct' (``scf_patch_train_route``, the kernel's own
+    formula; a host call)."""
+    r = int(_lib.load().scf_patch_train_route(int(ph), int(pw), int(new_h), int(new_w), int(k)))
+    _lib.check(min(r, 0), 'scf_patch_train_route')
+    return ('lds', 'direct')[r]
+
+
+def patch_boxes_train(mesh, labels: Optional[Tensor], rot: Optional[Tensor], trans: Optional[Tensor], k: Tensor,
+                      frame_size: Tuple[int, int], params: '_lib.PatchParams', aug: '_lib.PatchAugParams', *,
+                      id_base: int = 0, sample_ids: Optional[Tensor] = None, crop_rects: Optional[Tensor] = None) -> dict:
+    """``patch_boxes`` with the size ratio drawn per object from ``aug.size_range``, plus the colour draws
+    (``scf_patch_boxes_train``).  -> what ``patch_boxes`` returns, with ``records`` the train workspace
+    ``extract_patches_train`` reads (its head is what ``extract_patches`` reads: ``records[:64 * N]``) and ``draws``
+    (N,8) float64 = (size_ratio, h gain, s gain, v gain, sigma, k, hsv on, noise on).  No host synchronisation."""
+    n = k.shape[0] if isinstance(k, torch.Tensor) and k.dim() == 3 else -1
+    if n <= 0:
+        raise _lib.ScflowHipError('patch_boxes_train: k must be (N,3,3) with N > 0')
+    hf, wf = int(frame_size[0]), int(frame_size[1])
+    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
+        raise _lib.ScflowHipError(f'patch_boxes_train: frame size {(hf, wf)} outside 1..16384')
+    kp = _mats(k, n, (3, 3), 'k')
+    dev = k.device
+    store, lab, rp, tp, cin = None, None, None, None, None
+    if crop_rects is not None:
+        cin = _int_vec(crop_rects, (n, 4), dev, 'patch_boxes_train: crop_rects')
+    else:
+        if mesh is None or labels is None or rot is None or trans is None:
+            raise _lib.ScflowHipError('patch_boxes_train: mesh, labels, rot and trans are needed without crop_rects')
+        lab = _int_vec(labels, (n,), dev, 'patch_boxes_train: labels')
+        rp, tp = _mats(rot, n, (3, 3), 'rot'), _mats(trans, n, (3,), 'trans')
+        store = _mesh_store(mesh, dev, 'patch_boxes_train')
+    sid = _sample_ids(sample_ids, n, dev, 'patch_boxes_train')
+    lib = _lib.load()
+    wsb = int(lib.scf_patch_train_workspace_bytes(n))
+    _lib.check(min(wsb, 0), 'scf_patch_train_workspace_bytes')
+    rec = torch.empty((wsb,), dtype=torch.uint8, device=dev)
+    draws = torch.empty((n, 8), dtype=torch.float64, device=dev)
+    box = torch.empty((n, 4), dtype=torch.float32, device=dev)
+    crop = torch.empty((n, 4), dtype=torch.int32, device=dev)
+    scale = torch.empty((n,), dtype=torch.float32, device=dev)
+    tm = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    kout = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
+    valid = torch.empty((n,), dtype=torch.int32, device=dev)
+    _lib.check(lib.scf_patch_boxes_train(
+        None if store is None else C.byref(store), None if lab is None else lab.data_ptr(), rp, tp, kp,
+        None if cin is None else cin.data_ptr(), n, hf, wf, C.byref(params), C.byref(aug),
+        _id_base(id_base, 'patch_boxes_train'), sid, draws.data_ptr(), box.data_ptr(), crop.data_ptr(), scale.data_ptr(),
+        tm.data_ptr(), kout.data_ptr(), valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes_train')
+    return dict(box=box, crop=crop, scale=scale, transform_matrix=tm, k=kout, valid=valid, records=rec, draws=draws)
+
+
+def extract_patches_train(frames: Tensor, frame_index: Tensor, records: Tensor, params: '_lib.PatchParams',
+                          aug: '_lib.PatchAugParams', masks: Optional[Tensor] = None, out: Optional[Tensor] = None,
+                          mask_out: Optional[Tensor] = None):
+    """crop, augment (RandomHSV, RandomNoise, RandomSmooth), resize, pad and normalise every object's patch, and crop,
+    resize (nearest) and pad its mask (``scf_patch_extract_train``).  frames (F,Hf,Wf,3) uint8 GPU tensor (BGR),
+    frame_index (N,) int GPU tensor, ``records`` from ``patch_boxes_train``, masks (N,Hf,Wf) uint8 or bool (nonzero =
+    object) or None.  -> (img (N,3,out_h,out_w) float32, mask (N,out_h,out_w) bool or None).  No host synchronisation."""
+    if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4
+            or frames.shape[3] != 3 or frames.shape[0] < 1):
+        raise _lib.ScflowHipError('extract_patches_train: frames must be a (F,Hf,Wf,3) uint8 tensor on the GPU '
+                                  '(HIP path only, no CPU fallback)')
+    if frames.device.index != _cur_dev():
+        raise _lib.ScflowHipError(f'extract_patches_train: frames live on cuda:{frames.device.index} but the current '
+                                  f'device is cuda:{_cur_dev()}: wrap the call in torch.cuda.device(tensor.device)')
+    if not frames.is_contiguous():
+        raise _lib.ScflowHipError('extract_patches_train: expected contiguous frames')
+    f, hf, wf = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
+        raise _lib.ScflowHipError(f'extract_patches_train: frame size {(hf, wf)} outside 1..16384')
+    dev = frames.device
+    if not isinstance(frame_index, torch.Tensor) or frame_index.dim() != 1 or frame_index.shape[0] < 1:
+        raise _lib.ScflowHipError('extract_patches_train: frame_index must be (N,) with N > 0')
+    n = int(frame_index.shape[0])
+    fidx = _int_vec(frame_index, (n,), dev, 'extract_patches_train: frame_index')
+    lib = _lib.load()
+    if (not isinstance(records, torch.Tensor) or records.device != dev or records.dtype != torch.uint8
+            or not records.is_contiguous() or records.numel() != int(lib.scf_patch_train_workspace_bytes(n))):
+        raise _lib.ScflowHipError('extract_patches_train: records must be the workspace patch_boxes_train returned for '
+                                  'the same N')
+    shape = (n, 3, int(params.out_h), int(params.out_w))
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=dev)
+    elif tuple(out.shape) != shape or out.device != dev:
+        raise _lib.ScflowHipError(f'extract_patches_train: out must be {shape} on {dev}')
+    mp = None
+    if masks is not None:
+        if (not isinstance(masks, torch.Tensor) or masks.device != dev or masks.dtype not in (torch.uint8, torch.bool)
+                or tuple(masks.shape) != (n, hf, wf) or not masks.is_contiguous()):
+            raise _lib.ScflowHipError(f'extract_patches_train: masks must be a contiguous uint8 / bool tensor of shape '
+                                      f'{(n, hf, wf)} on {dev}')
+        mshape = (n, shape[2], shape[3])
+        if mask_out is None:
+            mask_out = torch.empty(mshape, dtype=torch.bool, device=dev)
+        elif (tuple(mask_out.shape) != mshape or mask_out.device != dev or mask_out.dtype != torch.bool
+              or not mask_out.is_contiguous()):
+            raise _lib.ScflowHipError(f'extract_patches_train: mask_out must be a contiguous bool tensor {mshape} on {dev}')
+        mp = masks.data_ptr()
+    elif mask_out is not None:
+        raise _lib.ScflowHipError('extract_patches_train: mask_out without masks')
+    _lib.check(lib.scf_patch_extract_train(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), mp, n, records.data_ptr(),
+                                           C.byref(params), C.byref(aug), _dense(out, 'out'),
+                                           None if mask_out is None else mask_out.data_ptr(), _stream()),
+               'scf_patch_extract_train')
+    return out, mask_out
+
+
 def unproject_depth(depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor) -> Tensor:
     n, h, w = depth.shape
     out = torch.empty((n, 3, h, w), dtype=torch.float32, device=depth.device)
