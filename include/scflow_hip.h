@@ -723,7 +723,7 @@ int scf_cal_epe(const float* flow_tgt, const float* flow_pred, const float* mask
                 scf_stream_t stream);
 
 /* Forward values of the supervised losses (models/loss/sequence_loss.py, point_matching_loss.py) for all T iterations
- * of a prediction sequence.  No gradients.  Every sequence is a HOST array of T device pointers, T <= 256 (32 travel
+ * of a prediction sequence; the *_grad entries further down add the gradients.  Every sequence is a HOST array of T device pointers, T <= 256 (32 travel
  * per launch; longer sequences take several launches inside the call).  Sums are accumulated in fp64 in a fixed
  * order and rounded to fp32 once; there are no atomics, so results are bitwise reproducible.
  *
@@ -780,6 +780,55 @@ int scf_point_matching_loss(const float* verts, const int32_t* offsets, int num_
                             int loss_type, int flags, float scale_depth_factor, int reduction, float loss_weight,
                             double gamma, float* loss_i, float* per_iter, float* total, int32_t* nn_idx,
                             void* workspace, scf_stream_t stream);
+
+/* Value AND gradient of the supervised losses: each entry takes the arguments of the forward entry above it is named
+ * after and returns the same values bit for bit (same pixel-to-thread mapping, same reduction tree), plus the derivative
+ * of  sum_row upstream[row] * total[row]  with respect to every prediction, from the same pass over the predictions and
+ * the same neighbour search.  The gamma weight w_i = (float)(gamma^(T-1-i)) of iteration i is therefore included.
+ * upstream: DEVICE pointer to fp32 scalars (3 for the pixel entry, one per row; 1 for point matching), NULL = 1, so
+ * that a 0-dim grad_output is passed on without a host sync.  No gradient goes to ground truths, meshes or scales.
+ *
+ * scf_seq_pixel_loss_grad: grad_a, grad_b (N,2,H,W each) and grad_mask (N,H,W each) are HOST arrays of T device
+ * pointers; any of them may be NULL (that sequence gets no gradient).
+ *   flow  g = c_i * v * sgn(p - q),  c_i = ((upstream * w_i) * loss_weight) / ((float)count(v) + eps) in fp32, v the
+ *         forward's own decision;  mask  g = ((upstream * w_i) * loss_weight) / (float)(N*H*W) * sgn(m - occ); valid is
+ *         ignored by the mask gradient as by its value.
+ *   sgn compares its two operands: 0 when equal, +-1 for +-inf, NaN when either is NaN -- also where v = 0 (0 * NaN).
+ *   count(v) = 0: every flow gradient is 0 for eps > 0 and NaN (0 * inf) for eps = 0.
+ * count(v) comes from a pre-pass over gt_flow / valid; the predictions are read once and the gradients written once.
+ * Loads take the quad route by the alignment rule of the forward entry; the stores take it when, in addition, every
+ * gradient plane is 16-byte aligned.  Either way the bits are the same.
+ * workspace: scf_seq_pixel_loss_grad_workspace_bytes(N, H, W, T) bytes of device memory. */
+int64_t scf_seq_pixel_loss_grad_workspace_bytes(int N, int H, int W, int T);
+int scf_seq_pixel_loss_grad(const float* gt_flow, const float* valid, const float* mask_gt, const float* const* flow_a,
+                            const float* const* flow_b, const float* const* mask_seq, int T, int N, int H, int W,
+                            float max_flow, const float* loss_weight, const float* eps, const double* gamma,
+                            const float* upstream, float* const* grad_a, float* const* grad_b, float* const* grad_mask,
+                            float* per_iter, float* totals, void* workspace, scf_stream_t stream);
+
+/* scf_point_matching_loss_grad: grad_r (T pointers to (N,3,3)) and grad_t (T pointers to (N,3); NULL for SCF_PM_ROT)
+ * are HOST arrays of device pointers; either may be NULL.  With d_p = pred_point[idx_p] - target_p in the bits the
+ * forward normed, u_p = d_p / |d_p| (0 where |d_p| = 0) for L2 and sgn(d_p) per component for L1, the neighbour index a
+ * constant, and k = upstream * w_i * loss_weight / (V * diameter[label]) [/ N for SCF_PM_REDUCE_MEAN]:
+ *   FULL         grad_R = k sum_p u_p (x) verts[idx_p]  (the model point of the NEIGHBOUR),  grad_t' = k sum_p u_p
+ *   DISENTANGLE  grad_R from the rotation term; grad_t' from the translation term, or with SCF_PM_DISENTANGLE_Z its z
+ *                from the depth term and its xy from the xy term (structurally zero components are exact zeros)
+ *   ROT          grad_R only
+ *   grad_t.xy = s * grad_t'.xy under SCF_PM_SCALE_XY;  grad_t.z = s * factor * grad_t'.z under SCF_PM_SCALE_DEPTH, else
+ *   factor * grad_t'.z.
+ * u and its product with the coordinate are fp32; the 9 + 3 sums go through the fixed-order fp64 reduction of the
+ * values and are scaled by k in fp64 and rounded once.  A group or label out of range gives NaN gradients for that
+ * sample and reads nothing; an empty point set gives NaN as it does for the value.
+ * workspace: scf_point_matching_grad_workspace_bytes(N, T, max_points) bytes of device memory. */
+int64_t scf_point_matching_grad_workspace_bytes(int N, int T, int max_points);
+int scf_point_matching_loss_grad(const float* verts, const int32_t* offsets, int num_groups, const int32_t* group,
+                                 const int32_t* labels, int num_classes, const int32_t* symmetric, const float* diameter,
+                                 const float* const* pred_r, const float* const* pred_t, int T, const float* gt_r,
+                                 const float* gt_t, const float* scale_factors, int N, int max_points, int mode,
+                                 int loss_type, int flags, float scale_depth_factor, int reduction, float loss_weight,
+                                 double gamma, const float* upstream, float* const* grad_r, float* const* grad_t,
+                                 float* loss_i, float* per_iter, float* total, int32_t* nn_idx, void* workspace,
+                                 scf_stream_t stream);
 
 /* object-frame points of every pixel (dense cal_3d_2d_corr): pts (N,3,H,W), 0 where
  * depth <= 0.  Test/diagnostic entry; scf_reproject_flow recomputes them on the fly. */

@@ -200,6 +200,16 @@ SIGNATURES = {
     'scf_point_matching_loss': (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.POINTER(_fp), C.POINTER(_fp),
                                           C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float,
                                           C.c_int, C.c_float, C.c_double, _fp, _fp, _fp, _fp, _fp, _fp]),
+    'scf_seq_pixel_loss_grad_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_seq_pixel_loss_grad': (C.c_int, [_fp, _fp, _fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int,
+                                          C.c_int, C.c_int, C.c_float, C.POINTER(C.c_float), C.POINTER(C.c_float),
+                                          C.POINTER(C.c_double), _fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), _fp,
+                                          _fp, _fp, _fp]),
+    'scf_point_matching_grad_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'scf_point_matching_loss_grad': (C.c_int, [_fp, _fp, C.c_int, _fp, _fp, C.c_int, _fp, _fp, C.POINTER(_fp),
+                                               C.POINTER(_fp), C.c_int, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_float, C.c_int, C.c_float, C.c_double, _fp, C.POINTER(_fp),
+                                               C.POINTER(_fp), _fp, _fp, _fp, _fp, _fp, _fp]),
     'scf_timer_create': (C.c_int, [C.POINTER(_fp)]),
     'scf_timer_destroy': (C.c_int, [_fp]),
     'scf_timer_arm': (C.c_int, [_fp]),

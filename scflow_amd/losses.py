@@ -1,9 +1,22 @@
-"""Forward values of the supervised losses (reference models/loss/): the ``LOSSES`` registry, ``build_loss`` and
+"""Values and gradients of the supervised losses (reference models/loss/): the ``LOSSES`` registry, ``build_loss`` and
 ``RAFTLoss``, ``L1Loss``, ``SequenceLoss``, ``PointMatchingLoss``, ``DisentanglePointMatchingLoss``,
 ``RotPointMatchingLoss`` with the reference's constructor keys and call signatures, on the HIP kernels of loss.hip.
 
-**No autograd.**  Every class returns the VALUE the reference trains against and logs -- a 0-dim GPU tensor without a
-graph behind it; nothing here can be back-propagated, and ``forward(return_loss=True)`` of the refiners keeps raising.
+**Values and gradients.**  Called on predictions that do not require a gradient, every class returns the VALUE the
+reference trains against and logs -- a 0-dim GPU tensor without a graph behind it, from the forward-only launches.
+The derivative of the gamma-weighted total with respect to every prediction comes from the ``*_grad`` entries of loss.hip
+(``seq_pixel_loss_grad``, ``point_matching_loss_grad``), which return the same values bit for bit and the gradients from
+the same pass, in two ways:
+
+* ``SequenceLoss.value_and_grad(*preds, **kwargs)`` -> ``(total, [loss_i], grads)``, ``grads`` a tuple of lists that
+  mirrors ``preds``; no autograd involved;
+* autograd: when grad mode is on and a prediction requires a gradient, the returned total carries a graph (one
+  ``torch.autograd.Function``; the gradients are computed with the values and scaled by ``grad_output`` in
+  ``backward``), so ``total.backward()`` leaves the same gradients in ``.grad``.  DEVIATION from the reference: the
+  per-iteration list ``[loss_i]`` stays detached -- only the total can be back-propagated.
+
+No gradient goes to ground truths, meshes or scale factors, and the network behind the predictions has no backward:
+``forward(return_loss=True)`` of the refiners keeps raising (see ``loss_and_grads``).
 CPU tensors are refused (``ScflowHipError``), like everywhere else in this package.
 
 ``SequenceLoss`` over one of the classes above evaluates ALL iterations in one launch (``scf_seq_pixel_loss`` /
@@ -36,7 +49,8 @@ from . import _lib, ops
 from .registry import Registry, build_from_cfg
 
 __all__ = ['LOSSES', 'build_loss', 'RAFTLoss', 'L1Loss', 'SequenceLoss', 'PointMatchingLoss',
-           'DisentanglePointMatchingLoss', 'RotPointMatchingLoss', 'seq_pixel_loss', 'point_matching_loss', 'to_host']
+           'DisentanglePointMatchingLoss', 'RotPointMatchingLoss', 'seq_pixel_loss', 'point_matching_loss', 'seq_pixel_loss_grad',
+           'point_matching_loss_grad', 'to_host']
 
 Tensor = torch.Tensor
 LOSSES = Registry('loss')
@@ -76,13 +90,36 @@ def _seq(tensors, shape, name) -> Optional[List[Tensor]]:
     return out
 
 
-def seq_pixel_loss(gt_flow: Optional[Tensor], valid: Optional[Tensor] = None, flow_a=None, flow_b=None, masks=None,
-                   mask_gt: Optional[Tensor] = None, max_flow: float = 400., loss_weight=(1., 1., 1.),
-                   eps=(1e-10, 1e-10, 1e-10), gamma=(0.8, 0.8, 0.8)):
-    """``scf_seq_pixel_loss``: SequenceLoss(RAFTLoss) of up to two flow sequences and SequenceLoss(L1Loss) of one mask
-    sequence against the same ground truth, one pass -> (per_iter (3,T), totals (3)); rows flow_a, flow_b, masks, zeros
-    where a sequence is absent.  Without ``mask_gt`` the mask target is ``(gt_x + gt_y < max_flow)`` -- the SUM of the two
-    channels, not the magnitude, as scflow_refiner.py:230 has it."""
+def _upstream(upstream, count, device):
+    """a device pointer to ``count`` fp32 scalars (or None = 1) and the tensor that keeps it alive."""
+    if upstream is None:
+        return None, None
+    if not isinstance(upstream, torch.Tensor) or not upstream.is_cuda:
+        raise _lib.ScflowHipError('upstream: expected a tensor on the GPU (it is read by the kernel, never by the host)')
+    up = upstream.detach().to(torch.float32).reshape(-1).contiguous()
+    if up.numel() != count:
+        raise _lib.ScflowHipError(f'upstream: expected {count} scalar(s), got {up.numel()}')
+    return up.data_ptr(), up
+
+
+def _grad_planes(out, like, want, name):
+    """the gradient tensors of one sequence: ``out`` (caller's, dense fp32 GPU tensors with the elements of the
+    predictions) or one fresh allocation; None when the sequence is absent or not wanted."""
+    if like is None or not want:
+        return None
+    if out is None:
+        return list(torch.empty((len(like),) + tuple(like[0].shape), dtype=torch.float32, device=like[0].device).unbind(0))
+    if len(out) != len(like):
+        raise ValueError(f'{name}: {len(out)} gradient tensors for {len(like)} predictions')
+    for i, g in enumerate(out):
+        ops._dev(g, f'{name}[{i}]')
+        if g.numel() != like[i].numel() or not g.is_contiguous():
+            raise _lib.ScflowHipError(f'{name}[{i}]: expected a contiguous tensor of {like[i].numel()} elements')
+    return list(out)
+
+
+def _seq_pixel(gt_flow, valid, flow_a, flow_b, masks, mask_gt, max_flow, loss_weight, eps, gamma, grad=False,
+               upstream=None, want=(True, True, True), grad_out=(None, None, None)):
     seqs = [s for s in (flow_a, flow_b, masks) if s is not None]
     if not seqs:
         raise ValueError('seq_pixel_loss: no sequence given')
@@ -103,6 +140,7 @@ def seq_pixel_loss(gt_flow: Optional[Tensor], valid: Optional[Tensor] = None, fl
         if flow_a is not None or flow_b is not None or mask_gt is None:
             raise ValueError('seq_pixel_loss: gt_flow is needed unless only masks against mask_gt are given')
         n, h, w = mask_gt.shape
+    mask_shapes = None if masks is None else [tuple(m.shape) for m in masks]
     flow_a = _seq(flow_a, (n, 2, h, w), 'flow_a')
     flow_b = _seq(flow_b, (n, 2, h, w), 'flow_b')
     masks = _seq(masks, (n, h, w), 'masks')
@@ -121,21 +159,100 @@ def seq_pixel_loss(gt_flow: Optional[Tensor], valid: Optional[Tensor] = None, fl
     pv, pm = plane(valid, 'valid'), plane(mask_gt, 'mask_gt')
     lib = _lib.load()
     dev = first.device
-    ws = torch.empty((int(lib.scf_seq_pixel_loss_workspace_bytes(n, h, w, T)),), dtype=torch.uint8, device=dev)
     per_iter = torch.empty((3, T), dtype=torch.float32, device=dev)
     totals = torch.empty((3,), dtype=torch.float32, device=dev)
     f3 = lambda v: (C.c_float * 3)(*[float(x) for x in v])
-    _lib.check(lib.scf_seq_pixel_loss(None if gt_flow is None else gt_flow.data_ptr(), pv, pm, _ptr_array(flow_a),
-                                      _ptr_array(flow_b), _ptr_array(masks), T, n, h, w, float(max_flow), f3(loss_weight),
-                                      f3(eps), (C.c_double * 3)(*[float(g) for g in gamma]), per_iter.data_ptr(),
-                                      totals.data_ptr(), ws.data_ptr(), ops._stream()), 'scf_seq_pixel_loss')
-    return per_iter, totals
+    head = (None if gt_flow is None else gt_flow.data_ptr(), pv, pm, _ptr_array(flow_a), _ptr_array(flow_b),
+            _ptr_array(masks), T, n, h, w, float(max_flow), f3(loss_weight), f3(eps),
+            (C.c_double * 3)(*[float(g) for g in gamma]))
+    if not grad:
+        ws = torch.empty((int(lib.scf_seq_pixel_loss_workspace_bytes(n, h, w, T)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.scf_seq_pixel_loss(*head, per_iter.data_ptr(), totals.data_ptr(), ws.data_ptr(), ops._stream()),
+                   'scf_seq_pixel_loss')
+        return per_iter, totals
+    ws = torch.empty((int(lib.scf_seq_pixel_loss_grad_workspace_bytes(n, h, w, T)),), dtype=torch.uint8, device=dev)
+    up_ptr, up_keep = _upstream(upstream, 3, dev)
+    grads = [_grad_planes(o, s, wnt, name) for o, s, wnt, name in
+             zip(grad_out, (flow_a, flow_b, masks), want, ('grad_a', 'grad_b', 'grad_mask'))]
+    _lib.check(lib.scf_seq_pixel_loss_grad(*head, up_ptr, _ptr_array(grads[0]), _ptr_array(grads[1]), _ptr_array(grads[2]),
+                                           per_iter.data_ptr(), totals.data_ptr(), ws.data_ptr(), ops._stream()),
+               'scf_seq_pixel_loss_grad')
+    del up_keep
+    if grads[2] is not None and grad_out[2] is None:
+        grads[2] = [g.view(shape) for g, shape in zip(grads[2], mask_shapes)]       # (N,1,H,W) predictions get their shape
+    return per_iter, totals, tuple(grads)
+
+
+def seq_pixel_loss(gt_flow: Optional[Tensor], valid: Optional[Tensor] = None, flow_a=None, flow_b=None, masks=None,
+                   mask_gt: Optional[Tensor] = None, max_flow: float = 400., loss_weight=(1., 1., 1.),
+                   eps=(1e-10, 1e-10, 1e-10), gamma=(0.8, 0.8, 0.8)):
+    """``scf_seq_pixel_loss``: SequenceLoss(RAFTLoss) of up to two flow sequences and SequenceLoss(L1Loss) of one mask
+    sequence against the same ground truth, one pass -> (per_iter (3,T), totals (3)); rows flow_a, flow_b, masks, zeros
+    where a sequence is absent.  Without ``mask_gt`` the mask target is ``(gt_x + gt_y < max_flow)`` -- the SUM of the two
+    channels, not the magnitude, as scflow_refiner.py:230 has it."""
+    return _seq_pixel(gt_flow, valid, flow_a, flow_b, masks, mask_gt, max_flow, loss_weight, eps, gamma)
+
+
+def seq_pixel_loss_grad(gt_flow: Optional[Tensor], valid: Optional[Tensor] = None, flow_a=None, flow_b=None, masks=None,
+                        mask_gt: Optional[Tensor] = None, max_flow: float = 400., loss_weight=(1., 1., 1.),
+                        eps=(1e-10, 1e-10, 1e-10), gamma=(0.8, 0.8, 0.8), upstream: Optional[Tensor] = None,
+                        want=(True, True, True), grad_out=(None, None, None)):
+    """``scf_seq_pixel_loss_grad``: the values of ``seq_pixel_loss`` (the same bits) and, from the same pass, the
+    derivative of ``sum_row upstream[row] * totals[row]`` -> (per_iter, totals, grads); ``grads`` = (grad_a, grad_b,
+    grad_mask), each a list of T tensors shaped like the predictions, or None where the sequence is absent or its entry of
+    ``want`` is false.  ``upstream``: a GPU tensor of 3 scalars (read on the device; None = 1).  ``grad_out``: tensors to
+    write into instead of fresh ones."""
+    return _seq_pixel(gt_flow, valid, flow_a, flow_b, masks, mask_gt, max_flow, loss_weight, eps, gamma, True, upstream,
+                      want, grad_out)
+
+
+class _TotalWithGrad(torch.autograd.Function):
+    """the one autograd node of this module: ``run(tensors)`` -> (total, gradients aligned with ``tensors``, None where
+    there is none) computes both in one launch; ``backward`` scales the kept gradients by ``grad_output`` on the device."""
+
+    @staticmethod
+    def forward(ctx, run, *tensors):
+        total, grads = run(tensors)
+        ctx.present = [g is not None for g in grads]
+        ctx.save_for_backward(*[g for g in grads if g is not None])
+        return total.clone()
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        kept = iter(ctx.saved_tensors)
+        return (None,) + tuple(next(kept) * grad_output if p else None for p in ctx.present)
+
+
+def _wants_graph(*seqs) -> bool:
+    return torch.is_grad_enabled() and any(isinstance(t, torch.Tensor) and t.requires_grad
+                                           for s in seqs if s is not None for t in s)
+
+
+def _through_autograd(seqs, run_grad):
+    """seqs: lists of predictions (None allowed); run_grad(detached seqs, want per sequence) -> (total, extras, grads per
+    sequence).  -> (total with a graph, extras)."""
+    lens = [0 if s is None else len(s) for s in seqs]
+    want = tuple(s is not None and any(t.requires_grad for t in s) for s in seqs)
+    box = {}
+
+    def run(flat):
+        flat, det = list(flat), []
+        for n, s in zip(lens, seqs):
+            det.append(None if s is None else [t.detach() for t in flat[:n]])
+            flat = flat[n:]
+        total, box['extras'], grads = run_grad(det, want)
+        out = []
+        for n, g in zip(lens, grads):
+            out += [None] * n if g is None else list(g)
+        return total, out
+    total = _TotalWithGrad.apply(run, *[t for s in seqs if s is not None for t in s])
+    return total, box['extras']
 
 
 @LOSSES.register_module()
 class RAFTLoss:
     """sequence_loss.py:8-24: ``loss_weight * sum(valid * |pred - gt|) / (count(valid) + eps)`` with
-    ``valid = (valid >= 0.5) & (|gt| < max_flow)``.  Forward value only."""
+    ``valid = (valid >= 0.5) & (|gt| < max_flow)``."""
 
     def __init__(self, loss_weight=1.0, max_flow=400, eps=1e-10):
         self.loss_weight, self.max_flow, self.eps = loss_weight, max_flow, eps
@@ -144,13 +261,26 @@ class RAFTLoss:
         return self
 
     def sequence(self, preds, gt_flow, valid=None, gamma=0.8):
+        if _wants_graph(preds):
+            return _through_autograd([list(preds)], lambda det, want: self._with_grad(det[0], gt_flow, valid, gamma))
         per_iter, totals = seq_pixel_loss(gt_flow, valid, flow_a=preds, max_flow=self.max_flow,
                                           loss_weight=(self.loss_weight, 1., 1.), eps=(self.eps, 0., 0.),
                                           gamma=(gamma, 1., 1.))
         return totals[0], per_iter[0]
 
+    def _with_grad(self, preds, gt_flow, valid, gamma):
+        per_iter, totals, grads = seq_pixel_loss_grad(gt_flow, valid, flow_a=preds, max_flow=self.max_flow,
+                                                      loss_weight=(self.loss_weight, 1., 1.), eps=(self.eps, 0., 0.),
+                                                      gamma=(gamma, 1., 1.))
+        return totals[0], per_iter[0], (grads[0],)
+
+    def sequence_grad(self, preds, gt_flow, valid=None, gamma=0.8):
+        """-> (total, per_iter (T), (gradients of total w.r.t. ``preds``,)); no graph."""
+        return self._with_grad(preds, gt_flow, valid, gamma)
+
     def forward(self, pred_flow, gt_flow, valid=None):
-        return self.sequence([pred_flow], gt_flow, valid)[1][0]
+        total, per_iter = self.sequence([pred_flow], gt_flow, valid)
+        return total if total.requires_grad else per_iter[0]          # one iteration: the total IS the value (weight 1)
 
     __call__ = forward
 
@@ -158,7 +288,7 @@ class RAFTLoss:
 @LOSSES.register_module()
 class L1Loss:
     """sequence_loss.py:28-37: ``mean(|pred_mask - gt_mask|) * loss_weight``; ``valid`` and ``eps`` are accepted and
-    ignored, as in the reference.  Forward value only."""
+    ignored, as in the reference."""
 
     def __init__(self, loss_weight=1.0, eps=1e-10):
         self.loss_weight, self.eps = loss_weight, eps
@@ -167,24 +297,32 @@ class L1Loss:
         return self
 
     def sequence(self, preds, gt_mask, valid=None, gamma=0.8):
+        if _wants_graph(preds):
+            return _through_autograd([list(preds)], lambda det, want: self._with_grad(det[0], gt_mask, gamma))
         per_iter, totals = seq_pixel_loss(None, None, masks=preds, mask_gt=gt_mask,
                                           loss_weight=(1., 1., self.loss_weight), gamma=(1., 1., gamma))
         return totals[2], per_iter[2]
 
+    def _with_grad(self, preds, gt_mask, gamma):
+        per_iter, totals, grads = seq_pixel_loss_grad(None, None, masks=preds, mask_gt=gt_mask,
+                                                      loss_weight=(1., 1., self.loss_weight), gamma=(1., 1., gamma))
+        return totals[2], per_iter[2], (grads[2],)
+
+    def sequence_grad(self, preds, gt_mask, valid=None, gamma=0.8):
+        """-> (total, per_iter (T), (gradients of total w.r.t. ``preds``,)); no graph."""
+        return self._with_grad(preds, gt_mask, gamma)
+
     def forward(self, pred_mask, gt_mask, valid=None):
-        return self.sequence([pred_mask], gt_mask, valid)[1][0]
+        total, per_iter = self.sequence([pred_mask], gt_mask, valid)
+        return total if total.requires_grad else per_iter[0]
 
     __call__ = forward
 
 
 # ------------------------------------------------------------------------------------------------- point matching
-def point_matching_loss(verts: Tensor, offsets: Tensor, group: Tensor, labels: Tensor, symmetric: Tensor,
-                        diameter: Tensor, seq_r, seq_t, gt_r: Tensor, gt_t: Optional[Tensor],
-                        scale_factors: Optional[Tensor], max_points: int, mode: int, loss_type: int, flags: int = 0,
-                        scale_depth_factor: float = 1., reduction: str = 'mean', loss_weight: float = 1.,
-                        gamma: float = 0.8, return_nn: bool = False):
-    """``scf_point_matching_loss`` -> (loss_i (T,N), per_iter (T), total (1), nn_idx (T,N,max_points) int32 or None;
-    -1 past a sample's point count).  See include/scflow_hip.h for the arguments."""
+def _point_matching(verts, offsets, group, labels, symmetric, diameter, seq_r, seq_t, gt_r, gt_t, scale_factors,
+                    max_points, mode, loss_type, flags, scale_depth_factor, reduction, loss_weight, gamma, return_nn,
+                    grad=False, upstream=None, want=(True, True)):
     T = len(seq_r)
     if T == 0 or T > MAX_T:
         raise _lib.ScflowHipError(f'point_matching_loss: 1..{MAX_T} iterations, got {T}')
@@ -214,20 +352,53 @@ def point_matching_loss(verts: Tensor, offsets: Tensor, group: Tensor, labels: T
         raise _lib.ScflowHipError('point_matching_loss: verts (total,3), offsets (groups+1), symmetric and diameter (classes)')
     lib = _lib.load()
     dev = gt_r.device
-    ws = torch.empty((int(lib.scf_point_matching_workspace_bytes(n, T, max_points)),), dtype=torch.uint8, device=dev)
     loss_i = torch.empty((T, n), dtype=torch.float32, device=dev)
     per_iter = torch.empty((T,), dtype=torch.float32, device=dev)
     total = torch.empty((1,), dtype=torch.float32, device=dev)
     nn_idx = torch.full((T, n, max(max_points, 1)), -1, dtype=torch.int32, device=dev) if return_nn else None
     P = lambda t: None if t is None else t.data_ptr()
-    _lib.check(lib.scf_point_matching_loss(
-        ops._dense(verts, 'verts'), offsets.data_ptr(), int(offsets.numel()) - 1, group.data_ptr(), labels.data_ptr(),
-        int(symmetric.numel()), symmetric.data_ptr(), ops._dense(diameter, 'diameter'), _ptr_array(seq_r),
-        _ptr_array(seq_t), T, gt_r.data_ptr(), P(gt_t), P(scale_factors), n, int(max_points), int(mode), int(loss_type),
-        int(flags), float(scale_depth_factor), 0 if reduction == 'mean' else 1, float(loss_weight), float(gamma),
-        loss_i.data_ptr(), per_iter.data_ptr(), total.data_ptr(), P(nn_idx), ws.data_ptr(), ops._stream()),
-        'scf_point_matching_loss')
-    return loss_i, per_iter, total, nn_idx
+    head = (ops._dense(verts, 'verts'), offsets.data_ptr(), int(offsets.numel()) - 1, group.data_ptr(), labels.data_ptr(),
+            int(symmetric.numel()), symmetric.data_ptr(), ops._dense(diameter, 'diameter'), _ptr_array(seq_r),
+            _ptr_array(seq_t), T, gt_r.data_ptr(), P(gt_t), P(scale_factors), n, int(max_points), int(mode), int(loss_type),
+            int(flags), float(scale_depth_factor), 0 if reduction == 'mean' else 1, float(loss_weight), float(gamma))
+    tail = (loss_i.data_ptr(), per_iter.data_ptr(), total.data_ptr(), P(nn_idx))
+    if not grad:
+        ws = torch.empty((int(lib.scf_point_matching_workspace_bytes(n, T, max_points)),), dtype=torch.uint8, device=dev)
+        _lib.check(lib.scf_point_matching_loss(*head, *tail, ws.data_ptr(), ops._stream()), 'scf_point_matching_loss')
+        return loss_i, per_iter, total, nn_idx
+    ws = torch.empty((int(lib.scf_point_matching_grad_workspace_bytes(n, T, max_points)),), dtype=torch.uint8, device=dev)
+    up_ptr, up_keep = _upstream(upstream, 1, dev)
+    grad_r = _grad_planes(None, seq_r, want[0], 'grad_r')
+    grad_t = _grad_planes(None, seq_t, want[1], 'grad_t')
+    _lib.check(lib.scf_point_matching_loss_grad(*head, up_ptr, _ptr_array(grad_r), _ptr_array(grad_t), *tail, ws.data_ptr(),
+                                                ops._stream()), 'scf_point_matching_loss_grad')
+    del up_keep
+    return loss_i, per_iter, total, nn_idx, grad_r, grad_t
+
+
+def point_matching_loss(verts: Tensor, offsets: Tensor, group: Tensor, labels: Tensor, symmetric: Tensor,
+                        diameter: Tensor, seq_r, seq_t, gt_r: Tensor, gt_t: Optional[Tensor],
+                        scale_factors: Optional[Tensor], max_points: int, mode: int, loss_type: int, flags: int = 0,
+                        scale_depth_factor: float = 1., reduction: str = 'mean', loss_weight: float = 1.,
+                        gamma: float = 0.8, return_nn: bool = False):
+    """``scf_point_matching_loss`` -> (loss_i (T,N), per_iter (T), total (1), nn_idx (T,N,max_points) int32 or None;
+    -1 past a sample's point count).  See include/scflow_hip.h for the arguments."""
+    return _point_matching(verts, offsets, group, labels, symmetric, diameter, seq_r, seq_t, gt_r, gt_t, scale_factors,
+                           max_points, mode, loss_type, flags, scale_depth_factor, reduction, loss_weight, gamma, return_nn)
+
+
+def point_matching_loss_grad(verts: Tensor, offsets: Tensor, group: Tensor, labels: Tensor, symmetric: Tensor,
+                             diameter: Tensor, seq_r, seq_t, gt_r: Tensor, gt_t: Optional[Tensor],
+                             scale_factors: Optional[Tensor], max_points: int, mode: int, loss_type: int, flags: int = 0,
+                             scale_depth_factor: float = 1., reduction: str = 'mean', loss_weight: float = 1.,
+                             gamma: float = 0.8, return_nn: bool = False, upstream: Optional[Tensor] = None,
+                             want=(True, True)):
+    """``scf_point_matching_loss_grad``: the values of ``point_matching_loss`` (the same bits) and the derivative of
+    ``upstream * total`` from the same neighbour search -> (loss_i, per_iter, total, nn_idx, grad_r, grad_t): lists of T
+    (N,3,3) / (N,3) tensors; ``grad_t`` is None for ``PM_ROT``.  ``upstream``: one scalar on the GPU (None = 1)."""
+    return _point_matching(verts, offsets, group, labels, symmetric, diameter, seq_r, seq_t, gt_r, gt_t, scale_factors,
+                           max_points, mode, loss_type, flags, scale_depth_factor, reduction, loss_weight, gamma, return_nn,
+                           True, upstream, want)
 
 
 class _PointMatchingBase:
@@ -303,7 +474,24 @@ class _PointMatchingBase:
 
     def sequence(self, seq_r, seq_t, gt_r, gt_t, labels, points_list=None, scale_factors=None, gamma=0.8,
                  return_nn=False):
-        """all iterations in one launch -> (total (0-dim), per_iter (T), loss_i (T,N), nn_idx or None)."""
+        """all iterations in one launch -> (total (0-dim), per_iter (T), loss_i (T,N), nn_idx or None).  The total
+        carries a graph when grad mode is on and a prediction requires a gradient."""
+        if _wants_graph(seq_r, seq_t):
+            def run_grad(det, want):
+                out = self._run(det[0], det[1], gt_r, gt_t, labels, points_list, scale_factors, gamma, return_nn, True, want)
+                return out[0], out[1:4], (out[4], out[5])
+            total, extras = _through_autograd([list(seq_r), None if seq_t is None else list(seq_t)], run_grad)
+            return (total,) + tuple(extras)
+        return self._run(seq_r, seq_t, gt_r, gt_t, labels, points_list, scale_factors, gamma, return_nn)
+
+    def sequence_grad(self, seq_r, seq_t, gt_r, gt_t, labels, points_list=None, scale_factors=None, gamma=0.8,
+                      return_nn=False):
+        """-> (total, per_iter, loss_i, nn_idx, grad_r, grad_t): ``sequence`` plus the gradients of the total with respect
+        to every rotation and translation (``grad_t`` None for rotations only); no graph."""
+        return self._run(seq_r, seq_t, gt_r, gt_t, labels, points_list, scale_factors, gamma, return_nn, True)
+
+    def _run(self, seq_r, seq_t, gt_r, gt_t, labels, points_list, scale_factors, gamma, return_nn, grad=False,
+             want=(True, True)):
         ops._dev(gt_r, 'gt_r')
         if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
             raise _lib.ScflowHipError('labels: expected a tensor on the GPU (HIP path only, no CPU fallback)')
@@ -330,16 +518,19 @@ class _PointMatchingBase:
         else:
             verts, offsets, sym, diam, max_points = self._class_tables(dev)
             group = lab32
-        loss_i, per_iter, total, nn_idx = point_matching_loss(
-            verts, offsets, group, lab32, sym, diam, seq_r, seq_t, gt_r, gt_t,
-            scale_factors if flags & (PM_SCALE_XY | PM_SCALE_DEPTH) else None, max_points, self._mode, self.loss_type,
-            flags, getattr(self, 'scale_depth_factor', 1.), self.reduction, self.loss_weight, gamma, return_nn)
-        return total[0], per_iter, loss_i, nn_idx
+        args = (verts, offsets, group, lab32, sym, diam, seq_r, seq_t, gt_r, gt_t,
+                scale_factors if flags & (PM_SCALE_XY | PM_SCALE_DEPTH) else None, max_points, self._mode, self.loss_type,
+                flags, getattr(self, 'scale_depth_factor', 1.), self.reduction, self.loss_weight, gamma, return_nn)
+        if not grad:
+            loss_i, per_iter, total, nn_idx = point_matching_loss(*args)
+            return total[0], per_iter, loss_i, nn_idx
+        loss_i, per_iter, total, nn_idx, grad_r, grad_t = point_matching_loss_grad(*args, want=want)
+        return total[0], per_iter, loss_i, nn_idx, grad_r, grad_t
 
 
 @LOSSES.register_module()
 class PointMatchingLoss(_PointMatchingBase):
-    """point_matching_loss.py:14-103.  Forward value only."""
+    """point_matching_loss.py:14-103."""
     _mode = PM_FULL
 
     def __init__(self, symmetry_types, mesh_diameter, scale_xy=False, scale_depth=False, scale_depth_factor=1.,
@@ -352,7 +543,8 @@ class PointMatchingLoss(_PointMatchingBase):
         return (PM_SCALE_XY if self.scale_xy else 0) | (PM_SCALE_DEPTH if self.scale_depth else 0)
 
     def forward(self, pred_r, pred_t, gt_r, gt_t, labels, points_list=None, scale_factors=None):
-        return self.sequence([pred_r], [pred_t], gt_r, gt_t, labels, points_list, scale_factors)[1][0]
+        out = self.sequence([pred_r], [pred_t], gt_r, gt_t, labels, points_list, scale_factors)
+        return out[0] if out[0].requires_grad else out[1][0]           # one iteration: the total IS the value (weight 1)
 
     __call__ = forward
 
@@ -361,7 +553,7 @@ class PointMatchingLoss(_PointMatchingBase):
 class DisentanglePointMatchingLoss(PointMatchingLoss):
     """point_matching_loss.py:106-218 (https://arxiv.org/abs/1905.12365): the rotation term uses the ground-truth
     translation on both sides; the translation term (or, with ``disentangle_z``, the depth and the xy terms) the
-    ground-truth rotation.  Forward value only."""
+    ground-truth rotation."""
     _mode = PM_DISENTANGLE
 
     def __init__(self, symmetry_types, mesh_diameter, scale_xy=False, scale_depth=False, scale_depth_factor=1.,
@@ -377,7 +569,7 @@ class DisentanglePointMatchingLoss(PointMatchingLoss):
 
 @LOSSES.register_module()
 class RotPointMatchingLoss(_PointMatchingBase):
-    """point_matching_loss.py:221-291: rotations only.  Forward value only."""
+    """point_matching_loss.py:221-291: rotations only."""
     _mode = PM_ROT
 
     def __init__(self, symmetry_types, mesh_diameter, use_perspective_shape=False, mesh_path=None, loss_weight=1.0,
@@ -386,7 +578,8 @@ class RotPointMatchingLoss(_PointMatchingBase):
                           loss_type)
 
     def forward(self, pred_r, gt_r, labels, points_list=None):
-        return self.sequence([pred_r], None, gt_r, None, labels, points_list)[1][0]
+        out = self.sequence([pred_r], None, gt_r, None, labels, points_list)
+        return out[0] if out[0].requires_grad else out[1][0]
 
     __call__ = forward
 
@@ -399,7 +592,9 @@ _POINT = (PointMatchingLoss, DisentanglePointMatchingLoss, RotPointMatchingLoss)
 class SequenceLoss:
     """sequence_loss.py:41-82: ``sum_i gamma**(T-1-i) * loss_func(preds[..][i], **kwargs)`` -> (loss, [loss_i]).
     One launch for all iterations when ``loss_func`` is one of this module's classes; the reference's loop for any other
-    class registered in ``LOSSES``.  Forward values only."""
+    class registered in ``LOSSES``.  ``value_and_grad`` adds the gradients of ``loss`` with respect to every prediction
+    (this module's classes only); with predictions that require a gradient, ``loss`` carries a graph and ``[loss_i]``
+    stays detached."""
 
     def __init__(self, loss_func_cfg: dict, gamma: float = 0.8) -> None:
         self.loss_func = build_loss(loss_func_cfg)
@@ -430,3 +625,21 @@ class SequenceLoss:
         return total, values
 
     __call__ = forward
+
+    def value_and_grad(self, *preds, **kwargs):
+        """-> (loss, [loss_i], grads): ``forward`` and d loss / d preds from the same launch; ``grads`` is a tuple of
+        lists that mirrors ``preds``.  No graph is built, whatever the predictions require."""
+        f = self.loss_func
+        if not ((type(f) in _PIXEL or type(f) in _POINT) and len(preds[0])):
+            raise NotImplementedError(f'value_and_grad: no gradient kernel for {type(f).__name__}; it exists for '
+                                      + ', '.join(c.__name__ for c in _PIXEL + _POINT))
+        det = [[t.detach() for t in seq] for seq in preds]
+        if type(f) in _PIXEL:
+            total, per_iter, grads = f.sequence_grad(det[0], *det[1:], gamma=self.gamma, **kwargs)
+            return total, list(per_iter.unbind(0)), grads
+        if f._mode == PM_ROT:
+            out = f.sequence_grad(det[0], None, kwargs['gt_r'], None, kwargs['labels'], kwargs.get('points_list'),
+                                  gamma=self.gamma)
+            return out[0], list(out[1].unbind(0)), (out[4],)
+        out = f.sequence_grad(det[0], det[1], gamma=self.gamma, **kwargs)
+        return out[0], list(out[1].unbind(0)), (out[4], out[5])

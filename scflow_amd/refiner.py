@@ -8,8 +8,9 @@ keys.  PnP re-mapping is outside the hot path, and
 ``forward_single_pass`` consumes an already formatted ``data`` dict (what
 ``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).  The loss
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
-``loss()`` returns the forward VALUES the reference trains against -- no autograd, no
-``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
+``loss()`` returns the forward VALUES the reference trains against and ``loss_and_grads()`` adds their gradients at
+the network's outputs -- the network has no backward and there is no ``train_step``; ``forward(return_loss=True)``
+keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
@@ -99,7 +100,7 @@ class _RenderingRefiner:
         data['rendered_masks'] = mask
         return data
 
-    # ------------------------------------------------------------------ supervised loss values (no autograd)
+    # ------------------------------------------------------------------ supervised loss values and output gradients
     render_augmentations = None
     _loss_cfgs: Dict[str, Optional[dict]] = {}
 
@@ -181,11 +182,12 @@ class _RenderingRefiner:
             gt_flow = filter_flow_by_mask(gt_flow, data['gt_masks'], invalid_num=self.max_flow)
         return gt_flow
 
-    def _pixel_losses(self, gt_flow, valid, flow_funcs, flow_seqs, mask_func, mask_seq):
+    def _pixel_losses(self, gt_flow, valid, flow_funcs, flow_seqs, mask_func, mask_seq, grads=False):
         """SequenceLoss values of up to two flow sequences and the mask sequence.  One fused launch when every loss is a
         ``SequenceLoss`` over ``RAFTLoss`` / ``L1Loss`` with the refiner's ``max_flow``; else one call per loss with the
         occlusion target built as the reference builds it (the SUM of the two channels < max_flow,
-        scflow_refiner.py:230 -- not the magnitude)."""
+        scflow_refiner.py:230 -- not the magnitude).  ``grads``: every (total, [value_i]) becomes (total, [value_i],
+        [gradient_i]) -- the fused value-and-gradient launch under the same condition, ``value_and_grad`` per loss else."""
         from . import losses as L
         fusable = all(type(f) is L.SequenceLoss and type(f.loss_func) is L.RAFTLoss
                       and float(f.loss_func.max_flow) == float(self.max_flow) for f in flow_funcs)
@@ -194,18 +196,26 @@ class _RenderingRefiner:
             fl = list(flow_funcs) + [None] * (2 - len(flow_funcs))
             sq = list(flow_seqs) + [None] * (2 - len(flow_seqs))
             get = lambda f, name, default: default if f is None else getattr(f.loss_func, name)
-            per_iter, totals = L.seq_pixel_loss(
-                gt_flow, valid, flow_a=sq[0], flow_b=sq[1], masks=mask_seq, max_flow=self.max_flow,
-                loss_weight=(get(fl[0], 'loss_weight', 1.), get(fl[1], 'loss_weight', 1.), get(mask_func, 'loss_weight', 1.)),
-                eps=(get(fl[0], 'eps', 0.), get(fl[1], 'eps', 0.), 0.),
-                gamma=tuple(1. if f is None else f.gamma for f in (fl[0], fl[1], mask_func)))
-            out = [(totals[i], list(per_iter[i].unbind(0))) for i in range(len(flow_funcs))]
-            return out, (None if mask_func is None else (totals[2], list(per_iter[2].unbind(0))))
-        out = [f(seq, gt_flow=gt_flow, valid=valid) for f, seq in zip(flow_funcs, flow_seqs)]
+            kw = dict(flow_a=sq[0], flow_b=sq[1], masks=mask_seq, max_flow=self.max_flow,
+                      loss_weight=(get(fl[0], 'loss_weight', 1.), get(fl[1], 'loss_weight', 1.), get(mask_func, 'loss_weight', 1.)),
+                      eps=(get(fl[0], 'eps', 0.), get(fl[1], 'eps', 0.), 0.),
+                      gamma=tuple(1. if f is None else f.gamma for f in (fl[0], fl[1], mask_func)))
+            if grads:
+                per_iter, totals, g = L.seq_pixel_loss_grad(gt_flow, valid, **kw)
+            else:
+                (per_iter, totals), g = L.seq_pixel_loss(gt_flow, valid, **kw), None
+            row = lambda i: (totals[i], list(per_iter[i].unbind(0))) + ((g[i],) if grads else ())
+            return [row(i) for i in range(len(flow_funcs))], (None if mask_func is None else row(2))
+        call = (lambda f, *a, **k: f.value_and_grad(*a, **k)) if grads else (lambda f, *a, **k: f(*a, **k))
+        out = [call(f, seq, gt_flow=gt_flow, valid=valid) for f, seq in zip(flow_funcs, flow_seqs)]
         mask_out = None
         if mask_func is not None:
             occluded_target = (gt_flow[:, 0] + gt_flow[:, 1] < self.max_flow).float()       # channel SUM, not magnitude
-            mask_out = mask_func([m[:, 0] if m.dim() == 4 else m for m in mask_seq], gt_mask=occluded_target, valid=valid)
+            mask_out = call(mask_func, [m[:, 0] if m.dim() == 4 else m for m in mask_seq], gt_mask=occluded_target, valid=valid)
+            if grads:                           # the gradients take the shape of the predictions they belong to
+                mask_out = mask_out[:2] + ([g.view(m.shape) for g, m in zip(mask_out[2][0], mask_seq)],)
+        if grads:
+            out = [o[:2] + (o[2][0],) for o in out]
         return out, mask_out
 
     @staticmethod
@@ -357,6 +367,18 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         has the reference's keys in the reference's order (the ``init_add_*`` pair only when the data carries it) and
         reaches the host in one transfer.  ``data``: an already formatted dict (``format_data_train_sup``'s), the only
         way to call this without an attached renderer; it needs ``gt_masks`` when ``filter_invalid_flow`` is set."""
+        return self._loss(data_batch, data, False)
+
+    def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss()`` plus the training signal at the network's outputs -> (loss, None, log_vars, seq_rotations,
+        seq_translations, grads): ``grads`` maps ``sequence_flow_from_pred``, ``sequence_masks`` and either
+        ``seq_rotations`` / ``seq_translations`` or, when the pose loss is a ``RAFTLoss``, ``sequence_flow_from_pose`` to the
+        list of d loss / d prediction per iteration (``loss = loss_pose + loss_flow + loss_mask``), from the
+        value-and-gradient launches: the values are the bits ``loss()`` returns and ``log_vars`` still costs one
+        transfer.  The network itself has no backward yet."""
+        return self._loss(data_batch, data, True)
+
+    def _loss(self, data_batch, data, with_grads):
         from . import losses as L
         self._build_loss_funcs()
         if data is None:
@@ -370,14 +392,15 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         if pose_is_flow:
             (flow_out, pose_out), mask_out = self._pixel_losses(
                 gt_flow, valid, [self.flow_loss_func, self.pose_loss_func], [flow_from_pred, flow_from_pose],
-                self.mask_loss_func, sequence_masks)
+                self.mask_loss_func, sequence_masks, with_grads)
         else:
-            pose_out = self.pose_loss_func(seq_rotations, seq_translations, gt_r=data['gt_rotations'],
-                                           gt_t=data['gt_translations'], labels=labels,
-                                           scale_factors=self._scale_factors(data, data_batch, gt_flow.device))
+            pose_call = self.pose_loss_func.value_and_grad if with_grads else self.pose_loss_func
+            pose_out = pose_call(seq_rotations, seq_translations, gt_r=data['gt_rotations'],
+                                 gt_t=data['gt_translations'], labels=labels,
+                                 scale_factors=self._scale_factors(data, data_batch, gt_flow.device))
             (flow_out,), mask_out = self._pixel_losses(gt_flow, valid, [self.flow_loss_func], [flow_from_pred],
-                                                       self.mask_loss_func, sequence_masks)
-        (loss_pose, seq_pose), (loss_flow, seq_flow), (loss_mask, seq_mask) = pose_out, flow_out, mask_out
+                                                       self.mask_loss_func, sequence_masks, with_grads)
+        (loss_pose, seq_pose), (loss_flow, seq_flow), (loss_mask, seq_mask) = pose_out[:2], flow_out[:2], mask_out[:2]
         loss = loss_pose + loss_flow + loss_mask
         named = []
         if 'init_add_error_mean' in data:
@@ -386,11 +409,22 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             named += [(f'seq_{i}_pose_loss', seq_pose[i]), (f'seq_{i}_flow_loss', seq_flow[i]),
                       (f'seq_{i}_mask_loss', seq_mask[i])]
         named += [('loss_mask', loss_mask), ('loss_flow', loss_flow), ('loss_pose', loss_pose), ('loss', loss)]
-        return loss, None, self._log_vars(named), seq_rotations, seq_translations
+        out = (loss, None, self._log_vars(named), seq_rotations, seq_translations)
+        if not with_grads:
+            return out
+        grads = dict(sequence_flow_from_pred=flow_out[2], sequence_masks=mask_out[2])
+        if pose_is_flow:
+            grads['sequence_flow_from_pose'] = pose_out[2]
+        else:
+            grads['seq_rotations'] = pose_out[2][0]
+            if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
+                grads['seq_translations'] = pose_out[2][1]
+        return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:
-            raise NotImplementedError('training is outside the hot path (SURVEY.md section 2)')
+            raise NotImplementedError('train_step and the backward of the network are not implemented; loss_and_grads() '
+                                      'returns the loss values and their gradients at the network outputs')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
@@ -556,7 +590,8 @@ class _FlowRefinerBase(_RenderingRefiner, HipModule):
 
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:
-            raise NotImplementedError('training is outside the hot path (SURVEY.md section 2)')
+            raise NotImplementedError('train_step and the backward of the network are not implemented; loss_and_grads() '
+                                      'returns the loss values and their gradients at the network outputs')
         return self.forward_single_view(data, data_batch)
 
 
@@ -575,21 +610,30 @@ class RAFTRefinerFlowMask(_FlowRefinerBase):
         """raft_refiner_flow_mask.py:169-222 -> (loss, None, log_vars): the forward VALUES of the flow and the occlusion
         sequence losses (keys ``seq_<i>_flow_loss``, ``seq_<i>_occ_loss``, ``loss_occ``, ``loss_flow``, ``loss``).  **No
         autograd.**  ``data``: an already formatted dict, as for ``SCFlowRefiner.loss``."""
+        return self._loss(data_batch, data, False)
+
+    def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss()`` plus d loss / d prediction per iteration -> (loss, None, log_vars, grads) with the keys
+        ``sequence_flow_from_pred`` and ``sequence_masks`` (the occlusion sequence)."""
+        return self._loss(data_batch, data, True)
+
+    def _loss(self, data_batch, data, with_grads):
         self._no_depth_filter()
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         sequence_flow, sequence_occlusion = self.get_flow(data['rendered_images'], data['real_images'])
         gt_flow = self._supervision(data, self.filter_invalid_flow_by_mask)
-        ((loss_flow, seq_flow),), (loss_occ, seq_occ) = self._pixel_losses(
-            gt_flow, data['rendered_masks'], [self.flow_loss_func], [sequence_flow], self.occlusion_loss_func,
-            sequence_occlusion)
+        (flow_out,), occ_out = self._pixel_losses(gt_flow, data['rendered_masks'], [self.flow_loss_func], [sequence_flow],
+                                                  self.occlusion_loss_func, sequence_occlusion, with_grads)
+        (loss_flow, seq_flow), (loss_occ, seq_occ) = flow_out[:2], occ_out[:2]
         loss = loss_flow + loss_occ
         named = []
         for i in range(len(seq_flow)):
             named += [(f'seq_{i}_flow_loss', seq_flow[i]), (f'seq_{i}_occ_loss', seq_occ[i])]
         named += [('loss_occ', loss_occ), ('loss_flow', loss_flow), ('loss', loss)]
-        return loss, None, self._log_vars(named)
+        out = (loss, None, self._log_vars(named))
+        return out + (dict(sequence_flow_from_pred=flow_out[2], sequence_masks=occ_out[2]),) if with_grads else out
 
 
 @REFINERS.register_module()
@@ -604,13 +648,23 @@ class RAFTRefinerFlow(_FlowRefinerBase):
     def loss(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
         """raft_refiner_flow.py:177-212 -> (loss, None, log_vars): the forward VALUES of the flow sequence loss (keys
         ``seq_<i>_loss``, ``loss``).  **No autograd.**  ``data``: an already formatted dict."""
+        return self._loss(data_batch, data, False)
+
+    def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss()`` plus d loss / d prediction per iteration -> (loss, None, log_vars, grads) with the key
+        ``sequence_flow_from_pred``."""
+        return self._loss(data_batch, data, True)
+
+    def _loss(self, data_batch, data, with_grads):
         self._no_depth_filter()
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         sequence_flow = self.get_flow(data['rendered_images'], data['real_images'])
         gt_flow = self._supervision(data, self.filter_invalid_flow)
-        ((loss, seq_loss),), _ = self._pixel_losses(gt_flow, data['rendered_masks'], [self.loss_func], [sequence_flow],
-                                                    None, None)
+        (flow_out,), _ = self._pixel_losses(gt_flow, data['rendered_masks'], [self.loss_func], [sequence_flow], None, None,
+                                            with_grads)
+        loss, seq_loss = flow_out[:2]
         named = [(f'seq_{i}_loss', v) for i, v in enumerate(seq_loss)] + [('loss', loss)]
-        return loss, None, self._log_vars(named)
+        out = (loss, None, self._log_vars(named))
+        return out + (dict(sequence_flow_from_pred=flow_out[2]),) if with_grads else out
