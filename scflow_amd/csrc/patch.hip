@@ -168,29 +168,16 @@ __global__ void __launch_bounds__(PATCH_THREADS) patch_extract_kernel(const uint
       patch_tap(frame, Hf, Wf, rec.y1 + iy1, rec.x1 + ix, p.crop_pad, t10);
       patch_tap(frame, Hf, Wf, rec.y1 + iy1, rec.x1 + ix1, p.crop_pad, t11);
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const int s0 = t00[c] * a0 + t01[c] * a1, s1 = t10[c] * a0 + t11[c] * a1;
-        val[c] = min((((b0 * (s0 >> 4)) >> 16) + ((b1 * (s1 >> 4)) >> 16) + 2) >> 2, 255);
-      }
+      for (int c = 0; c < 3; ++c) val[c] = patch_blend(t00[c], t01[c], t10[c], t11[c], a0, a1, b0, b1);
     }
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int oc = p.to_rgb ? 2 - c : c;
-      res[oc][j] = ((float)val[c] - p.mean[oc]) * p.inv_std[oc];
+      res[oc][j] = patch_norm(p, val[c], oc);
     }
   }
   const int64_t HW = (int64_t)p.H * p.W;
-  float* dst = out + (int64_t)n * 3 * HW + (int64_t)Y * p.W + X0;
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if constexpr (VEC) {
-      *reinterpret_cast<float4*>(dst + c * HW) = make_float4(res[c][0], res[c][1], res[c][2], res[c][3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (X0 + j < p.W) dst[c * HW + j] = res[c][j];
-    }
-  }
+  patch_store4<VEC>(p, res, X0, HW, out + (int64_t)n * 3 * HW + (int64_t)Y * p.W + X0);
 }
 
 // ------------------------------------------------------------------------------------------------ host
@@ -232,19 +219,8 @@ extern "C" int scf_patch_boxes(const scf_mesh_store* mesh, const int32_t* labels
 extern "C" int scf_patch_extract(const uint8_t* frames, int F, int frame_h, int frame_w, const int32_t* frame_index,
                                  int N, const void* workspace, const scf_patch_params* p, float* out,
                                  scf_stream_t stream) {
-  if (!patch_params_ok(p) || !frames || !frame_index || !workspace || !out) return SCF_EINVAL;
-  if (N <= 0 || N > 65535 || F <= 0) return SCF_EINVAL;
-  if (frame_h <= 0 || frame_w <= 0 || frame_h > PATCH_MAX_FRAME || frame_w > PATCH_MAX_FRAME) return SCF_EINVAL;
-  PatchPix x;
-  for (int c = 0; c < 3; ++c) {
-    x.crop_pad[c] = p->crop_pad_val[c];
-    x.pad[c] = p->pad_val[c];
-    x.mean[c] = p->mean[c];
-    x.inv_std[c] = (float)(1.0 / (double)p->std[c]);
-  }
-  x.to_rgb = p->to_rgb != 0;
-  x.H = p->out_h;
-  x.W = p->out_w;
+  if (!patch_extract_args_ok(p, frames, frame_index, workspace, out, N, F, frame_h, frame_w)) return SCF_EINVAL;
+  const PatchPix x = patch_pix(p);
   const int64_t threads = (int64_t)((p->out_w + 3) / 4) * p->out_h;
   const dim3 grid((unsigned)scf_cdiv(threads, PATCH_THREADS), N);
   const bool vec = p->out_w % 4 == 0 && ((uintptr_t)out & 15) == 0;

@@ -1,5 +1,7 @@
 // What patch.hip and patch_train.hip share: the per-object record, items 2, 3 and 5 for one object (patch_finish), the
-// resize coefficients and the frame tap, and the check of scf_patch_params.  patch.hip states the semantics.
+// resize coefficients, the frame tap and the blend of item 3, item 6 for one value, the three plane stores of four columns,
+// and on the host the check of scf_patch_params, of the extract entries' arguments and the PatchPix they launch with.
+// patch.hip states the semantics.
 #pragma once
 #include "scf_common.h"
 #include <math.h>
@@ -139,6 +141,32 @@ __device__ __forceinline__ void patch_tap(const uint8_t* frame, int Hf, int Wf, 
   }
 }
 
+// one channel of item 3 from its four taps: the two unshifted horizontal sums, then the vertical pass (one expression:
+// with the sums named, the scalar-store patch_extract_kernel takes a VGPR more)
+__device__ __forceinline__ int patch_blend(int p00, int p01, int p10, int p11, int a0, int a1, int b0, int b1) {
+  return min((((b0 * ((p00 * a0 + p01 * a1) >> 4)) >> 16) + ((b1 * ((p10 * a0 + p11 * a1) >> 4)) >> 16) + 2) >> 2, 255);
+}
+
+// item 6 for one value that lands in output channel oc (the channel loop around it stays in the kernels: behind a call
+// patch_extract_kernel takes two SGPRs more)
+__device__ __forceinline__ float patch_norm(const PatchPix& p, int v, int oc) { return ((float)v - p.mean[oc]) * p.inv_std[oc]; }
+
+// the three plane stores of four consecutive columns from X0, res[output channel][column]; dst: column X0 of the row in
+// plane 0
+template <bool VEC>
+__device__ __forceinline__ void patch_store4(const PatchPix& p, const float (&res)[3][4], int X0, int64_t HW, float* dst) {
+#pragma unroll
+  for (int c = 0; c < 3; ++c) {
+    if constexpr (VEC) {
+      *reinterpret_cast<float4*>(dst + c * HW) = make_float4(res[c][0], res[c][1], res[c][2], res[c][3]);
+    } else {
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+        if (X0 + j < p.W) dst[c * HW + j] = res[c][j];
+    }
+  }
+}
+
 static bool patch_params_ok(const scf_patch_params* p) {
   if (!p) return false;
   if (p->out_h <= 0 || p->out_w <= 0 || p->out_h > PATCH_MAX_OUT || p->out_w > PATCH_MAX_OUT) return false;
@@ -151,6 +179,28 @@ static bool patch_params_ok(const scf_patch_params* p) {
     if (!isfinite(p->mean[c]) || !isfinite(p->std[c]) || !(p->std[c] != 0.f)) return false;
   }
   return true;
+}
+
+// what scf_patch_extract and scf_patch_extract_train check alike
+static bool patch_extract_args_ok(const scf_patch_params* p, const void* frames, const void* frame_index, const void* workspace,
+                                  const void* out, int N, int F, int frame_h, int frame_w) {
+  if (!patch_params_ok(p) || !frames || !frame_index || !workspace || !out) return false;
+  if (N <= 0 || N > 65535 || F <= 0) return false;
+  return frame_h > 0 && frame_w > 0 && frame_h <= PATCH_MAX_FRAME && frame_w <= PATCH_MAX_FRAME;
+}
+
+static PatchPix patch_pix(const scf_patch_params* p) {
+  PatchPix x;
+  for (int c = 0; c < 3; ++c) {
+    x.crop_pad[c] = p->crop_pad_val[c];
+    x.pad[c] = p->pad_val[c];
+    x.mean[c] = p->mean[c];
+    x.inv_std[c] = (float)(1.0 / (double)p->std[c]);
+  }
+  x.to_rgb = p->to_rgb != 0;
+  x.H = p->out_h;
+  x.W = p->out_w;
+  return x;
 }
 
 

@@ -384,9 +384,7 @@ __device__ __forceinline__ void pt_emit(const AugCtx& q, const PatchRec& rec, co
 #pragma unroll
       for (int c = 0; c < 3; ++c) {
         const int sh = 8 * c;
-        const int s0 = (int)((t00 >> sh) & 255) * a0 + (int)((t01 >> sh) & 255) * a1;
-        const int s1 = (int)((t10 >> sh) & 255) * a0 + (int)((t11 >> sh) & 255) * a1;
-        val[c] = min((((b0 * (s0 >> 4)) >> 16) + ((b1 * (s1 >> 4)) >> 16) + 2) >> 2, 255);
+        val[c] = patch_blend((t00 >> sh) & 255, (t01 >> sh) & 255, (t10 >> sh) & 255, (t11 >> sh) & 255, a0, a1, b0, b1);
       }
       if (mask_out) {
         const int mx = min((int)floor((double)dx * rec.rx), pw - 1);
@@ -406,7 +404,7 @@ __device__ __forceinline__ void pt_emit(const AugCtx& q, const PatchRec& rec, co
       column(j, val, mv);
       for (int c = 0; c < 3; ++c) {
         const int oc = p.to_rgb ? 2 - c : c;
-        dst[oc * HW + j] = ((float)val[c] - p.mean[oc]) * p.inv_std[oc];
+        dst[oc * HW + j] = patch_norm(p, val[c], oc);
       }
       if (md) md[j] = (uint8_t)mv;
     }
@@ -422,19 +420,10 @@ __device__ __forceinline__ void pt_emit(const AugCtx& q, const PatchRec& rec, co
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
       const int oc = p.to_rgb ? 2 - c : c;
-      res[oc][j] = ((float)val[c] - p.mean[oc]) * p.inv_std[oc];
+      res[oc][j] = patch_norm(p, val[c], oc);
     }
   }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) {
-    if constexpr (VEC) {
-      *reinterpret_cast<float4*>(dst + c * HW) = make_float4(res[c][0], res[c][1], res[c][2], res[c][3]);
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j)
-        if (X0 + j < p.W) dst[c * HW + j] = res[c][j];
-    }
-  }
+  patch_store4<VEC>(p, res, X0, HW, dst);
   if (md) {
     if constexpr (VEC) {
       *reinterpret_cast<uchar4*>(md) = make_uchar4(mres[0], mres[1], mres[2], mres[3]);
@@ -609,20 +598,9 @@ extern "C" int scf_patch_boxes_train(const scf_mesh_store* mesh, const int32_t* 
 extern "C" int scf_patch_extract_train(const uint8_t* frames, int F, int frame_h, int frame_w, const int32_t* frame_index,
                                        const uint8_t* masks, int N, const void* workspace, const scf_patch_params* p,
                                        const scf_patch_aug_params* aug, float* out, uint8_t* mask_out, scf_stream_t stream) {
-  if (!aug_params_ok(aug) || !patch_params_ok(p) || !frames || !frame_index || !workspace || !out) return SCF_EINVAL;
+  if (!aug_params_ok(aug) || !patch_extract_args_ok(p, frames, frame_index, workspace, out, N, F, frame_h, frame_w)) return SCF_EINVAL;
   if ((masks == nullptr) != (mask_out == nullptr)) return SCF_EINVAL;
-  if (N <= 0 || N > 65535 || F <= 0) return SCF_EINVAL;
-  if (frame_h <= 0 || frame_w <= 0 || frame_h > PATCH_MAX_FRAME || frame_w > PATCH_MAX_FRAME) return SCF_EINVAL;
-  PatchPix x;
-  for (int c = 0; c < 3; ++c) {
-    x.crop_pad[c] = p->crop_pad_val[c];
-    x.pad[c] = p->pad_val[c];
-    x.mean[c] = p->mean[c];
-    x.inv_std[c] = (float)(1.0 / (double)p->std[c]);
-  }
-  x.to_rgb = p->to_rgb != 0;
-  x.H = p->out_h;
-  x.W = p->out_w;
+  const PatchPix x = patch_pix(p);
   const int64_t tiles = scf_cdiv(p->out_w, PT_TW) * scf_cdiv(p->out_h, PT_TH);
   const dim3 grid((unsigned)tiles, N);
   const PatchRec* recs = static_cast<const PatchRec*>(workspace);

@@ -1498,38 +1498,35 @@ def _int_vec(t: Tensor, shape: Tuple[int, ...], dev, name: str) -> Tensor:
     return t.to(torch.int32).contiguous()
 
 
-def patch_boxes(mesh, labels: Optional[Tensor], rot: Optional[Tensor], trans: Optional[Tensor], k: Tensor,
-                frame_size: Tuple[int, int], params: '_lib.PatchParams', crop_rects: Optional[Tensor] = None) -> dict:
-    """crop rectangle, resize scale, padding and intrinsics of every object (``scf_patch_boxes``; patch.hip states
-    the semantics).  ``mesh`` is a ``mesh.DeviceMesh``, labels (N,) int GPU tensor (read on the device), rot / k
-    (N,3,3), trans (N,3), frame_size (Hf, Wf).  With ``crop_rects`` (N,4) int GPU tensor of (x1, y1, x2, y2) the
-    caller's rectangles replace the box and the crop rule, and mesh / labels / rot / trans may be None.
-    -> dict(box (N,4) the projected fp32 box, crop (N,4) int32, scale (N), transform_matrix (N,3,3), k (N,3,3), valid (N) int32, records: the
-    workspace ``extract_patches`` reads).  No host synchronisation."""
+def _patch_boxes(what: str, mesh, labels, rot, trans, k, frame_size, params, crop_rects, aug=None, id_base: int = 0,
+                 sample_ids: Optional[Tensor] = None) -> dict:
+    """``scf_patch_boxes``, or with ``aug`` ``scf_patch_boxes_train``, for the wrapper named ``what``."""
     n = k.shape[0] if isinstance(k, torch.Tensor) and k.dim() == 3 else -1
     if n <= 0:
-        raise _lib.ScflowHipError('patch_boxes: k must be (N,3,3) with N > 0')
+        raise _lib.ScflowHipError(f'{what}: k must be (N,3,3) with N > 0')
     hf, wf = int(frame_size[0]), int(frame_size[1])
     if not 0 < hf <= 16384 or not 0 < wf <= 16384:
-        raise _lib.ScflowHipError(f'patch_boxes: frame size {(hf, wf)} outside 1..16384')
+        raise _lib.ScflowHipError(f'{what}: frame size {(hf, wf)} outside 1..16384')
     kp = _mats(k, n, (3, 3), 'k')
     dev = k.device
     store, lab, rp, tp, cin = None, None, None, None, None
     if crop_rects is not None:
-        cin = _int_vec(crop_rects, (n, 4), dev, 'patch_boxes: crop_rects')
+        cin = _int_vec(crop_rects, (n, 4), dev, what + ': crop_rects')
     else:
         if mesh is None or labels is None or rot is None or trans is None:
-            raise _lib.ScflowHipError('patch_boxes: mesh, labels, rot and trans are needed without crop_rects')
-        lab = _int_vec(labels, (n,), dev, 'patch_boxes: labels')
+            raise _lib.ScflowHipError(f'{what}: mesh, labels, rot and trans are needed without crop_rects')
+        lab = _int_vec(labels, (n,), dev, what + ': labels')
         rp, tp = _mats(rot, n, (3, 3), 'rot'), _mats(trans, n, (3,), 'trans')
-        _dense(mesh.verts, 'verts')
-        if mesh.vert_offset.device != dev or mesh.vert_offset.dtype != torch.int32 or not mesh.vert_offset.is_contiguous():
-            raise _lib.ScflowHipError(f'patch_boxes: the mesh store must live on {dev} (MeshStore.on(device))')
-        store = _lib.MeshStore(mesh.verts.data_ptr(), mesh.normals.data_ptr(), mesh.colors.data_ptr(),
-                               mesh.faces.data_ptr(), mesh.vert_offset.data_ptr(), mesh.face_offset.data_ptr(),
-                               int(mesh.num_classes), int(mesh.max_faces))
+        store = _mesh_store(mesh, dev, what)
+    sp = None if store is None else C.byref(store)
+    lp = None if lab is None else lab.data_ptr()
+    cp = None if cin is None else cin.data_ptr()
     lib = _lib.load()
-    wsb = int(lib.scf_patch_workspace_bytes(n))
+    if aug is None:
+        wsb = int(lib.scf_patch_workspace_bytes(n))
+    else:
+        sid = _sample_ids(sample_ids, n, dev, what)
+        wsb = int(lib.scf_patch_train_workspace_bytes(n))
     _lib.check(min(wsb, 0), 'scf_patch_workspace_bytes')
     rec = torch.empty((wsb,), dtype=torch.uint8, device=dev)
     box = torch.empty((n, 4), dtype=torch.float32, device=dev)
@@ -1538,11 +1535,68 @@ def patch_boxes(mesh, labels: Optional[Tensor], rot: Optional[Tensor], trans: Op
     tm = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
     kout = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
     valid = torch.empty((n,), dtype=torch.int32, device=dev)
-    _lib.check(lib.scf_patch_boxes(
-        None if store is None else C.byref(store), None if lab is None else lab.data_ptr(), rp, tp, kp,
-        None if cin is None else cin.data_ptr(), n, hf, wf, C.byref(params), box.data_ptr(), crop.data_ptr(), scale.data_ptr(),
-        tm.data_ptr(), kout.data_ptr(), valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes')
-    return dict(box=box, crop=crop, scale=scale, transform_matrix=tm, k=kout, valid=valid, records=rec)
+    out = dict(box=box, crop=crop, scale=scale, transform_matrix=tm, k=kout, valid=valid, records=rec)
+    if aug is None:
+        _lib.check(lib.scf_patch_boxes(
+            sp, lp, rp, tp, kp, cp, n, hf, wf, C.byref(params), box.data_ptr(), crop.data_ptr(), scale.data_ptr(),
+            tm.data_ptr(), kout.data_ptr(), valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes')
+    else:
+        out['draws'] = draws = torch.empty((n, 8), dtype=torch.float64, device=dev)
+        _lib.check(lib.scf_patch_boxes_train(
+            sp, lp, rp, tp, kp, cp, n, hf, wf, C.byref(params), C.byref(aug), _id_base(id_base, what), sid,
+            draws.data_ptr(), box.data_ptr(), crop.data_ptr(), scale.data_ptr(), tm.data_ptr(), kout.data_ptr(),
+            valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes_train')
+    return out
+
+
+def patch_boxes(mesh, labels: Optional[Tensor], rot: Optional[Tensor], trans: Optional[Tensor], k: Tensor,
+                frame_size: Tuple[int, int], params: '_lib.PatchParams', crop_rects: Optional[Tensor] = None) -> dict:
+    """crop rectangle, resize scale, padding and intrinsics of every object (``scf_patch_boxes``; patch.hip states
+    the semantics).  ``mesh`` is a ``mesh.DeviceMesh``, labels (N,) int GPU tensor (read on the device), rot / k
+    (N,3,3), trans (N,3), frame_size (Hf, Wf).  With ``crop_rects`` (N,4) int GPU tensor of (x1, y1, x2, y2) the
+    caller's rectangles replace the box and the crop rule, and mesh / labels / rot / trans may be None.
+    -> dict(box (N,4) the projected fp32 box, crop (N,4) int32, scale (N), transform_matrix (N,3,3), k (N,3,3), valid (N) int32, records: the
+    workspace ``extract_patches`` reads).  No host synchronisation."""
+    return _patch_boxes('patch_boxes', mesh, labels, rot, trans, k, frame_size, params, crop_rects)
+
+
+def _patch_frames(frames: Tensor, what: str) -> tuple:
+    """the frames argument of an extract wrapper, checked -> (F, Hf, Wf, device)."""
+    if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4
+            or frames.shape[3] != 3 or frames.shape[0] < 1):
+        raise _lib.ScflowHipError(f'{what}: frames must be a (F,Hf,Wf,3) uint8 tensor on the GPU '
+                                  '(HIP path only, no CPU fallback)')
+    if frames.device.index != _cur_dev():
+        raise _lib.ScflowHipError(f'{what}: frames live on cuda:{frames.device.index} but the current device '
+                                  f'is cuda:{_cur_dev()}: wrap the call in torch.cuda.device(tensor.device)')
+    if not frames.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: expected contiguous frames')
+    f, hf, wf = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
+        raise _lib.ScflowHipError(f'{what}: frame size {(hf, wf)} outside 1..16384')
+    return f, hf, wf, frames.device
+
+
+def _patch_index(frame_index: Tensor, dev, what: str) -> Tensor:
+    if not isinstance(frame_index, torch.Tensor) or frame_index.dim() != 1 or frame_index.shape[0] < 1:
+        raise _lib.ScflowHipError(f'{what}: frame_index must be (N,) with N > 0')
+    return _int_vec(frame_index, (int(frame_index.shape[0]),), dev, what + ': frame_index')
+
+
+def _patch_records(records: Tensor, nbytes: int, dev, what: str, boxes: str) -> int:
+    if (not isinstance(records, torch.Tensor) or records.device != dev or records.dtype != torch.uint8
+            or not records.is_contiguous() or records.numel() != nbytes):
+        raise _lib.ScflowHipError(f'{what}: records must be the workspace {boxes} returned for the same N')
+    return records.data_ptr()
+
+
+def _patch_out(t: Optional[Tensor], shape: Tuple[int, ...], dev, what: str) -> Tensor:
+    """``out`` checked against shape and device (``_dense`` does the rest at the call), or a new tensor."""
+    if t is None:
+        return torch.empty(shape, dtype=torch.float32, device=dev)
+    if tuple(t.shape) != shape or t.device != dev:
+        raise _lib.ScflowHipError(f'{what}: out must be {shape} on {dev}')
+    return t
 
 
 def extract_patches(frames: Tensor, frame_index: Tensor, records: Tensor, params: '_lib.PatchParams',
@@ -1550,34 +1604,14 @@ def extract_patches(frames: Tensor, frame_index: Tensor, records: Tensor, params
     """crop, resize, pad and normalise every object's patch (``scf_patch_extract``).  frames (F,Hf,Wf,3) uint8 GPU
     tensor (BGR, as cv2 loads them), frame_index (N,) int GPU tensor, ``records`` from ``patch_boxes``.
     -> (N,3,out_h,out_w) float32.  No host synchronisation."""
-    if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4
-            or frames.shape[3] != 3 or frames.shape[0] < 1):
-        raise _lib.ScflowHipError('extract_patches: frames must be a (F,Hf,Wf,3) uint8 tensor on the GPU '
-                                  '(HIP path only, no CPU fallback)')
-    if frames.device.index != _cur_dev():
-        raise _lib.ScflowHipError(f'extract_patches: frames live on cuda:{frames.device.index} but the current device '
-                                  f'is cuda:{_cur_dev()}: wrap the call in torch.cuda.device(tensor.device)')
-    if not frames.is_contiguous():
-        raise _lib.ScflowHipError('extract_patches: expected contiguous frames')
-    f, hf, wf = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
-        raise _lib.ScflowHipError(f'extract_patches: frame size {(hf, wf)} outside 1..16384')
-    dev = frames.device
-    if not isinstance(frame_index, torch.Tensor) or frame_index.dim() != 1 or frame_index.shape[0] < 1:
-        raise _lib.ScflowHipError('extract_patches: frame_index must be (N,) with N > 0')
-    n = int(frame_index.shape[0])
-    fidx = _int_vec(frame_index, (n,), dev, 'extract_patches: frame_index')
+    f, hf, wf, dev = _patch_frames(frames, 'extract_patches')
+    fidx = _patch_index(frame_index, dev, 'extract_patches')
+    n = int(fidx.shape[0])
     lib = _lib.load()
-    if (not isinstance(records, torch.Tensor) or records.device != dev or records.dtype != torch.uint8
-            or not records.is_contiguous() or records.numel() != int(lib.scf_patch_workspace_bytes(n))):
-        raise _lib.ScflowHipError('extract_patches: records must be the workspace patch_boxes returned for the same N')
-    shape = (n, 3, int(params.out_h), int(params.out_w))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or out.device != dev:
-        raise _lib.ScflowHipError(f'extract_patches: out must be {shape} on {dev}')
-    _lib.check(lib.scf_patch_extract(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), n, records.data_ptr(),
-                                     C.byref(params), _dense(out, 'out'), _stream()), 'scf_patch_extract')
+    rec = _patch_records(records, int(lib.scf_patch_workspace_bytes(n)), dev, 'extract_patches', 'patch_boxes')
+    out = _patch_out(out, (n, 3, int(params.out_h), int(params.out_w)), dev, 'extract_patches')
+    _lib.check(lib.scf_patch_extract(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), n, rec, C.byref(params), _dense(out, 'out'),
+                                     _stream()), 'scf_patch_extract')
     return out
 
 
@@ -1705,41 +1739,8 @@ def patch_boxes_train(mesh, labels: Optional[Tensor], rot: Optional[Tensor], tra
     (``scf_patch_boxes_train``).  -> what ``patch_boxes`` returns, with ``records`` the train workspace
     ``extract_patches_train`` reads (its head is what ``extract_patches`` reads: ``records[:64 * N]``) and ``draws``
     (N,8) float64 = (size_ratio, h gain, s gain, v gain, sigma, k, hsv on, noise on).  No host synchronisation."""
-    n = k.shape[0] if isinstance(k, torch.Tensor) and k.dim() == 3 else -1
-    if n <= 0:
-        raise _lib.ScflowHipError('patch_boxes_train: k must be (N,3,3) with N > 0')
-    hf, wf = int(frame_size[0]), int(frame_size[1])
-    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
-        raise _lib.ScflowHipError(f'patch_boxes_train: frame size {(hf, wf)} outside 1..16384')
-    kp = _mats(k, n, (3, 3), 'k')
-    dev = k.device
-    store, lab, rp, tp, cin = None, None, None, None, None
-    if crop_rects is not None:
-        cin = _int_vec(crop_rects, (n, 4), dev, 'patch_boxes_train: crop_rects')
-    else:
-        if mesh is None or labels is None or rot is None or trans is None:
-            raise _lib.ScflowHipError('patch_boxes_train: mesh, labels, rot and trans are needed without crop_rects')
-        lab = _int_vec(labels, (n,), dev, 'patch_boxes_train: labels')
-        rp, tp = _mats(rot, n, (3, 3), 'rot'), _mats(trans, n, (3,), 'trans')
-        store = _mesh_store(mesh, dev, 'patch_boxes_train')
-    sid = _sample_ids(sample_ids, n, dev, 'patch_boxes_train')
-    lib = _lib.load()
-    wsb = int(lib.scf_patch_train_workspace_bytes(n))
-    _lib.check(min(wsb, 0), 'scf_patch_train_workspace_bytes')
-    rec = torch.empty((wsb,), dtype=torch.uint8, device=dev)
-    draws = torch.empty((n, 8), dtype=torch.float64, device=dev)
-    box = torch.empty((n, 4), dtype=torch.float32, device=dev)
-    crop = torch.empty((n, 4), dtype=torch.int32, device=dev)
-    scale = torch.empty((n,), dtype=torch.float32, device=dev)
-    tm = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
-    kout = torch.empty((n, 3, 3), dtype=torch.float32, device=dev)
-    valid = torch.empty((n,), dtype=torch.int32, device=dev)
-    _lib.check(lib.scf_patch_boxes_train(
-        None if store is None else C.byref(store), None if lab is None else lab.data_ptr(), rp, tp, kp,
-        None if cin is None else cin.data_ptr(), n, hf, wf, C.byref(params), C.byref(aug),
-        _id_base(id_base, 'patch_boxes_train'), sid, draws.data_ptr(), box.data_ptr(), crop.data_ptr(), scale.data_ptr(),
-        tm.data_ptr(), kout.data_ptr(), valid.data_ptr(), rec.data_ptr(), _stream()), 'scf_patch_boxes_train')
-    return dict(box=box, crop=crop, scale=scale, transform_matrix=tm, k=kout, valid=valid, records=rec, draws=draws)
+    return _patch_boxes('patch_boxes_train', mesh, labels, rot, trans, k, frame_size, params, crop_rects, aug, id_base,
+                        sample_ids)
 
 
 def extract_patches_train(frames: Tensor, frame_index: Tensor, records: Tensor, params: '_lib.PatchParams',
@@ -1749,52 +1750,31 @@ def extract_patches_train(frames: Tensor, frame_index: Tensor, records: Tensor, 
     resize (nearest) and pad its mask (``scf_patch_extract_train``).  frames (F,Hf,Wf,3) uint8 GPU tensor (BGR),
     frame_index (N,) int GPU tensor, ``records`` from ``patch_boxes_train``, masks (N,Hf,Wf) uint8 or bool (nonzero =
     object) or None.  -> (img (N,3,out_h,out_w) float32, mask (N,out_h,out_w) bool or None).  No host synchronisation."""
-    if (not isinstance(frames, torch.Tensor) or not frames.is_cuda or frames.dtype != torch.uint8 or frames.dim() != 4
-            or frames.shape[3] != 3 or frames.shape[0] < 1):
-        raise _lib.ScflowHipError('extract_patches_train: frames must be a (F,Hf,Wf,3) uint8 tensor on the GPU '
-                                  '(HIP path only, no CPU fallback)')
-    if frames.device.index != _cur_dev():
-        raise _lib.ScflowHipError(f'extract_patches_train: frames live on cuda:{frames.device.index} but the current '
-                                  f'device is cuda:{_cur_dev()}: wrap the call in torch.cuda.device(tensor.device)')
-    if not frames.is_contiguous():
-        raise _lib.ScflowHipError('extract_patches_train: expected contiguous frames')
-    f, hf, wf = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
-    if not 0 < hf <= 16384 or not 0 < wf <= 16384:
-        raise _lib.ScflowHipError(f'extract_patches_train: frame size {(hf, wf)} outside 1..16384')
-    dev = frames.device
-    if not isinstance(frame_index, torch.Tensor) or frame_index.dim() != 1 or frame_index.shape[0] < 1:
-        raise _lib.ScflowHipError('extract_patches_train: frame_index must be (N,) with N > 0')
-    n = int(frame_index.shape[0])
-    fidx = _int_vec(frame_index, (n,), dev, 'extract_patches_train: frame_index')
+    what = 'extract_patches_train'
+    f, hf, wf, dev = _patch_frames(frames, what)
+    fidx = _patch_index(frame_index, dev, what)
+    n = int(fidx.shape[0])
     lib = _lib.load()
-    if (not isinstance(records, torch.Tensor) or records.device != dev or records.dtype != torch.uint8
-            or not records.is_contiguous() or records.numel() != int(lib.scf_patch_train_workspace_bytes(n))):
-        raise _lib.ScflowHipError('extract_patches_train: records must be the workspace patch_boxes_train returned for '
-                                  'the same N')
+    rec = _patch_records(records, int(lib.scf_patch_train_workspace_bytes(n)), dev, what, 'patch_boxes_train')
     shape = (n, 3, int(params.out_h), int(params.out_w))
-    if out is None:
-        out = torch.empty(shape, dtype=torch.float32, device=dev)
-    elif tuple(out.shape) != shape or out.device != dev:
-        raise _lib.ScflowHipError(f'extract_patches_train: out must be {shape} on {dev}')
+    out = _patch_out(out, shape, dev, what)
     mp = None
     if masks is not None:
         if (not isinstance(masks, torch.Tensor) or masks.device != dev or masks.dtype not in (torch.uint8, torch.bool)
                 or tuple(masks.shape) != (n, hf, wf) or not masks.is_contiguous()):
-            raise _lib.ScflowHipError(f'extract_patches_train: masks must be a contiguous uint8 / bool tensor of shape '
-                                      f'{(n, hf, wf)} on {dev}')
+            raise _lib.ScflowHipError(f'{what}: masks must be a contiguous uint8 / bool tensor of shape {(n, hf, wf)} on {dev}')
         mshape = (n, shape[2], shape[3])
         if mask_out is None:
             mask_out = torch.empty(mshape, dtype=torch.bool, device=dev)
         elif (tuple(mask_out.shape) != mshape or mask_out.device != dev or mask_out.dtype != torch.bool
               or not mask_out.is_contiguous()):
-            raise _lib.ScflowHipError(f'extract_patches_train: mask_out must be a contiguous bool tensor {mshape} on {dev}')
+            raise _lib.ScflowHipError(f'{what}: mask_out must be a contiguous bool tensor {mshape} on {dev}')
         mp = masks.data_ptr()
     elif mask_out is not None:
-        raise _lib.ScflowHipError('extract_patches_train: mask_out without masks')
-    _lib.check(lib.scf_patch_extract_train(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), mp, n, records.data_ptr(),
-                                           C.byref(params), C.byref(aug), _dense(out, 'out'),
-                                           None if mask_out is None else mask_out.data_ptr(), _stream()),
-               'scf_patch_extract_train')
+        raise _lib.ScflowHipError(f'{what}: mask_out without masks')
+    _lib.check(lib.scf_patch_extract_train(frames.data_ptr(), f, hf, wf, fidx.data_ptr(), mp, n, rec, C.byref(params),
+                                           C.byref(aug), _dense(out, 'out'), None if mask_out is None else mask_out.data_ptr(),
+                                           _stream()), 'scf_patch_extract_train')
     return out, mask_out
 
 

@@ -14,7 +14,7 @@ import torch
 import scflow_amd
 from scflow_amd import _lib, ops
 from scflow_amd.mesh import MeshStore, icosphere, make_mesh
-from scflow_amd.patches import PatchPipeline
+from scflow_amd.patches import PatchPipeline, TrainPatchPipeline
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GOLDEN = os.path.join(ROOT, 'tests', 'golden')
@@ -392,6 +392,27 @@ def _edit(kind, **kw):
 def test_from_cfg_refuses_what_it_cannot_do(steps, word):
     with pytest.raises(NotImplementedError, match=word):
         PatchPipeline.from_cfg(steps, _store())
+
+
+@pytest.mark.parametrize('case', ['keep_ratio', 'img_scale', 'keep_intrinsic', 'dst_k', 'unknown', 'no_normalize'])
+@pytest.mark.parametrize('name', ['PatchPipeline', 'TrainPatchPipeline'])
+def test_shared_refusals_carry_the_asked_class_name(name, case):
+    """the two classes refuse these through one base class: the message starts with the class that was asked."""
+    if name == 'PatchPipeline':
+        cls, steps = PatchPipeline, _val_pipeline()
+    else:
+        from test_patches_train_host import TRAIN_PIPELINE              # that module imports this one
+        cls, steps = TrainPatchPipeline, [dict(s) for s in TRAIN_PIPELINE]
+
+    def edit(kind, **kw):
+        return [dict(s, **kw) if s['type'] == kind else s for s in steps]
+    steps = dict(keep_ratio=edit('Resize', keep_ratio=False), img_scale=edit('Resize', img_scale=(256, 320)),
+                 keep_intrinsic=edit('RemapPose', keep_intrinsic=True),
+                 dst_k=edit('RemapPose', dst_k=[1, 0, 0, 0, 1, 0, 0, 0, 1]), unknown=steps + [dict(type='Mystery')],
+                 no_normalize=[s for s in steps if s['type'] != 'Normalize'])[case]
+    with pytest.raises(NotImplementedError) as err:
+        cls.from_cfg(steps, _store())
+    assert str(err.value).startswith(name + ': ')
 
 
 def test_patch_params_are_checked_by_name():
