@@ -840,6 +840,62 @@ int scf_unproject_depth(const float* depth, const float* K, const float* R0, con
 int scf_resize_bilinear(const float* a, const float* b, float* out, int64_t planes, int Hin,
                         int Win, int Hout, int Wout, float mul, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Backward of the parameter-free tail of an SCFlow iteration (scflow_decoder.py:222-249): the vector-Jacobian product
+ * that takes d loss / d (flow_from_pose, flow_from_pred, rotation, translation, up-sampled mask) of every iteration to
+ * d loss / d (delta_flow, mask, delta_rotation, delta_translation).  Every entry takes the T <= SCF_TAIL_MAX_T
+ * iterations as HOST arrays of device pointers and is one launch; none allocates, synchronises or reads back; no
+ * entry uses atomics, and every sum has one order fixed by the geometry, so results are bit-identical from run to run
+ * and do not depend on how many iterations share a call.
+ * Added without a version bump (SCF_VERSION stays at .3), as the renderer's and the losses' entries were: the presence of
+ * scf_pose_tail_grad marks the feature.
+ * --------------------------------------------------------------------------------- */
+#define SCF_TAIL_MAX_T 32
+#define SCF_TAIL_DETACH_POSE 1            /* detach_pose: no gradient from iteration i into the pose of iteration i - 1 */
+#define SCF_TAIL_DETACH_DEPTH_FOR_XY 2    /* detach_depth_for_xy (pose.py:142-147): v_z is a constant in v_x, v_y */
+
+/* Adjoint of scf_resize_bilinear for the same (Hin, Win, Hout, Wout):  out[t] (planes, Hin, Win) = mul * U^T (g[t] +
+ * g_add[t]?) with g[t] (planes, Hout, Wout) and U the forward's interpolation matrix, its coordinate fl(fl(scale) *
+ * index) and its weights l = f - i0, 1 - l included; the clamped +1 tap at the last row / column puts both weights
+ * on the same node.  accumulate != 0: out[t] += instead of =.  g_add may be NULL, and so may any of its entries.
+ * A second job of the same geometry (g1, out1, planes1, mul1, accumulate1; planes1 = 0: none) rides in the launch:
+ * the flow planes and the mask planes of a pass.
+ * Order of the sums (fp32, no contraction): per input node, rows ascending of  wy * (quads of four output columns
+ * ascending of (columns ascending of wx * g)); see tail_grad.hip.  Two kernels produce these bits: a workgroup-per-plane
+ * walk with 16-byte loads when Wout % 4 == 0, every g[t] / g1[t] is 16-byte aligned, there is no g_add and the x scale
+ * is <= 1/4 (the x8 up-sampling of the decoder), and a thread-per-node gather otherwise. */
+int scf_resize_bilinear_grad(const float* const* g, const float* const* g_add, float* const* out, int64_t planes, float mul,
+                             int accumulate, const float* const* g1, float* const* out1, int64_t planes1, float mul1,
+                             int accumulate1, int T, int Hin, int Win, int Hout, int Wout, scf_stream_t stream);
+
+/* Re-projection sums of scf_reproject_flow's backward: for iteration i and sample n, over the pixels the forward
+ * treats as foreground (depth > 0; NaN is background), with P and q = K (R_i P + t_i) recomputed as the forward does,
+ *   g_q = (gu / qz, gv / qz, -(gu qx + gv qy) / qz^2),  g_p = K^T g_q   (fp32),
+ *   words [0, 9) = sum g_p (x) P  (row-major: d / dR_i),  words [9, 12) = sum g_p  (d / dt_i)   (fp64, fixed order).
+ * g_flow[i] (N,2,H,W) may be NULL: exact zeros, as for a sample without foreground.  The workspace receives
+ * (T, N, tiles, 12) doubles, tiles = workspace_bytes / (T * N * 96): per-block partial sums that scf_pose_tail_grad
+ * (or the caller) adds in ascending tile order.  scf_tail_grad_workspace_bytes(N, H, W, T) bytes of device memory. */
+int64_t scf_tail_grad_workspace_bytes(int N, int H, int W, int T);
+int scf_reproject_flow_grad(const float* depth, const float* K, const float* R0, const float* t0, const float* const* R,
+                            const float* const* t, const float* const* g_flow, int T, int N, int H, int W, void* workspace,
+                            scf_stream_t stream);
+
+/* Reverse scan over the pose updates  R_i = Rd(d_rot_i) R_{i-1},  t_i = compose(d_trans_i, t_{i-1})  (scf_pose_update
+ * on the selected rows; R_{-1} = R0, t_{-1} = t0 get no gradient), one thread per sample, i = T-1 .. 0:
+ *   G = g_R[i] | g_t[i]  +  the re-projection sums of iteration i  +  carry
+ *   g_d_rot[i]   = ortho6d backward of  G_R R_{i-1}^T  (F.normalize's backward: through the norm only where it is
+ *                  not clamped at 1e-12)
+ *   g_d_trans[i] = backward of the compose, for both depth transforms (label_mode & SCF_POSE_DEPTH_LINEAR)
+ *   carry        = (Rd^T G_R, (d t_i / d t_{i-1})^T G_t), or 0 under SCF_TAIL_DETACH_POSE.
+ * Evaluated in fp64 from the fp32 values the forward stored (d_rot[i] (N,6), d_trans[i] (N,3), R[i] (N,3,3), t[i] (N,3):
+ * entry i - 1 is the input of iteration i; entry T - 1 is not read); each output is rounded to fp32 once.
+ * g_R, g_t: NULL, or arrays whose entries may be NULL.  reproject_sums: NULL, or the workspace scf_reproject_flow_grad
+ * wrote for the same (T, N, H, W). */
+int scf_pose_tail_grad(const float* const* d_rot, const float* const* d_trans, const float* R0, const float* t0,
+                       const float* const* R, const float* const* t, const float* const* g_R, const float* const* g_t,
+                       const void* reproject_sums, int H, int W, int flags, int label_mode, float* const* g_d_rot,
+                       float* const* g_d_trans, int T, int N, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

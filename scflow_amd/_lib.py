@@ -279,6 +279,15 @@ SIGNATURES = {
     'scf_unproject_depth': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_resize_bilinear': (C.c_int, [_fp, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                       C.c_int, C.c_float, _fp]),
+    'scf_resize_bilinear_grad': (C.c_int, [C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int64, C.c_float, C.c_int,
+                                           C.POINTER(_fp), C.POINTER(_fp), C.c_int64, C.c_float, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_tail_grad_workspace_bytes': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_reproject_flow_grad': (C.c_int, [_fp, _fp, _fp, _fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp), C.c_int, C.c_int,
+                                          C.c_int, C.c_int, _fp, _fp]),
+    'scf_pose_tail_grad': (C.c_int, [C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
+                                     C.POINTER(_fp), _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
+                                     C.c_int, C.c_int, _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),

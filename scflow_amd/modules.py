@@ -606,9 +606,11 @@ class SCFlowDecoder(HipModule):
         if net_type != 'Basic':
             raise NotImplementedError("SCFlowDecoder: net_type='Basic'")
         self.mask_flow, self.mask_corr = bool(mask_flow), bool(mask_corr)      # scflow_decoder.py:199-205
+        # scflow_decoder.py:192-193, 232-233: autograd only -- the forward ignores them, tail_backward reads them
+        self.detach_flow, self.detach_pose = bool(detach_flow), bool(detach_pose)
         # pose.py:137-141: 'exp' -> t_z / exp(d_z); ANY other value takes the reference's else branch t_z * (d_z + 1)
         self.depth_transform = depth_transform
-        self.detach_depth_for_xy = detach_depth_for_xy      # autograd only (pose.py:142-147): no effect at inference
+        self.detach_depth_for_xy = detach_depth_for_xy      # autograd only (pose.py:142-147): tail_backward reads it
         self.net_type, self.num_levels, self.radius, self.iters = net_type, num_levels, radius, iters
         self.h_channels = self._h_channels[net_type]
         self.cxt_channels = self._cxt_channels[net_type]
@@ -724,6 +726,72 @@ class SCFlowDecoder(HipModule):
             for lst, v in zip(outs, (flow, flow_pred, rot, trans, up_mask, d_rot, d_trans)):
                 lst.append(v)
         return outs
+
+
+def _scflow_tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translation: Tensor, depth: Tensor,
+                          internel_k: Tensor, extra_flow_lr=None):
+    """Vector-Jacobian product of the parameter-free tail of every iteration (scflow_decoder.py:222-249: the x8
+    up-sampling of ``flow_lr + delta_flow`` and of the mask, ``get_pose_from_delta_pose``, the pose-induced flow and,
+    with ``detach_flow=False``, its 1/8 down-sampling into the next iteration).
+
+    ``outs``: the 7-tuple ``forward`` returned.  ``grads``: cotangents under the keys of ``loss_and_grads()``
+    (``sequence_flow_from_pose``, ``sequence_flow_from_pred``, ``seq_rotations``, ``seq_translations``,
+    ``sequence_masks``), each a list over the iterations, each optional.  ``extra_flow_lr``: optional list of cotangents
+    of ``flow_lr_i`` (N,2,h,w) from a later lookup / motion-encoder backward.  Returns the gradients at the head outputs:
+    ``dict(delta_flow_preds, masks, delta_rotation_preds, delta_translation_preds)``, a list per key (``masks`` at the
+    post-sigmoid map; the sigmoid's derivative belongs to the head backward).  ``detach_flow`` / ``detach_pose`` /
+    ``detach_depth_for_xy`` / ``depth_transform`` are the decoder's.  Launches: one for all up-sampling adjoints, one for
+    the pose scan; one more when a pose-induced flow has a cotangent, one more under ``detach_flow=False``."""
+    rots, transs, d_rots, d_transs = outs[2], outs[3], outs[5], outs[6]
+    T = len(rots)
+    n, H, W = depth.shape
+    scale = 2 ** (self.num_levels - 1)
+    h, w = H // scale, W // scale
+    seq = lambda key: None if grads.get(key) is None else list(grads[key])       # noqa: E731
+    g_fpose, g_fpred, g_mask = seq('sequence_flow_from_pose'), seq('sequence_flow_from_pred'), seq('sequence_masks')
+    for name, s_ in (('sequence_flow_from_pose', g_fpose), ('sequence_flow_from_pred', g_fpred), ('sequence_masks', g_mask),
+                     ('extra_flow_lr', extra_flow_lr)):
+        if s_ is not None and len(s_) != T:
+            raise ValueError(f'tail_backward: {name} has {len(s_)} entries for {T} iterations')
+    dev = depth.device
+    zeros = lambda *shape: torch.zeros((T,) + shape, dtype=torch.float32, device=dev).unbind(0)   # noqa: E731
+    if g_mask is not None:
+        g_mask = [m.view(n, 1, H, W) for m in g_mask]
+    # ---- up-sampling adjoints: g_delta_flow_i = scale U^T g_flow_pred_i, g_mask_i = U^T g_up_mask_i, one launch
+    if g_fpred is not None and g_mask is not None:
+        g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale), second=(g_mask, 1.0))
+    elif g_fpred is not None:
+        g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale)), list(zeros(n, 1, h, w))
+    elif g_mask is not None:
+        g_dflow, g_m = list(zeros(n, 2, h, w)), ops.resize_bilinear_grad(g_mask, (h, w))
+    else:
+        g_dflow, g_m = list(zeros(n, 2, h, w)), list(zeros(n, 1, h, w))
+    # ---- detach_flow=False: flow_lr_i = D(flow_from_pose_{i-1}) / scale, so g_flow_from_pose_{i-1} += D^T (g_flow_lr_i) / scale
+    if not self.detach_flow and T > 1 and (g_fpred is not None or extra_flow_lr is not None):
+        src = g_dflow[1:]
+        add = None if extra_flow_lr is None else list(extra_flow_lr[1:])
+        if g_fpred is None:                       # only the caller's cotangents of flow_lr
+            src, add = [e if e is not None else z for e, z in zip(add, g_dflow[1:])], None
+        if g_fpose is None:
+            g_fpose = ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add) + [None]
+        else:                                     # the caller's cotangents are not written: accumulate into copies
+            acc = [g.clone() for g in g_fpose[:-1]]
+            ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add, out=acc, accumulate=True)
+            g_fpose = acc + [g_fpose[-1]]
+    # ---- re-projection sums of every iteration, one launch
+    sums = None
+    if g_fpose is not None:
+        sums = ops.reproject_flow_grad(g_fpose, depth, internel_k, ref_rotation.contiguous(), ref_translation.contiguous(),
+                                       rots, transs)
+    # ---- combine + reverse scan over the pose updates, one launch
+    g_drot, g_dtrans = ops.pose_update_grad(d_rots, d_transs, ref_rotation.contiguous(), ref_translation.contiguous(), rots, transs,
+                                            g_rots=seq('seq_rotations'), g_transs=seq('seq_translations'),
+                                            reproject_sums=sums, image_hw=(H, W), detach_pose=self.detach_pose,
+                                            detach_depth_for_xy=self.detach_depth_for_xy, label_mode=self.pose_flags())
+    return dict(delta_flow_preds=g_dflow, masks=g_m, delta_rotation_preds=g_drot, delta_translation_preds=g_dtrans)
+
+
+SCFlowDecoder.tail_backward = _scflow_tail_backward
 
 
 def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,

@@ -29,7 +29,7 @@ __all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scfl
            'get_conv_precision', 'set_conv_kslices', 'conv_kslices', 'conv_kslices_for', 'constant', 'clear_constants', 'register_conv_workspace', 'choose_kc', 'conv2d', 'conv2d_pair', 'corr_build', 'corr_lookup',
            'instance_norm', 'group_norm_relu', 'linear', 'fc_splitk', 'fc_slices', 'pose_update', 'reproject_flow',
            'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
-           'unproject_depth', 'linear_pair', 'resize_bilinear', 'convex_upsample', 'avgpool2x2', 'copy_channels',
+           'unproject_depth', 'linear_pair', 'resize_bilinear', 'resize_bilinear_grad', 'reproject_flow_grad', 'pose_update_grad', 'convex_upsample', 'avgpool2x2', 'copy_channels',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_TANH', 'CONV_PLAIN', 'CONV_GRU_ZR',
            'CONV_GRU_Q']
 
@@ -1799,6 +1799,134 @@ def resize_bilinear(a: Tensor, out_hw: Tuple[int, int], mul: float = 1.0,
                                                ho, wo, float(mul), _stream()),
                'scf_resize_bilinear')
     return out
+
+
+TAIL_MAX_T = 32                                  # SCF_TAIL_MAX_T
+TAIL_DETACH_POSE, TAIL_DETACH_DEPTH_FOR_XY = 1, 2
+
+
+def _ptrs(tensors, name: str, n_expected: Optional[int] = None, shape=None, optional: bool = False):
+    """HOST array of the device pointers of a list of dense fp32 GPU tensors (None entries -> NULL when ``optional``)."""
+    if tensors is None:
+        return None
+    if n_expected is not None and len(tensors) != n_expected:
+        raise ValueError(f'{name}: {len(tensors)} entries for {n_expected} iterations')
+    ptrs = []
+    for i, t in enumerate(tensors):
+        if t is None:
+            if not optional:
+                raise ValueError(f'{name}[{i}] is None')
+            ptrs.append(None)
+            continue
+        if shape is not None and tuple(t.shape) != tuple(shape):
+            raise _lib.ScflowHipError(f'{name}[{i}] has shape {tuple(t.shape)}, expected {tuple(shape)}')
+        ptrs.append(_dense(t, f'{name}[{i}]'))
+    return (C.c_void_p * len(ptrs))(*ptrs)
+
+
+def _seq_like(seq, shape):
+    """T fresh tensors of ``shape`` for the T entries of ``seq``: one allocation, a view per iteration."""
+    return list(torch.empty((len(seq),) + tuple(shape), dtype=torch.float32, device=seq[0].device).unbind(0))
+
+
+def resize_bilinear_grad(g, in_hw: Tuple[int, int], mul: float = 1.0, add=None, out=None, accumulate: bool = False,
+                         second=None):
+    """``scf_resize_bilinear_grad``: the adjoint of ``resize_bilinear(a, out_hw, mul)`` for ``a`` of size ``in_hw``.
+    ``g``: one (N,C,Hout,Wout) tensor or a list of T of them (one launch for all) -> mul * U^T (g + add), (N,C,*in_hw),
+    in the same structure.  ``out``: destination(s) to write, or with ``accumulate`` to add to.  ``second=(g2, mul2[, out2[,
+    accumulate2]])``: a second job of the same geometry in the same launch; the result is then a pair."""
+    single = isinstance(g, torch.Tensor)
+    gs = [g] if single else list(g)
+    T = len(gs)
+    if T == 0 or T > TAIL_MAX_T:
+        raise _lib.ScflowHipError(f'resize_bilinear_grad: 1 .. {TAIL_MAX_T} iterations, got {T}')
+    hin, win = in_hw
+    if gs[0].dim() != 4:
+        raise _lib.ScflowHipError('resize_bilinear_grad: expected (N,C,Hout,Wout) gradients')
+    n, c, ho, wo = gs[0].shape
+
+    def job(gl, outs, acc, name):
+        n2, c2 = gl[0].shape[:2]
+        pg = _ptrs(gl, name, T, (n2, c2, ho, wo))
+        if outs is None:
+            if acc:
+                raise ValueError(f'{name}: accumulate needs a destination')
+            outs = _seq_like(gl, (n2, c2, hin, win))
+        else:
+            outs = [outs] if isinstance(outs, torch.Tensor) else list(outs)
+        return pg, _ptrs(outs, name + ' out', T, (n2, c2, hin, win)), n2 * c2, outs
+
+    pg, po, planes, outs = job(gs, out, accumulate, 'g')
+    padd = None
+    if add is not None:
+        adds = [add] if isinstance(add, torch.Tensor) else list(add)
+        padd = _ptrs(adds, 'add', T, (n, c, ho, wo), optional=True)
+    pg1 = po1 = None
+    planes1, mul1, acc1, outs1 = 0, 1.0, False, None
+    if second is not None:
+        g2, mul1 = second[0], float(second[1])
+        out2 = second[2] if len(second) > 2 else None
+        acc1 = bool(second[3]) if len(second) > 3 else False
+        pg1, po1, planes1, outs1 = job([g2] if isinstance(g2, torch.Tensor) else list(g2), out2, acc1, 'second')
+    _lib.check(_lib.load().scf_resize_bilinear_grad(pg, padd, po, planes, float(mul), int(bool(accumulate)), pg1, po1, planes1,
+                                                    mul1, int(acc1), T, hin, win, ho, wo, _stream()),
+               'scf_resize_bilinear_grad')
+    res = outs[0] if single else outs
+    if second is None:
+        return res
+    return res, (outs1[0] if isinstance(second[0], torch.Tensor) else outs1)
+
+
+def reproject_flow_grad(g_flows, depth: Tensor, k: Tensor, rot0: Tensor, trans0: Tensor, rots, transs) -> Tensor:
+    """``scf_reproject_flow_grad``: the re-projection sums of T iterations in one launch -> (T, N, tiles, 12) float64
+    per-block partial sums, to be added over ``tiles`` in ascending order (``pose_update_grad`` does): words [0, 9) =
+    d / dR_i (row-major), [9, 12) = d / dt_i.  ``g_flows``: T cotangents (N,2,H,W) of ``reproject_flow``'s output; None
+    entries give exact zeros."""
+    T = len(g_flows)
+    n, h, w = depth.shape
+    if T == 0 or T > TAIL_MAX_T:
+        raise _lib.ScflowHipError(f'reproject_flow_grad: 1 .. {TAIL_MAX_T} iterations, got {T}')
+    lib = _lib.load()
+    nbytes = int(lib.scf_tail_grad_workspace_bytes(n, h, w, T))
+    _lib.check(min(nbytes, 0), 'scf_tail_grad_workspace_bytes')
+    ws = torch.empty((nbytes // 8,), dtype=torch.float64, device=depth.device)
+    _lib.check(lib.scf_reproject_flow_grad(
+        _dense(depth, 'depth'), _mats(k, n, (3, 3), 'k'), _mats(rot0, n, (3, 3), 'rot0'), _mats(trans0, n, (3,), 'trans0'),
+        _ptrs(rots, 'rots', T, (n, 3, 3)), _ptrs(transs, 'transs', T, (n, 3)),
+        _ptrs(g_flows, 'g_flows', T, (n, 2, h, w), optional=True), T, n, h, w, ws.data_ptr(), _stream()),
+        'scf_reproject_flow_grad')
+    return ws.view(T, n, -1, 12)
+
+
+def pose_update_grad(d_rots, d_transs, rot0: Tensor, trans0: Tensor, rots, transs, g_rots=None, g_transs=None,
+                     reproject_sums: Optional[Tensor] = None, image_hw: Optional[Tuple[int, int]] = None,
+                     detach_pose: bool = True, detach_depth_for_xy: bool = False, label_mode: int = 0):
+    """``scf_pose_tail_grad``: the reverse scan over T pose updates -> (list of d / d delta_rotation_i (N,6), list of
+    d / d delta_translation_i (N,3)).  ``d_rots`` / ``d_transs``: the selected head outputs ``pose_update`` returned;
+    ``rots`` / ``transs``: the poses it returned (entry i - 1 is the input of iteration i, ``rot0`` / ``trans0`` of the
+    first); ``g_rots`` / ``g_transs``: cotangents of the poses (lists, None entries allowed); ``reproject_sums``: what
+    ``reproject_flow_grad`` returned for images of ``image_hw``; ``label_mode``: the depth bit of ``pose_update``."""
+    T = len(d_rots)
+    if T == 0 or T > TAIL_MAX_T:
+        raise _lib.ScflowHipError(f'pose_update_grad: 1 .. {TAIL_MAX_T} iterations, got {T}')
+    n = d_rots[0].shape[0]
+    h, w = image_hw if image_hw is not None else (0, 0)
+    sums = None
+    if reproject_sums is not None:
+        lib = _lib.load()
+        if image_hw is None or reproject_sums.dtype != torch.float64 or not reproject_sums.is_cuda or \
+                reproject_sums.numel() * 8 != int(lib.scf_tail_grad_workspace_bytes(n, h, w, T)):
+            raise _lib.ScflowHipError('reproject_sums: expected what reproject_flow_grad returned for image_hw')
+        sums = reproject_sums.contiguous()
+    g_dr, g_dt = _seq_like(d_rots, (n, 6)), _seq_like(d_rots, (n, 3))
+    flags = (TAIL_DETACH_POSE if detach_pose else 0) | (TAIL_DETACH_DEPTH_FOR_XY if detach_depth_for_xy else 0)
+    _lib.check(_lib.load().scf_pose_tail_grad(
+        _ptrs(d_rots, 'd_rots', T, (n, 6)), _ptrs(d_transs, 'd_transs', T, (n, 3)), _mats(rot0, n, (3, 3), 'rot0'),
+        _mats(trans0, n, (3,), 'trans0'), _ptrs(rots, 'rots', T, (n, 3, 3)), _ptrs(transs, 'transs', T, (n, 3)),
+        _ptrs(g_rots, 'g_rots', T, (n, 3, 3), optional=True), _ptrs(g_transs, 'g_transs', T, (n, 3), optional=True),
+        None if sums is None else sums.data_ptr(), h, w, flags, int(label_mode) & 2, _ptrs(g_dr, 'g_d_rot'),
+        _ptrs(g_dt, 'g_d_trans'), T, n, _stream()), 'scf_pose_tail_grad')
+    return g_dr, g_dt
 
 
 def convex_upsample(x: Tensor, mask: Tensor, scale: int = 8, x_mul: float = 1.0,

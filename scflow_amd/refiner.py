@@ -378,6 +378,14 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         transfer.  The network itself has no backward yet."""
         return self._loss(data_batch, data, True)
 
+    def loss_and_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_grads()`` carried through the parameter-free tail of every iteration -> (loss, None, log_vars,
+        seq_rotations, seq_translations, grads): ``grads`` maps ``delta_flow_preds``, ``masks`` (the post-sigmoid map),
+        ``delta_rotation_preds`` and ``delta_translation_preds`` to the list of d loss / d head output per iteration
+        (``SCFlowDecoder.tail_backward`` on the gradients ``loss_and_grads()`` returns).  The values are the bits of
+        ``loss()`` and ``log_vars`` still costs one transfer.  The heads, the GRU and the encoders have no backward yet."""
+        return self._loss(data_batch, data, 'head')
+
     def _loss(self, data_batch, data, with_grads):
         from . import losses as L
         self._build_loss_funcs()
@@ -419,12 +427,16 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             grads['seq_rotations'] = pose_out[2][0]
             if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
                 grads['seq_translations'] = pose_out[2][1]
+        if with_grads == 'head':
+            grads = self.decoder.tail_backward(outs, grads, data['ref_rotations'], data['ref_translations'],
+                                               data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
         return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:
             raise NotImplementedError('train_step and the backward of the network are not implemented; loss_and_grads() '
-                                      'returns the loss values and their gradients at the network outputs')
+                                      'returns the loss values and their gradients at the network outputs, '
+                                      'loss_and_head_grads() carries them to the head outputs of every iteration')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
