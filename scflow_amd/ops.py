@@ -1178,15 +1178,30 @@ def group_norm_relu(x: Tensor, gamma: Tensor, beta: Tensor, groups: int, eps: fl
     return out
 
 
+def _fc_weight(weight: Tensor, k: int, bias: Optional[Tensor], what: str) -> int:
+    """out_features of a 2-D (O, k) weight whose optional bias has O entries: the kernels index both by these sizes."""
+    if weight.dim() != 2 or weight.shape[1] != k:
+        raise _lib.ScflowHipError(f'{what}: weight must be 2-D (out_features, {k}), got {tuple(weight.shape)}')
+    _fc_vector(bias, weight.shape[0], what, 'bias')
+    return weight.shape[0]
+
+
+def _fc_vector(t: Optional[Tensor], n: int, what: str, name: str, at_least: bool = False) -> None:
+    if t is not None and (t.numel() < n if at_least else t.numel() != n):
+        raise _lib.ScflowHipError(f'{what}: {name} has {t.numel()} entries, the kernel reads {n}')
+
+
 def linear(x: Tensor, weight: Tensor, bias: Optional[Tensor], act: int = ACT_NONE,
            out: Optional[Tensor] = None) -> Tensor:
     px = _dense(x, 'x')
+    if x.dim() != 2:
+        raise _lib.ScflowHipError('linear: x must be (N, K)')
     n, k = x.shape
-    o = weight.shape[0]
-    if weight.shape[1] != k:
-        raise _lib.ScflowHipError('linear: weight/in_features mismatch')
+    o = _fc_weight(weight, k, bias, 'linear')
     if out is None:
         out = torch.empty((n, o), dtype=torch.float32, device=x.device)
+    elif out.shape != (n, o):
+        raise _lib.ScflowHipError(f'linear: out must be ({n}, {o}), got {tuple(out.shape)}')
     _lib.check(_lib.load().scf_linear(px, _dense(weight, 'weight'), _opt(bias, 'bias'),
                                       _dense(out, 'out'), n, k, o, act, _stream()), 'scf_linear')
     return out
@@ -1214,14 +1229,19 @@ def fc_splitk(x: Tensor, weight: Tensor, bias: Optional[Tensor] = None, *, x_bia
     if x.dim() != 3 or not x.is_contiguous():
         raise _lib.ScflowHipError('fc_splitk: x must be a contiguous (N, K) or (parts, N, K) tensor')
     parts, n, k = x.shape
-    o = weight.shape[0]
-    if weight.shape[1] != k or (weight2 is not None and weight2.shape[1] != k):
-        raise _lib.ScflowHipError('fc_splitk: weight / in_features mismatch')
+    o = _fc_weight(weight, k, bias, 'fc_splitk')
+    if weight2 is not None:
+        _fc_weight(weight2, k, bias2, 'fc_splitk (weight2)')
+    _fc_vector(x_bias, k, 'fc_splitk', 'x_bias')
     d = _lib.FcDesc()
     d.x, d.x_parts, d.x_part_stride = x.data_ptr(), parts, n * k
     d.x_bias, d.x_relu = _opt(x_bias, 'x_bias'), int(bool(x_relu))
     if gn is not None:
         groups, hw, gamma, beta, eps = gn
+        if hw <= 0:
+            raise _lib.ScflowHipError('fc_splitk: gn hw must be positive')
+        _fc_vector(gamma, -(-k // hw), 'fc_splitk', 'gamma', at_least=True)       # channel of feature f: f // hw
+        _fc_vector(beta, -(-k // hw), 'fc_splitk', 'beta', at_least=True)
         d.gn_groups, d.gn_hw, d.gn_gamma, d.gn_beta, d.gn_eps = groups, hw, _dense(gamma, 'gamma'), _dense(beta, 'beta'), eps
     d.N, d.K = n, k
     y = torch.empty((slices, n, o) if slices > 1 else (n, o), dtype=torch.float32, device=x.device)
@@ -1239,9 +1259,11 @@ def linear_pair(x: Tensor, w1: Tensor, b1: Optional[Tensor], w2: Tensor, b2: Opt
                 act: int = ACT_NONE) -> Tuple[Tensor, Tensor]:
     """(linear(x, w1, b1), linear(x, w2, b2)) in one launch (scf_linear_pair)."""
     px = _dense(x, 'x')
+    if x.dim() != 2:
+        raise _lib.ScflowHipError('linear_pair: x must be (N, K)')
     n, k = x.shape
-    if w1.shape[1] != k or w2.shape[1] != k:
-        raise _lib.ScflowHipError('linear_pair: weight/in_features mismatch')
+    _fc_weight(w1, k, b1, 'linear_pair (w1)')
+    _fc_weight(w2, k, b2, 'linear_pair (w2)')
     y1 = torch.empty((n, w1.shape[0]), dtype=torch.float32, device=x.device)
     y2 = torch.empty((n, w2.shape[0]), dtype=torch.float32, device=x.device)
     _lib.check(_lib.load().scf_linear_pair(px, _dense(w1, 'w1'), _opt(b1, 'b1'), y1.data_ptr(),
