@@ -896,6 +896,57 @@ int scf_pose_tail_grad(const float* const* d_rot, const float* const* d_trans, c
                        const void* reproject_sums, int H, int W, int flags, int label_mode, float* const* g_d_rot,
                        float* const* g_d_trans, int T, int N, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Backward of the pose head's fully connected tail (pose_head.py:151-172, 201-211): from d loss / d (delta_rotation,
+ * delta_translation) to d loss / d (raw output of the last convolution) and to the gradients of fc1, fc2, the two heads
+ * and the last GroupNorm's affine.  The weights are shared by the T iterations of a pass: the caller stacks the
+ * iterations, M = T N rows (row m = iteration m / N, sample m % N), and every entry is one launch over all of them
+ * (scf_group_norm_flat_grad: two).  None allocates, synchronises or reads back; none uses atomics; every sum has one
+ * order fixed by the shapes (fc_grad.hip), so results are bit-identical from run to run.  ReLU masks are `a > 0` on the
+ * activations the forward computed: a NaN activation is 0 (the forward's fmaxf / v > 0 ? v : 0) and passes no gradient.
+ * Added without a version bump; the presence of scf_fc_dgrad marks the feature.
+ * --------------------------------------------------------------------------------- */
+
+/* The operand an scf_fc_splitk launch contracted, as a finished (M, K) matrix in the launch's own bits: the in-order
+ * sum of `parts` tensors part_stride floats apart, + x_bias (may be NULL), ReLU if x_relu; gn_groups > 0: then
+ * GroupNorm(gn_groups, gn_eps, affine) + ReLU over groups of K / gn_groups (even) consecutive features, channel of
+ * feature k = k / gn_hw, in the arithmetic and operation order of the forward's fold. */
+int scf_fc_operand(const float* x, int parts, int64_t part_stride, const float* x_bias, int x_relu, int gn_groups,
+                   int gn_hw, const float* gn_gamma, const float* gn_beta, float gn_eps, float* out, int M, int K,
+                   scf_stream_t stream);
+
+/* rotation_pred | translation_pred and the class selection, backward.  Class of row m: label[0], or label[m % N] under
+ * SCF_POSE_LABEL_PER_SAMPLE, clamped as scf_pose_update clamps it.  g_rot (M, 6), g_trans (M, 3), Wr (6 num_class, K),
+ * Wt (3 num_class, K), a (M, K): the heads' input (fc2's activation).
+ *   g_s (M, K) = (g_rot . Wr[6c : 6c + 6] + g_trans . Wt[3c : 3c + 3]) * [a > 0]   (a NULL: no mask; g_s NULL: skipped)
+ *   dWr[6c + r] = sum over the rows of class c, ascending, of g_rot[m][r] a[m],  dbr[6c + r] = sum g_rot[m][r], and the
+ *   same for dWt / dbt (all four or none).  Rows of classes no row selected: exact zeros, or untouched under accumulate.
+ * Plain fp32, no contraction: nine products added in the order r = 0..5 (rotation), 0..2 (translation). */
+int scf_pose_select_grad(const float* g_rot, const float* g_trans, const float* Wr, const float* Wt, const float* a,
+                         const int64_t* label, int N, int num_class, int label_mode, float* g_s, float* dWr,
+                         float* dbr, float* dWt, float* dbt, int accumulate, int M, int K, scf_stream_t stream);
+
+/* g_s (M, K) = (g (M, O) . W (O, K)) * [a > 0]  (a (M, K), NULL: no mask): nn.Linear's input gradient, W row-major
+ * (O, K) like nn.Linear.weight, contracted over O on the matrix cores in one fma chain per output, o ascending.  A
+ * row of g_s depends on that row of g (and of a) alone, whatever M is. */
+int scf_fc_dgrad(const float* g, const float* W, const float* a, float* g_s, int M, int O, int K, scf_stream_t stream);
+
+/* dW (O, K) = sum_m g[m][o] a[m][k],  db (O) = sum_m g[m][o] (db may be NULL): nn.Linear's parameter gradients,
+ * contracted over the M rows on the matrix cores.  Rows go in ascending chunks of 32: a chunk's chain starts at +0, the
+ * chunk partials are added in ascending order.  accumulate != 0: the sum is added to what dW / db hold. */
+int scf_fc_wgrad(const float* g, const float* a, float* dW, float* db, int M, int O, int K, int accumulate,
+                 scf_stream_t stream);
+
+/* GroupNorm(groups, eps, affine) + ReLU on the flattened (C, hw) map, backward.  y: the raw input in parts form (as
+ * scf_fc_operand's x), x0 (M, K): the forward's output (the mask is x0 > 0), g_x0 (M, K).  With mean, rstd recomputed
+ * from y in fp32 (two passes), xh = (y - mean) rstd, g_u = g_x0 [x0 > 0], t = gamma[k / hw] g_u:
+ *   g_y = rstd (t - mean_g(t) - xh mean_g(t xh)),   dbeta[c] = sum g_u,   dgamma[c] = sum g_u xh   over rows and hw
+ * (dgamma / dbeta: both or neither; accumulate as above).  K % groups == 0, K / groups even, any hw.
+ * stats: 2 M groups floats of device memory (mean, rstd per row and group; written, then read by the parameter pass). */
+int scf_group_norm_flat_grad(const float* g_x0, const float* y, int y_parts, int64_t y_part_stride, const float* x0,
+                             const float* gamma, int groups, int hw, float eps, float* g_y, float* dgamma,
+                             float* dbeta, int accumulate, float* stats, int M, int K, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

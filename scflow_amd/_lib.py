@@ -288,6 +288,14 @@ SIGNATURES = {
     'scf_pose_tail_grad': (C.c_int, [C.POINTER(_fp), C.POINTER(_fp), _fp, _fp, C.POINTER(_fp), C.POINTER(_fp), C.POINTER(_fp),
                                      C.POINTER(_fp), _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_fp), C.POINTER(_fp),
                                      C.c_int, C.c_int, _fp]),
+    'scf_fc_operand': (C.c_int, [_fp, C.c_int, C.c_int64, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, C.c_float, _fp,
+                                 C.c_int, C.c_int, _fp]),
+    'scf_pose_select_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp, _fp, _fp, _fp, _fp,
+                                       C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_fc_dgrad': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_fc_wgrad': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_group_norm_flat_grad': (C.c_int, [_fp, _fp, C.c_int, C.c_int64, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp,
+                                           _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),

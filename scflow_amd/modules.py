@@ -578,6 +578,113 @@ class MultiClassPoseHead(HipModule):
                                              self.translation_pred.weight, self.translation_pred.bias)
         return rot_all, trans_all
 
+    def tail_input(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tensor:
+        """What ``features()`` computes up to and including the last convolution: its raw output ``y`` (N, 128, h', w'), or
+        the (S, N, 128, h', w') partial tensors of a K-sliced launch -- the input of the fully connected tail (GroupNorm +
+        ReLU, fc1, fc2, the two heads) and all ``tail_backward`` needs of an iteration."""
+        x = self.conv_layers[0](x0, x1)
+        x = self.conv_layers[1](x)
+        last = self.conv_layers[2]
+        return ops.conv2d(last.packed, x, kslices=ops.conv_kslices_for(last.packed, x))
+
+    def _features_from_tail_input(self, y: Tensor) -> Tuple[Tensor, Tensor]:
+        """``features()`` from ``tail_input()``'s result on: the same launches in the same order, so the same bits, without
+        running the convolutions a second time (the decoder's loop under ``keep_pose_tail_input``)."""
+        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
+        ks = y.shape[0] if y.dim() == 5 else 1
+        n, hw = y.shape[-4], y.shape[-2] * y.shape[-1]
+        feat = y.shape[-3] * hw
+        s1, s2 = self.fc_plan()
+        if s1:
+            if feat != fc1.in_features:
+                raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {feat}')
+            yv = y.view(ks, n, feat) if ks > 1 else y.view(n, feat)
+            p1 = ops.fc_splitk(yv, fc1.weight, gn=(last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps), slices=s1)
+            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
+            return ops.fc_splitk(p2, self.rotation_pred.weight, self.rotation_pred.bias, x_bias=fc2.bias, x_relu=True,
+                                 weight2=self.translation_pred.weight, bias2=self.translation_pred.bias)
+        x = ops.group_norm_relu(y, last.gn.weight, last.gn.bias, last.groups, last.gn.eps)
+        x = x.view(x.shape[0], -1)
+        for fc in self.fc_layers:
+            x = ops.linear(x, fc[0].weight, fc[0].bias, ACT_RELU)
+        return ops.linear_pair(x, self.rotation_pred.weight, self.rotation_pred.bias,
+                               self.translation_pred.weight, self.translation_pred.bias)
+
+    def _tail_activations(self, y: Tensor, m: int) -> Tuple[Tensor, Tensor, Tensor]:
+        """(x0, a1, a2) of the stacked tail inputs ``y`` (parts, M, C, h, w), by the route -- and so in the bits -- of
+        ``features()``."""
+        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
+        hw = y.shape[-2] * y.shape[-1]
+        feat = y.shape[-3] * hw
+        s1, s2 = self.fc_plan()
+        if s1:
+            yv = y.view(y.shape[0], m, feat)
+            gn = (last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps)
+            x0 = ops.fc_operand(yv, gn=gn)
+            p1 = ops.fc_splitk(yv, fc1.weight, gn=gn, slices=s1)
+            a1 = ops.fc_operand(p1, x_bias=fc1.bias, x_relu=True)
+            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
+            return x0, a1, ops.fc_operand(p2, x_bias=fc2.bias, x_relu=True)
+        x0 = ops.group_norm_relu(y if y.shape[0] > 1 else y[0], last.gn.weight, last.gn.bias, last.groups, last.gn.eps)
+        x0 = x0.view(m, feat)
+        a1 = ops.linear(x0, fc1.weight, fc1.bias, ACT_RELU)
+        return x0, a1, ops.linear(a1, fc2.weight, fc2.bias, ACT_RELU)
+
+    def tail_backward(self, ys: Sequence[Tensor], label: Tensor, g_delta_rotations: Sequence[Tensor],
+                      g_delta_translations: Sequence[Tensor], label_mode: Optional[int] = None,
+                      param_grads: Optional[dict] = None) -> Tuple[list, dict]:
+        """Backward of the fully connected tail for the T iterations of a pass at once.  ``ys``: ``tail_input()`` of every
+        iteration; ``g_delta_rotations`` (N, 6) / ``g_delta_translations`` (N, 3): the cotangents of ``forward()``'s outputs
+        (what ``SCFlowDecoder.tail_backward`` returns).  -> (``g_ys``: T tensors (N, 128, h', w'), the cotangent at the last
+        convolution's raw output; ``param_grads``: the gradients of ``conv_layers.2.gn``, ``fc_layers``, ``rotation_pred``
+        and ``translation_pred``, summed over all T N rows, keyed as in ``named_parameters()``).  A dict passed in is
+        accumulated into (entries it lacks are created).
+
+        The ReLU masks are ``a > 0`` on the activations recomputed from ``ys`` by the route ``features()`` takes (both
+        ``fused_fc`` settings, any geometry), so they are the forward's.  Shipped geometry (fused route): 12 library launches
+        -- ``scf_fc_operand`` x 3 and ``scf_fc_splitk`` x 2 (the activations), ``scf_pose_select_grad``, ``scf_fc_wgrad`` x 2,
+        ``scf_fc_dgrad`` x 2, ``scf_group_norm_flat_grad`` (2 kernels) -- after three copies that stack the T iterations
+        (none for T = 1)."""
+        T = len(ys)
+        if T == 0 or T > ops.TAIL_MAX_T or len(g_delta_rotations) != T or len(g_delta_translations) != T:
+            raise _lib_error(f'tail_backward: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent pair each')
+        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
+        if last.groups is None or last.act != ACT_RELU:
+            raise _lib_error('tail_backward: the last convolution is followed by GroupNorm + ReLU')
+        if any(y.shape != ys[0].shape or y.dim() not in (4, 5) for y in ys):
+            raise _lib_error('tail_backward: ys are the (N, C, h, w) or (S, N, C, h, w) tensors of tail_input()')
+        y5 = [y if y.dim() == 5 else y.unsqueeze(0) for y in ys]
+        parts, n, c, h, w = y5[0].shape
+        if c * h * w != fc1.in_features:
+            raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {c * h * w}')
+        m = T * n
+        y = y5[0].contiguous() if T == 1 else torch.stack(y5, 1).view(parts, m, c, h, w)
+        g_rot = g_delta_rotations[0].contiguous() if T == 1 else torch.cat(list(g_delta_rotations))
+        g_trans = g_delta_translations[0].contiguous() if T == 1 else torch.cat(list(g_delta_translations))
+        mode = self.label_mode if label_mode is None else label_mode
+        x0, a1, a2 = self._tail_activations(y, m)
+
+        names = ('rotation_pred.weight', 'rotation_pred.bias', 'translation_pred.weight', 'translation_pred.bias',
+                 'fc_layers.1.0.weight', 'fc_layers.1.0.bias', 'fc_layers.0.0.weight', 'fc_layers.0.0.bias',
+                 'conv_layers.2.gn.weight', 'conv_layers.2.gn.bias')
+        grads = {} if param_grads is None else param_grads
+        have = [k in grads for k in names]
+        if any(have) and not all(have):
+            raise _lib_error('tail_backward: param_grads holds some of the tail\'s gradients but not all')
+        acc = all(have)
+        dst = [grads.get(k) for k in names]
+        g_s2, heads = ops.pose_select_grad(g_rot, g_trans, self.rotation_pred.weight, self.translation_pred.weight, a2,
+                                           label, n, mode, grads=dst[0:4] if acc else None, accumulate=acc)
+        dw2, db2 = ops.fc_wgrad(g_s2, a1, dst[4], dst[5], accumulate=acc)
+        g_s1 = ops.fc_dgrad(g_s2, fc2.weight, a1)
+        dw1, db1 = ops.fc_wgrad(g_s1, x0, dst[6], dst[7], accumulate=acc)
+        g_x0 = ops.fc_dgrad(g_s1, fc1.weight)
+        g_y, dgam, dbet = ops.group_norm_flat_grad(g_x0, y.view(parts, m, c * h * w), x0, last.gn.weight, last.groups, h * w,
+                                                   last.gn.eps, dst[8], dst[9], accumulate=acc)
+        grads.update(zip(names, (*heads, dw2, db2, dw1, db1, dgam, dbet)))
+        g_y = g_y.view(T, n, c, h, w)
+        return [g_y[t] for t in range(T)], grads
+
     def forward(self, x: Tensor, label: Tensor) -> Tuple[Tensor, Tensor]:
         """pose_head.py:201-211 -> (delta rotation (N,6), delta translation (N,3))."""
         rot_all, trans_all = self.features(x)
@@ -634,6 +741,10 @@ class SCFlowDecoder(HipModule):
         # the launch sequence of an iteration issued by ONE C call (scf_scflow_iteration) instead of
         # ~33 Python-sequenced ones: same kernels, same order, same bits; False = sequence from here
         self.c_iteration = True
+        # True: every forward leaves a copy of the pose head's tail input (MultiClassPoseHead.tail_input) of each
+        # iteration in pose_tail_inputs, what MultiClassPoseHead.tail_backward needs; False: nothing is kept or launched
+        self.keep_pose_tail_input = False
+        self.pose_tail_inputs = []
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -662,6 +773,8 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
+        if self.keep_pose_tail_input:
+            self.pose_tail_inputs = []
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
         # GRU buffer [h | cxt | motion(126) | flow(2)]: the caller's own buffer only when the
@@ -716,7 +829,11 @@ class SCFlowDecoder(HipModule):
             with br:
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
-            rot_all, trans_all = self.pose_pred.features(hv, dm)                   # :218-219
+            if self.keep_pose_tail_input:      # features() in two steps, the launches and their order unchanged
+                self.pose_tail_inputs.append(self.pose_pred.tail_input(hv, dm))
+                rot_all, trans_all = self.pose_pred._features_from_tail_input(self.pose_tail_inputs[-1])
+            else:
+                rot_all, trans_all = self.pose_pred.features(hv, dm)               # :218-219
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
                 self.pose_flags())
@@ -872,6 +989,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.gn[i].C, it.gn[i].HW, it.gn[i].G, it.gn[i].eps = y.shape[-3], y.shape[-2] * y.shape[-1], blk.groups, blk.gn.eps
         keep += [y, g]
         x0, x1 = g, None
+    tail_input = y                  # the last convolution's raw output: rewritten by every iteration
     fc1, fc2 = ph.fc_layers[0][0], ph.fc_layers[1][0]
     if fc1.in_features != x0[0].numel():
         raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {x0[0].numel()}')
@@ -905,6 +1023,8 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
+        if self.keep_pose_tail_input:
+            self.pose_tail_inputs.append(tail_input.clone())
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already

@@ -30,6 +30,7 @@ __all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scfl
            'instance_norm', 'group_norm_relu', 'linear', 'fc_splitk', 'fc_slices', 'pose_update', 'reproject_flow',
            'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
            'unproject_depth', 'linear_pair', 'resize_bilinear', 'resize_bilinear_grad', 'reproject_flow_grad', 'pose_update_grad', 'convex_upsample', 'avgpool2x2', 'copy_channels',
+           'fc_operand', 'fc_dgrad', 'fc_wgrad', 'pose_select_grad', 'group_norm_flat_grad',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_TANH', 'CONV_PLAIN', 'CONV_GRU_ZR',
            'CONV_GRU_Q']
 
@@ -2000,3 +2001,149 @@ def copy_channels(src: Tensor, dst: Tensor) -> Tensor:
     _lib.check(_lib.load().scf_copy_strided(ps, ss, pd, sd, n, c * h * w, _stream()),
                'scf_copy_strided')
     return dst
+
+
+# ------------------------------------------------- backward of the pose head's fully connected tail (fc_grad.hip)
+def _fc_matrix(t: Tensor, what: str, name: str, shape=None) -> Tuple[int, int]:
+    _dev(t, f'{what}: {name}')
+    if t.dim() != 2 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = 'a contiguous 2-D tensor' if shape is None else f'a contiguous {tuple(shape)} tensor'
+        raise _lib.ScflowHipError(f'{what}: {name} must be {want}, got {tuple(t.shape)}')
+    return t.shape[0], t.shape[1]
+
+
+def _fc_parts(x: Tensor, what: str, name: str) -> Tuple[Tensor, int, int, int]:
+    _dev(x, f'{what}: {name}')
+    if x.dim() == 2:
+        x = x.unsqueeze(0)
+    if x.dim() != 3 or not x.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: {name} must be a contiguous (M, K) or (parts, M, K) tensor')
+    return (x,) + tuple(x.shape)
+
+
+def _fc_grad_out(out: Optional[Tensor], shape, like: Tensor, what: str, name: str, accumulate: bool = False) -> Tensor:
+    if out is None:
+        if accumulate:
+            raise _lib.ScflowHipError(f'{what}: accumulate needs {name}')
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    _dev(out, f'{what}: {name}')
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: {name} must be a contiguous {tuple(shape)} tensor, got {tuple(out.shape)}')
+    return out
+
+
+def fc_operand(x: Tensor, x_bias: Optional[Tensor] = None, x_relu: bool = False, gn=None,
+               out: Optional[Tensor] = None) -> Tensor:
+    """The (M, K) operand an ``fc_splitk`` launch with the same ``x``, ``x_bias``, ``x_relu``, ``gn`` contracted, in that
+    launch's bits (``scf_fc_operand``)."""
+    x, parts, m, k = _fc_parts(x, 'fc_operand', 'x')
+    _fc_vector(x_bias, k, 'fc_operand', 'x_bias')
+    groups, hw, gamma, beta, eps = 0, 1, None, None, 0.0
+    if gn is not None:
+        groups, hw, gamma, beta, eps = gn
+        if hw <= 0 or groups <= 0:
+            raise _lib.ScflowHipError('fc_operand: gn groups and hw must be positive')
+        _fc_vector(gamma, -(-k // hw), 'fc_operand', 'gamma', at_least=True)
+        _fc_vector(beta, -(-k // hw), 'fc_operand', 'beta', at_least=True)
+    out = _fc_grad_out(out, (m, k), x, 'fc_operand', 'out')
+    _lib.check(_lib.load().scf_fc_operand(x.data_ptr(), parts, m * k, _opt(x_bias, 'x_bias'), int(bool(x_relu)), groups, hw,
+                                          _opt(gamma, 'gamma'), _opt(beta, 'beta'), eps, out.data_ptr(), m, k, _stream()),
+               'scf_fc_operand')
+    return out
+
+
+def fc_dgrad(g: Tensor, weight: Tensor, a: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """``(g (M, O) @ weight (O, K)) * [a > 0]`` -> (M, K) (``scf_fc_dgrad``; ``a`` None: no mask)."""
+    m, o = _fc_matrix(g, 'fc_dgrad', 'g')
+    _fc_matrix(weight, 'fc_dgrad', 'weight')
+    if weight.shape[0] != o:
+        raise _lib.ScflowHipError(f'fc_dgrad: weight must be ({o}, K), got {tuple(weight.shape)}')
+    k = weight.shape[1]
+    if a is not None:
+        _fc_matrix(a, 'fc_dgrad', 'a', (m, k))
+    out = _fc_grad_out(out, (m, k), g, 'fc_dgrad', 'out')
+    _lib.check(_lib.load().scf_fc_dgrad(g.data_ptr(), weight.data_ptr(), _opt(a, 'a'), out.data_ptr(), m, o, k, _stream()),
+               'scf_fc_dgrad')
+    return out
+
+
+def fc_wgrad(g: Tensor, a: Tensor, dw: Optional[Tensor] = None, db: Optional[Tensor] = None, bias: bool = True,
+             accumulate: bool = False) -> Tuple[Tensor, Optional[Tensor]]:
+    """``(g^T @ a (O, K), g.sum(0) (O))`` (``scf_fc_wgrad``); ``accumulate``: added to ``dw`` / ``db``.  ``bias=False``: no
+    ``db``."""
+    m, o = _fc_matrix(g, 'fc_wgrad', 'g')
+    _fc_matrix(a, 'fc_wgrad', 'a')
+    if a.shape[0] != m:
+        raise _lib.ScflowHipError(f'fc_wgrad: a must be ({m}, K), got {tuple(a.shape)}')
+    k = a.shape[1]
+    dw = _fc_grad_out(dw, (o, k), g, 'fc_wgrad', 'dw', accumulate)
+    if bias or db is not None:
+        db = _fc_grad_out(db, (o,), g, 'fc_wgrad', 'db', accumulate)
+    _lib.check(_lib.load().scf_fc_wgrad(g.data_ptr(), a.data_ptr(), dw.data_ptr(), _opt(db, 'db'), m, o, k,
+                                        int(bool(accumulate)), _stream()), 'scf_fc_wgrad')
+    return dw, db
+
+
+def pose_select_grad(g_rot: Tensor, g_trans: Tensor, w_rot: Tensor, w_trans: Tensor, a: Tensor, label: Tensor,
+                     samples: int, label_mode: int = 0, mask: bool = True, grads=None, accumulate: bool = False):
+    """``scf_pose_select_grad``: ``g_rot`` (M, 6), ``g_trans`` (M, 3) (row m = iteration m // samples, sample m % samples),
+    the heads' weights and input ``a`` (M, K) -> (g_s (M, K), (dWr, dbr, dWt, dbt)); ``grads``: the four destinations
+    (required under ``accumulate``)."""
+    what = 'pose_select_grad'
+    m, _ = _fc_matrix(g_rot, what, 'g_rot')
+    _fc_matrix(g_rot, what, 'g_rot', (m, 6))
+    _fc_matrix(g_trans, what, 'g_trans', (m, 3))
+    _, k = _fc_matrix(a, what, 'a')
+    _fc_matrix(a, what, 'a', (m, k))
+    if w_rot.dim() != 2 or w_rot.shape[0] % 6 != 0:
+        raise _lib.ScflowHipError(f'{what}: w_rot must be (6 num_class, K), got {tuple(w_rot.shape)}')
+    nc = w_rot.shape[0] // 6
+    _fc_matrix(w_rot, what, 'w_rot', (6 * nc, k))
+    _fc_matrix(w_trans, what, 'w_trans', (3 * nc, k))
+    if samples <= 0 or m % samples != 0:
+        raise _lib.ScflowHipError(f'{what}: {m} rows are no multiple of {samples} samples')
+    if not label.is_cuda or label.dtype != torch.int64 or not label.is_contiguous() or label.numel() < (samples if label_mode & 1 else 1):
+        raise _lib.ScflowHipError('label must be a contiguous int64 GPU tensor with one entry per sample')
+    shapes = ((6 * nc, k), (6 * nc,), (3 * nc, k), (3 * nc,))
+    grads = (None,) * 4 if grads is None else tuple(grads)
+    if len(grads) != 4:
+        raise _lib.ScflowHipError(f'{what}: grads = (dWr, dbr, dWt, dbt)')
+    grads = tuple(_fc_grad_out(t, s, a, what, n, accumulate) for t, s, n in zip(grads, shapes, ('dWr', 'dbr', 'dWt', 'dbt')))
+    g_s = torch.empty((m, k), dtype=torch.float32, device=a.device)
+    lib = _lib.load()
+    head = (g_rot.data_ptr(), g_trans.data_ptr(), w_rot.data_ptr(), w_trans.data_ptr())
+    tail = (int(bool(accumulate)), m, k, _stream())
+    sel = (label.data_ptr(), samples, nc, label_mode)
+    dst = tuple(t.data_ptr() for t in grads)
+    if mask:
+        _lib.check(lib.scf_pose_select_grad(*head, a.data_ptr(), *sel, g_s.data_ptr(), *dst, *tail), 'scf_pose_select_grad')
+    else:       # two calls: the weight gradients need ``a``, the unmasked input gradient must not see it
+        _lib.check(lib.scf_pose_select_grad(*head, None, *sel, g_s.data_ptr(), None, None, None, None, *tail),
+                   'scf_pose_select_grad')
+        _lib.check(lib.scf_pose_select_grad(*head, a.data_ptr(), *sel, None, *dst, *tail), 'scf_pose_select_grad')
+    return g_s, grads
+
+
+def group_norm_flat_grad(g_x0: Tensor, y: Tensor, x0: Tensor, gamma: Tensor, groups: int, hw: int, eps: float = 1e-5,
+                         dgamma: Optional[Tensor] = None, dbeta: Optional[Tensor] = None, accumulate: bool = False,
+                         params: bool = True):
+    """``scf_group_norm_flat_grad``: ``y`` (M, K) or (parts, M, K), the forward's output ``x0`` (M, K) and its cotangent ->
+    (g_y (M, K), dgamma, dbeta) with ceil(K / hw) entries each (None with ``params=False``)."""
+    what = 'group_norm_flat_grad'
+    y, parts, m, k = _fc_parts(y, what, 'y')
+    _fc_matrix(g_x0, what, 'g_x0', (m, k))
+    _fc_matrix(x0, what, 'x0', (m, k))
+    if groups <= 0 or hw <= 0 or k % groups != 0:
+        raise _lib.ScflowHipError(f'{what}: {k} features do not split into {groups} groups of channels of {hw}')
+    c = -(-k // hw)
+    _fc_vector(gamma, c, what, 'gamma', at_least=True)
+    if params or dgamma is not None or dbeta is not None:
+        dgamma = _fc_grad_out(dgamma, (c,), y, what, 'dgamma', accumulate)
+        dbeta = _fc_grad_out(dbeta, (c,), y, what, 'dbeta', accumulate)
+    g_y = torch.empty((m, k), dtype=torch.float32, device=y.device)
+    stats = torch.empty((m, groups, 2), dtype=torch.float32, device=y.device)
+    _lib.check(_lib.load().scf_group_norm_flat_grad(g_x0.data_ptr(), y.data_ptr(), parts, m * k, x0.data_ptr(),
+                                                    _dense(gamma, 'gamma'), groups, hw, eps, g_y.data_ptr(),
+                                                    _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'), int(bool(accumulate)),
+                                                    stats.data_ptr(), m, k, _stream()), 'scf_group_norm_flat_grad')
+    return g_y, dgamma, dbeta

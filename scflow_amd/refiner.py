@@ -386,14 +386,31 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         ``loss()`` and ``log_vars`` still costs one transfer.  The heads, the GRU and the encoders have no backward yet."""
         return self._loss(data_batch, data, 'head')
 
+    def loss_and_pose_tail_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_head_grads()`` carried through the fully connected tail of the pose head -> the same tuple, ``grads``
+        with two more keys: ``pose_tail_inputs``, the list of d loss / d (raw output of the pose head's last convolution)
+        per iteration, and ``params``, the gradients of that tail's parameters (``decoder.pose_pred.conv_layers.2.gn``,
+        ``.fc_layers``, ``.rotation_pred``, ``.translation_pred``; keys as in ``named_parameters()``) summed over the
+        iterations (``MultiClassPoseHead.tail_backward``).  The values are the bits of ``loss()``, the head-output
+        gradients those of ``loss_and_head_grads()``.  ``delta_flow_preds`` / ``masks`` are NOT yet complete gradients: they
+        still lack the contribution that reaches them through the pose head's convolutions and the delta-flow / mask
+        encoders, whose backward (like the XHeads', the GRU's, the lookup's and the encoders') does not exist yet."""
+        return self._loss(data_batch, data, 'pose_tail')
+
     def _loss(self, data_batch, data, with_grads):
         from . import losses as L
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
-        outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
-                             data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
+        dec = self.decoder
+        kept = dec.keep_pose_tail_input
+        dec.keep_pose_tail_input = kept or with_grads == 'pose_tail'
+        try:
+            outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
+                                 data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
+        finally:
+            dec.keep_pose_tail_input = kept
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
@@ -427,16 +444,23 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             grads['seq_rotations'] = pose_out[2][0]
             if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
                 grads['seq_translations'] = pose_out[2][1]
-        if with_grads == 'head':
+        if with_grads in ('head', 'pose_tail'):
             grads = self.decoder.tail_backward(outs, grads, data['ref_rotations'], data['ref_translations'],
                                                data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
+        if with_grads == 'pose_tail':
+            head = dec.pose_pred
+            g_ys, params = head.tail_backward(dec.pose_tail_inputs, labels, grads['delta_rotation_preds'],
+                                              grads['delta_translation_preds'])
+            grads['pose_tail_inputs'] = g_ys
+            grads['params'] = {'decoder.pose_pred.' + key: val for key, val in params.items()}
         return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:
             raise NotImplementedError('train_step and the backward of the network are not implemented; loss_and_grads() '
                                       'returns the loss values and their gradients at the network outputs, '
-                                      'loss_and_head_grads() carries them to the head outputs of every iteration')
+                                      'loss_and_head_grads() carries them to the head outputs of every iteration, '
+                                      'loss_and_pose_tail_grads() through the fully connected tail of the pose head')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
