@@ -947,6 +947,39 @@ int scf_group_norm_flat_grad(const float* g_x0, const float* y, int y_parts, int
                              const float* gamma, int groups, int hw, float eps, float* g_y, float* dgamma,
                              float* dbeta, int accumulate, float* stats, int M, int K, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Backward of the pose head's convolutions (pose_head.py:131-149: three 3x3 / stride-2 / pad-1 ConvModules without bias):
+ * the input gradient and the weight gradient of one layer, fp32 on v_mfma_f32_32x32x2_f32.  The weights are shared by the
+ * T iterations of a pass: the caller stacks them, M = T N samples, and dgrad is one launch over all of them, wgrad two
+ * (the second combines the partial sums).  Neither allocates, synchronises or reads back; neither uses atomics; every sum
+ * has one order fixed by the shapes (conv_grad.hip), so results are bit-identical from run to run.
+ * Geometry: KH = KW = 3, stride 2, pad 1, any Hin, Win >= 1 with Ho = (Hin - 1) / 2 + 1, Wo = (Win - 1) / 2 + 1; another
+ * kernel, stride or padding: SCF_EUNSUPPORTED; sizes that do not belong together, a missing pointer: SCF_EINVAL; both with
+ * nothing launched.  w and dW are the raw (Cout, C0 + C1, 3, 3) parameter in the torch layout, not a packed weight.
+ * Added without a version bump; the presence of scf_conv_dgrad marks the feature.
+ * --------------------------------------------------------------------------------- */
+
+/* g (M, Cout, Ho, Wo) -> the input gradient, written whole as two dense tensors gx0 (M, C0, Hin, Win) and gx1 (M, C1,
+ * Hin, Win), the two parts the forward read (gx1 NULL <=> C1 = 0).  Only the taps that meet an output pixel are
+ * computed (1, 2, 2 or 4 of the 9, by the parity of (iy, ix)): 9 Cout Cin multiply-adds per 2 x 2 input pixels.  Per
+ * element ONE fma chain from +0: the contributing taps in ascending (ky, kx), inside a tap co ascending (padded with
+ * zeros to a multiple of 32; a tap that leaves the output map at the far border of an even-sized input contributes
+ * zeros).  A sample's result depends on that sample alone, whatever M is. */
+int scf_conv_dgrad(const float* g, const float* w, float* gx0, int C0, float* gx1, int C1, int M, int Cout, int Ho,
+                   int Wo, int Hin, int Win, int KH, int KW, int stride, int pad, scf_stream_t stream);
+
+/* dW[co][ci][ky][kx] = sum_{m, oy, ox} g[m, co, oy, ox] x[m, ci, 2 oy - 1 + ky, 2 ox - 1 + kx]  (zero outside the map), x
+ * in two parts x0 (M, C0, Hin, Win), x1 (M, C1, Hin, Win) (x1 NULL <=> C1 = 0).  The contraction over the M Ho Wo output
+ * pixels, (m, oy, ox) row-major, is cut into S splits of consecutive pixels (conv_grad.hip: cg_wgrad_plan); a split is
+ * ONE fma chain from +0 per element, pixels ascending, written to workspace[s][tap][co][ci]; the second launch takes
+ * partial 0, adds partials 1 .. S - 1 in ascending order and, with accumulate != 0, the previous value of dW last.
+ * workspace: scf_conv_wgrad_workspace(M, Cout, C0 + C1, Ho, Wo) floats of device memory (-1: invalid sizes); fewer:
+ * SCF_EINVAL.  The pose head's convolutions have no bias, so there is no bias gradient. */
+int64_t scf_conv_wgrad_workspace(int M, int Cout, int Cin, int Ho, int Wo);
+int scf_conv_wgrad(const float* g, const float* x0, int C0, const float* x1, int C1, float* dW, int accumulate,
+                   float* workspace, int64_t workspace_floats, int M, int Cout, int Ho, int Wo, int Hin, int Win, int KH,
+                   int KW, int stride, int pad, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

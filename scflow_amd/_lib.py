@@ -296,6 +296,11 @@ SIGNATURES = {
     'scf_fc_wgrad': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_group_norm_flat_grad': (C.c_int, [_fp, _fp, C.c_int, C.c_int64, _fp, _fp, C.c_int, C.c_int, C.c_float, _fp, _fp,
                                            _fp, C.c_int, _fp, C.c_int, C.c_int, _fp]),
+    'scf_conv_dgrad': (C.c_int, [_fp, _fp, _fp, C.c_int, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_conv_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_conv_wgrad': (C.c_int, [_fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
+                                 C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),

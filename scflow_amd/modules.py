@@ -587,6 +587,103 @@ class MultiClassPoseHead(HipModule):
         last = self.conv_layers[2]
         return ops.conv2d(last.packed, x, kslices=ops.conv_kslices_for(last.packed, x))
 
+    def _conv_outputs(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
+        """``tail_input()`` that also hands out the raw outputs of the first two convolutions: (y0, y1, y2), each
+        (N, 128, h', w') or the (S, N, 128, h', w') partial tensors of a K-sliced launch.  The launches of ``features()`` up
+        to the last convolution, in its order: the same bits."""
+        ys, x = [], x0
+        for i, blk in enumerate(self.conv_layers):
+            xb = x1 if i == 0 else None
+            y = ops.conv2d(blk.packed, x, xb, kslices=ops.conv_kslices_for(blk.packed, x, xb))
+            ys.append(y)
+            if i < 2:
+                x = ops.group_norm_relu(y, blk.gn.weight, blk.gn.bias, blk.groups, blk.gn.eps)
+        return tuple(ys)
+
+    def conv_backward(self, saved: dict, g_ys: Sequence[Tensor], param_grads: Optional[dict] = None
+                      ) -> Tuple[list, list, dict]:
+        """Backward of the three 3x3 / stride-2 convolutions with GroupNorms 0 and 1 for the T iterations of a pass at
+        once.  ``saved``: what a forward under ``SCFlowDecoder.keep_pose_head_input`` left in ``pose_head_inputs`` (``hv``
+        (T, N, 128, h, w), ``dm`` (T, N, 96, h, w), the raw convolution outputs ``y0``, ``y1`` as (S, T, N, 128, h', w')
+        partial tensors); ``g_ys``: what ``tail_backward`` returns.  -> (``g_x0s``, ``g_x1s``: T tensors each, the cotangents
+        at ``hv`` and at ``dm``; ``param_grads``: the gradients of ``conv_layers.{0,1,2}.conv.weight`` and
+        ``conv_layers.{0,1}.gn.{weight,bias}`` summed over all T N samples, keyed as in ``named_parameters()``).  A dict
+        passed in is accumulated into (entries it lacks are created; some but not all of these entries: an error).
+
+        The activations a0, a1 -- wgrad operands and, as ``a > 0``, the ReLU masks -- are recomputed from the saved raw
+        outputs by the forward's own ``scf_group_norm_relu_parts`` (one block per sample and group: the forward's bits at
+        any batch).  Launches: two GroupNorm forwards, then wgrad 2, dgrad 2, GroupNorm-1 grad, wgrad 1, dgrad 1,
+        GroupNorm-0 grad, wgrad 0, dgrad 0 (a wgrad is two kernels, a GroupNorm grad two), after one copy that stacks
+        ``g_ys`` (none for T = 1)."""
+        T = len(g_ys)
+        if T == 0 or T > ops.TAIL_MAX_T:
+            raise _lib_error(f'conv_backward: 1 .. {ops.TAIL_MAX_T} iterations')
+        L0, L1, L2 = self.conv_layers
+        for blk in (L0, L1, L2):
+            c = blk.conv
+            if blk.groups is None or blk.act != ACT_RELU or c.bias is not None or tuple(c.kernel_size) != (3, 3) or \
+                    tuple(c.stride) != (2, 2) or tuple(c.padding) != (1, 1):
+                raise _lib_error('conv_backward: 3x3 / stride-2 / pad-1 convolutions without bias, GroupNorm + ReLU')
+        try:
+            hv, dm, y0, y1 = (saved[k] for k in ('hv', 'dm', 'y0', 'y1'))
+        except (KeyError, TypeError):
+            raise _lib_error('conv_backward: saved is SCFlowDecoder.pose_head_inputs (hv, dm, y0, y1)') from None
+        if hv.dim() != 5 or dm.dim() != 5 or hv.shape[0] != T or dm.shape[0] != T or hv.shape[1] != dm.shape[1] or \
+                hv.shape[3:] != dm.shape[3:] or hv.shape[2] + dm.shape[2] != L0.conv.in_channels or \
+                not hv.is_contiguous() or not dm.is_contiguous():
+            raise _lib_error(f'conv_backward: hv / dm must be contiguous ({T}, N, C, h, w) tensors of the head\'s '
+                             f'{L0.conv.in_channels} input channels')
+        n, c0, h, w = hv.shape[1:]
+        m = T * n
+        sizes = [(h, w)]
+        for _ in range(3):
+            sizes.append(((sizes[-1][0] - 1) // 2 + 1, (sizes[-1][1] - 1) // 2 + 1))
+        for name, y, blk, hw_ in (('y0', y0, L0, sizes[1]), ('y1', y1, L1, sizes[2])):
+            if y.dim() != 6 or tuple(y.shape[1:]) != (T, n, blk.conv.out_channels) + hw_ or not y.is_contiguous():
+                raise _lib_error(f'conv_backward: {name} must be a contiguous (S, {T}, {n}, {blk.conv.out_channels}, '
+                                 f'{hw_[0]}, {hw_[1]}) tensor, got {tuple(y.shape)}')
+        c2 = L2.conv.out_channels
+        if any(tuple(g.shape) != (n, c2) + sizes[3] for g in g_ys):
+            raise _lib_error(f'conv_backward: g_ys are ({n}, {c2}, {sizes[3][0]}, {sizes[3][1]}) tensors')
+        names = ('conv_layers.2.conv.weight', 'conv_layers.1.gn.weight', 'conv_layers.1.gn.bias',
+                 'conv_layers.1.conv.weight', 'conv_layers.0.gn.weight', 'conv_layers.0.gn.bias',
+                 'conv_layers.0.conv.weight')
+        grads = {} if param_grads is None else param_grads
+        have = [k in grads for k in names]
+        if any(have) and not all(have):
+            raise _lib_error('conv_backward: param_grads holds some of the convolutions\' gradients but not all')
+        acc = all(have)
+        dst = [grads.get(k) for k in names]
+
+        def act(y, blk, hw_):       # the forward's launch on the stacked samples
+            yv = y.view(y.shape[0], m, blk.conv.out_channels, *hw_)
+            return ops.group_norm_relu(yv if y.shape[0] > 1 else yv[0], blk.gn.weight, blk.gn.bias, blk.groups, blk.gn.eps)
+
+        a0, a1 = act(y0, L0, sizes[1]), act(y1, L1, sizes[2])
+        g2 = g_ys[0].contiguous() if T == 1 else torch.stack(list(g_ys)).view(m, c2, *sizes[3])
+        x0, x1 = hv.view(m, c0, h, w), dm.view(m, dm.shape[2], h, w)
+        need = max(ops.conv_wgrad_workspace(m, blk.conv.out_channels, blk.conv.in_channels, *hw_)
+                   for blk, hw_ in zip((L0, L1, L2), sizes[1:]))
+        ws = torch.empty((need,), dtype=torch.float32, device=hv.device)
+
+        def norm_grad(g_a, y, a, blk, hw_, dgam, dbet):
+            k = blk.conv.out_channels * hw_[0] * hw_[1]
+            g_y, dg, db = ops.group_norm_flat_grad(g_a.view(m, k), y.view(y.shape[0], m, k), a.view(m, k), blk.gn.weight,
+                                                   blk.groups, hw_[0] * hw_[1], blk.gn.eps, dgam, dbet, accumulate=acc)
+            return g_y.view(m, blk.conv.out_channels, *hw_), dg, db
+
+        dw2 = ops.conv_wgrad(g2, a1, dw=dst[0], accumulate=acc, workspace=ws)
+        g_a1 = ops.conv_dgrad(g2, L2.conv.weight, sizes[2])
+        g_y1, dg1, db1 = norm_grad(g_a1, y1, a1, L1, sizes[2], dst[1], dst[2])
+        dw1 = ops.conv_wgrad(g_y1, a0, dw=dst[3], accumulate=acc, workspace=ws)
+        g_a0 = ops.conv_dgrad(g_y1, L1.conv.weight, sizes[1])
+        g_y0, dg0, db0 = norm_grad(g_a0, y0, a0, L0, sizes[1], dst[4], dst[5])
+        dw0 = ops.conv_wgrad(g_y0, x0, x1, dw=dst[6], accumulate=acc, workspace=ws)
+        g_hv, g_dm = ops.conv_dgrad(g_y0, L0.conv.weight, (h, w), split=c0)
+        grads.update(zip(names, (dw2, dg1, db1, dw1, dg0, db0, dw0)))
+        g_hv, g_dm = g_hv.view(T, n, c0, h, w), g_dm.view(T, n, dm.shape[2], h, w)
+        return [g_hv[t] for t in range(T)], [g_dm[t] for t in range(T)], grads
+
     def _features_from_tail_input(self, y: Tensor) -> Tuple[Tensor, Tensor]:
         """``features()`` from ``tail_input()``'s result on: the same launches in the same order, so the same bits, without
         running the convolutions a second time (the decoder's loop under ``keep_pose_tail_input``)."""
@@ -745,6 +842,12 @@ class SCFlowDecoder(HipModule):
         # iteration in pose_tail_inputs, what MultiClassPoseHead.tail_backward needs; False: nothing is kept or launched
         self.keep_pose_tail_input = False
         self.pose_tail_inputs = []
+        # True: every forward also keeps, per iteration, what MultiClassPoseHead.conv_backward needs, in pose_head_inputs:
+        # copies of hv and dm (T, N, C, h, w) and the raw outputs y0, y1, y2 of the head's convolutions as
+        # (S, T, N, 128, h', w') partial tensors (S: the K-slices of the forward's launch); implies keep_pose_tail_input.
+        # False: nothing is kept, allocated or launched
+        self.keep_pose_head_input = False
+        self.pose_head_inputs = {}
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -773,8 +876,10 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
-        if self.keep_pose_tail_input:
+        if self.keep_pose_tail_input or self.keep_pose_head_input:
             self.pose_tail_inputs = []
+        if self.keep_pose_head_input:
+            self.pose_head_inputs = {}
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
         # GRU buffer [h | cxt | motion(126) | flow(2)]: the caller's own buffer only when the
@@ -829,7 +934,12 @@ class SCFlowDecoder(HipModule):
             with br:
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
-            if self.keep_pose_tail_input:      # features() in two steps, the launches and their order unchanged
+            if self.keep_pose_head_input:      # features() in steps, the launches and their order unchanged
+                ys = self.pose_pred._conv_outputs(hv, dm)
+                self._keep_pose_head_input(len(outs[0]), hv, dm, ys)
+                self.pose_tail_inputs.append(ys[2])
+                rot_all, trans_all = self.pose_pred._features_from_tail_input(ys[2])
+            elif self.keep_pose_tail_input:    # features() in two steps, the launches and their order unchanged
                 self.pose_tail_inputs.append(self.pose_pred.tail_input(hv, dm))
                 rot_all, trans_all = self.pose_pred._features_from_tail_input(self.pose_tail_inputs[-1])
             else:
@@ -843,6 +953,25 @@ class SCFlowDecoder(HipModule):
             for lst, v in zip(outs, (flow, flow_pred, rot, trans, up_mask, d_rot, d_trans)):
                 lst.append(v)
         return outs
+
+
+def _scflow_keep_pose_head_input(self, t: int, hv: Tensor, dm: Tensor, ys) -> None:
+    """iteration ``t`` of ``pose_head_inputs``: the buffers for all iterations are allocated by the first one."""
+    kept = self.pose_head_inputs
+    if t == 0:
+        f32 = dict(dtype=torch.float32, device=hv.device)
+        kept['hv'] = torch.empty((self.iters,) + tuple(hv.shape), **f32)
+        kept['dm'] = torch.empty((self.iters,) + tuple(dm.shape), **f32)
+        for i, y in enumerate(ys):
+            s_ = y.shape[0] if y.dim() == 5 else 1
+            kept[f'y{i}'] = torch.empty((s_, self.iters) + tuple(y.shape[-4:]), **f32)
+    kept['hv'][t].copy_(hv)
+    kept['dm'][t].copy_(dm)
+    for i, y in enumerate(ys):
+        kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
+
+
+SCFlowDecoder._keep_pose_head_input = _scflow_keep_pose_head_input
 
 
 def _scflow_tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translation: Tensor, depth: Tensor,
@@ -978,6 +1107,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
     it.denc1 = cd(self.delta_flow_encoder[1], d1, out=dm[:, :64])
     # ---- pose head ----
     x0, x1 = hv, dm
+    raw_ys = []                     # the raw outputs of the head's convolutions: rewritten by every iteration
     for i, blk in enumerate(ph.conv_layers):
         if blk.groups is None or blk.act != ACT_RELU:
             raise NotImplementedError('pose head: conv + GroupNorm + ReLU blocks')
@@ -988,6 +1118,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.gn[i].gamma, it.gn[i].beta, it.gn[i].out = blk.gn.weight.data_ptr(), blk.gn.bias.data_ptr(), g.data_ptr()
         it.gn[i].C, it.gn[i].HW, it.gn[i].G, it.gn[i].eps = y.shape[-3], y.shape[-2] * y.shape[-1], blk.groups, blk.gn.eps
         keep += [y, g]
+        raw_ys.append(y)
         x0, x1 = g, None
     tail_input = y                  # the last convolution's raw output: rewritten by every iteration
     fc1, fc2 = ph.fc_layers[0][0], ph.fc_layers[1][0]
@@ -1023,7 +1154,10 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        if self.keep_pose_tail_input:
+        if self.keep_pose_head_input:
+            self._keep_pose_head_input(i, hv, dm, raw_ys)
+            self.pose_tail_inputs.append(tail_input.clone())
+        elif self.keep_pose_tail_input:
             self.pose_tail_inputs.append(tail_input.clone())
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)

@@ -2147,3 +2147,89 @@ def group_norm_flat_grad(g_x0: Tensor, y: Tensor, x0: Tensor, gamma: Tensor, gro
                                                     _opt(dgamma, 'dgamma'), _opt(dbeta, 'dbeta'), int(bool(accumulate)),
                                                     stats.data_ptr(), m, k, _stream()), 'scf_group_norm_flat_grad')
     return g_y, dgamma, dbeta
+
+
+# ------------------------------------------------- backward of the pose head's convolutions (conv_grad.hip)
+def _conv_grad_map(t: Tensor, what: str, name: str, shape=None) -> Tuple[int, int, int, int]:
+    _dev(t, f'{what}: {name}')
+    if t.dim() != 4 or not t.is_contiguous() or (shape is not None and tuple(t.shape) != tuple(shape)):
+        want = 'a contiguous 4-D tensor' if shape is None else f'a contiguous {tuple(shape)} tensor'
+        raise _lib.ScflowHipError(f'{what}: {name} must be {want}, got {tuple(t.shape)}')
+    return tuple(t.shape)
+
+
+def _conv_grad_geometry(what: str, g: Tensor, weight_shape, in_hw, stride: int, padding: int):
+    """(M, Cout, Ho, Wo, Cin, Hin, Win) of a 3x3 / stride-2 / pad-1 layer, or an error before the library is reached."""
+    m, cout, ho, wo = _conv_grad_map(g, what, 'g')
+    if len(weight_shape) != 4 or weight_shape[0] != cout:
+        raise _lib.ScflowHipError(f'{what}: the weight must be ({cout}, Cin, 3, 3), got {tuple(weight_shape)}')
+    cin, kh, kw = weight_shape[1:]
+    if (kh, kw, stride, padding) != (3, 3, 2, 1):
+        raise _lib.ScflowHipError(f'{what}: 3x3 / stride 2 / padding 1 only, got {kh}x{kw} / {stride} / {padding}')
+    hin, win = in_hw
+    if hin < 1 or win < 1 or ho != (hin - 1) // 2 + 1 or wo != (win - 1) // 2 + 1:
+        raise _lib.ScflowHipError(f'{what}: a {hin}x{win} input does not give the {ho}x{wo} map of g')
+    return m, cout, ho, wo, cin, hin, win
+
+
+def conv_dgrad(g: Tensor, weight: Tensor, in_hw: Tuple[int, int], split: Optional[int] = None, stride: int = 2,
+               padding: int = 1, out=None):
+    """Input gradient of ``F.conv2d(x, weight, stride=2, padding=1)`` (``scf_conv_dgrad``): ``g`` (M, Cout, Ho, Wo),
+    ``weight`` (Cout, Cin, 3, 3) the raw parameter -> (M, Cin, Hin, Win); ``split`` = C0: the pair of dense tensors
+    (M, C0, Hin, Win), (M, Cin - C0, Hin, Win) of a two-part input instead.  ``out``: the destination(s)."""
+    what = 'conv_dgrad'
+    _dev(weight, f'{what}: weight')
+    if not weight.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: weight must be contiguous')
+    m, cout, ho, wo, cin, hin, win = _conv_grad_geometry(what, g, tuple(weight.shape), in_hw, stride, padding)
+    c0 = cin if split is None else int(split)
+    c1 = cin - c0
+    if c0 < 1 or c1 < 0 or (split is not None and c1 < 1):
+        raise _lib.ScflowHipError(f'{what}: split {split} leaves no channels on one side of {cin}')
+    outs = (out,) if split is None else ((None, None) if out is None else tuple(out))
+    if len(outs) != (1 if split is None else 2):
+        raise _lib.ScflowHipError(f'{what}: out must hold one destination per input part')
+    gx0 = _fc_grad_out(outs[0], (m, c0, hin, win), g, what, 'out[0]')
+    gx1 = _fc_grad_out(outs[1], (m, c1, hin, win), g, what, 'out[1]') if split is not None else None
+    _lib.check(_lib.load().scf_conv_dgrad(g.data_ptr(), weight.data_ptr(), gx0.data_ptr(), c0,
+                                          None if gx1 is None else gx1.data_ptr(), c1, m, cout, ho, wo, hin, win, 3, 3,
+                                          stride, padding, _stream()), 'scf_conv_dgrad')
+    return gx0 if split is None else (gx0, gx1)
+
+
+def conv_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
+    """floats of workspace ``conv_wgrad`` needs (``scf_conv_wgrad_workspace``)."""
+    n = int(_lib.load().scf_conv_wgrad_workspace(m, cout, cin, ho, wo))
+    if n < 0:
+        raise _lib.ScflowHipError(f'conv_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
+    return n
+
+
+def conv_wgrad(g: Tensor, x0: Tensor, x1: Optional[Tensor] = None, dw: Optional[Tensor] = None, accumulate: bool = False,
+               workspace: Optional[Tensor] = None, stride: int = 2, padding: int = 1, kernel_size: int = 3) -> Tensor:
+    """Weight gradient of ``F.conv2d(cat(x0, x1), weight, stride=2, padding=1)`` (``scf_conv_wgrad``): ``g`` (M, Cout, Ho,
+    Wo), ``x0`` (M, C0, Hin, Win), ``x1`` (M, C1, Hin, Win) or None -> (Cout, C0 + C1, 3, 3); ``accumulate``: added to
+    ``dw``.  ``workspace``: a float32 tensor of at least ``conv_wgrad_workspace`` elements (allocated when None)."""
+    what = 'conv_wgrad'
+    m, c0, hin, win = _conv_grad_map(x0, what, 'x0')
+    c1 = 0
+    if x1 is not None:
+        c1 = _conv_grad_map(x1, what, 'x1')[1]
+        _conv_grad_map(x1, what, 'x1', (m, c1, hin, win))
+    cin = c0 + c1
+    _conv_grad_map(g, what, 'g')
+    if g.shape[0] != m:
+        raise _lib.ScflowHipError(f'{what}: g holds {g.shape[0]} samples, x0 {m}')
+    _, cout, ho, wo, _, _, _ = _conv_grad_geometry(what, g, (g.shape[1], cin, kernel_size, kernel_size), (hin, win), stride,
+                                                   padding)
+    dw = _fc_grad_out(dw, (cout, cin, 3, 3), g, what, 'dw', accumulate)
+    need = conv_wgrad_workspace(m, cout, cin, ho, wo)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=g.device)
+    _dev(workspace, f'{what}: workspace')
+    if not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.ScflowHipError(f'{what}: workspace must be contiguous with at least {need} floats, got {workspace.numel()}')
+    _lib.check(_lib.load().scf_conv_wgrad(g.data_ptr(), x0.data_ptr(), c0, None if x1 is None else x1.data_ptr(), c1,
+                                          dw.data_ptr(), int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m,
+                                          cout, ho, wo, hin, win, 3, 3, stride, padding, _stream()), 'scf_conv_wgrad')
+    return dw

@@ -397,6 +397,17 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         encoders, whose backward (like the XHeads', the GRU's, the lookup's and the encoders') does not exist yet."""
         return self._loss(data_batch, data, 'pose_tail')
 
+    def loss_and_pose_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_pose_tail_grads()`` carried through the pose head's three convolutions and GroupNorms 0 and 1 -> the
+        same tuple, ``grads`` with one more key: ``pose_head_inputs`` = (``g_hvs``, ``g_dms``), the lists of d loss / d
+        (GRU hidden state ``hv`` (N, 128, h, w)) and d loss / d (delta-flow and mask features ``dm`` (N, 96, h, w)) per
+        iteration; ``params`` now holds the gradient of EVERY parameter of ``decoder.pose_pred``, summed over the iterations
+        (``MultiClassPoseHead.conv_backward`` after ``tail_backward``).  The values are the bits of ``loss()``, every entry
+        ``loss_and_pose_tail_grads()`` returns has its bits.  ``delta_flow_preds`` / ``masks`` are still NOT complete
+        gradients: ``g_dms`` has to be carried through the delta-flow and mask encoders to reach them, and ``g_hvs`` through
+        the XHeads, the GRU, the lookup and the encoders; none of those has a backward yet."""
+        return self._loss(data_batch, data, 'pose_head')
+
     def _loss(self, data_batch, data, with_grads):
         from . import losses as L
         self._build_loss_funcs()
@@ -404,13 +415,14 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
         dec = self.decoder
-        kept = dec.keep_pose_tail_input
+        kept, kept_head = dec.keep_pose_tail_input, dec.keep_pose_head_input
         dec.keep_pose_tail_input = kept or with_grads == 'pose_tail'
+        dec.keep_pose_head_input = kept_head or with_grads == 'pose_head'
         try:
             outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
                                  data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
         finally:
-            dec.keep_pose_tail_input = kept
+            dec.keep_pose_tail_input, dec.keep_pose_head_input = kept, kept_head
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
@@ -444,14 +456,17 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             grads['seq_rotations'] = pose_out[2][0]
             if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
                 grads['seq_translations'] = pose_out[2][1]
-        if with_grads in ('head', 'pose_tail'):
+        if with_grads in ('head', 'pose_tail', 'pose_head'):
             grads = self.decoder.tail_backward(outs, grads, data['ref_rotations'], data['ref_translations'],
                                                data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
-        if with_grads == 'pose_tail':
+        if with_grads in ('pose_tail', 'pose_head'):
             head = dec.pose_pred
             g_ys, params = head.tail_backward(dec.pose_tail_inputs, labels, grads['delta_rotation_preds'],
                                               grads['delta_translation_preds'])
             grads['pose_tail_inputs'] = g_ys
+            if with_grads == 'pose_head':
+                g_hvs, g_dms, params = head.conv_backward(dec.pose_head_inputs, g_ys, params)
+                grads['pose_head_inputs'] = (g_hvs, g_dms)
             grads['params'] = {'decoder.pose_pred.' + key: val for key, val in params.items()}
         return out + (grads,)
 
@@ -460,7 +475,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             raise NotImplementedError('train_step and the backward of the network are not implemented; loss_and_grads() '
                                       'returns the loss values and their gradients at the network outputs, '
                                       'loss_and_head_grads() carries them to the head outputs of every iteration, '
-                                      'loss_and_pose_tail_grads() through the fully connected tail of the pose head')
+                                      'loss_and_pose_tail_grads() through the fully connected tail of the pose head, '
+                                      'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
