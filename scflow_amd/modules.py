@@ -496,6 +496,16 @@ class XHead(HipModule):
         return self.predict(self.layers[0](x))
 
 
+def _grad_slots(what: str, names: Sequence[str], param_grads: Optional[dict]) -> Tuple[dict, list, bool]:
+    """(the dict a backward writes its parameter gradients to, its entries under ``names`` -- None where absent --,
+    whether they are accumulated into): a ``param_grads`` that holds ``what`` must hold all of them."""
+    grads = {} if param_grads is None else param_grads
+    have = [k in grads for k in names]
+    if any(have) and not all(have):
+        raise _lib_error(what + ' but not all')
+    return grads, [grads.get(k) for k in names], all(have)
+
+
 @HEAD.register_module()
 class MultiClassPoseHead(HipModule):
     """head/pose_head.py:110-211."""
@@ -550,55 +560,60 @@ class MultiClassPoseHead(HipModule):
             ok = fc1.in_features % last.groups == 0 and gsz % 2 == 0 and (fc1.in_features // s1) % gsz == 0
         return (s1, s2) if ok else (0, 0)
 
-    def features(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
-        x = self.conv_layers[0](x0, x1)
-        x = self.conv_layers[1](x)
-        s1, s2 = self.fc_plan()
-        fc1, fc2 = self.fc_layers[0][0], self.fc_layers[1][0]
-        if s1:
-            last = self.conv_layers[2]
-            # GroupNorm + ReLU: applied by fc1's operand load, which also adds the partial tensors of a K-sliced launch
-            ks = ops.conv_kslices_for(last.packed, x)
-            y = ops.conv2d(last.packed, x, kslices=ks)
-            hw = y.shape[-2] * y.shape[-1]
-            feat = y.shape[-3] * hw
-            if feat != fc1.in_features:
-                raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {feat}')
-            yv = y.view(ks, x.shape[0], feat) if ks > 1 else y.view(x.shape[0], feat)
-            p1 = ops.fc_splitk(yv, fc1.weight, gn=(last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps),
-                               slices=s1)
-            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
-            return ops.fc_splitk(p2, self.rotation_pred.weight, self.rotation_pred.bias, x_bias=fc2.bias, x_relu=True,
-                                 weight2=self.translation_pred.weight, bias2=self.translation_pred.bias)
-        x = self.conv_layers[2](x)
-        x = x.view(x.shape[0], -1)
-        for fc in self.fc_layers:
-            x = ops.linear(x, fc[0].weight, fc[0].bias, ACT_RELU)
-        rot_all, trans_all = ops.linear_pair(x, self.rotation_pred.weight, self.rotation_pred.bias,
-                                             self.translation_pred.weight, self.translation_pred.bias)
-        return rot_all, trans_all
-
-    def tail_input(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tensor:
-        """What ``features()`` computes up to and including the last convolution: its raw output ``y`` (N, 128, h', w'), or
-        the (S, N, 128, h', w') partial tensors of a K-sliced launch -- the input of the fully connected tail (GroupNorm +
-        ReLU, fc1, fc2, the two heads) and all ``tail_backward`` needs of an iteration."""
-        x = self.conv_layers[0](x0, x1)
-        x = self.conv_layers[1](x)
-        last = self.conv_layers[2]
-        return ops.conv2d(last.packed, x, kslices=ops.conv_kslices_for(last.packed, x))
-
     def _conv_outputs(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tuple[Tensor, Tensor, Tensor]:
-        """``tail_input()`` that also hands out the raw outputs of the first two convolutions: (y0, y1, y2), each
-        (N, 128, h', w') or the (S, N, 128, h', w') partial tensors of a K-sliced launch.  The launches of ``features()`` up
-        to the last convolution, in its order: the same bits."""
+        """The convolution stage, the only place that sequences the three blocks: per block ``ConvBlock.forward``'s
+        K-sliced convolution, GroupNorm + ReLU between blocks.  -> the raw outputs (y0, y1, y2), each (N, 128, h', w') or
+        the (S, N, 128, h', w') partial tensors of a K-sliced launch."""
         ys, x = [], x0
         for i, blk in enumerate(self.conv_layers):
+            if blk.groups is None or blk.act != ACT_RELU:
+                raise NotImplementedError('pose head: conv + GroupNorm + ReLU blocks')
             xb = x1 if i == 0 else None
             y = ops.conv2d(blk.packed, x, xb, kslices=ops.conv_kslices_for(blk.packed, x, xb))
             ys.append(y)
             if i < 2:
                 x = ops.group_norm_relu(y, blk.gn.weight, blk.gn.bias, blk.groups, blk.gn.eps)
         return tuple(ys)
+
+    def _tail(self, y: Tensor, activations: bool = False):
+        """The fully connected stage, the only place that sequences it: the last GroupNorm + ReLU, fc1, fc2 and the two
+        heads on the last convolution's raw output ``y``, (M, C, h, w) or (parts, M, C, h, w) partial tensors (a stack of
+        iterations included), by ``fc_plan()``'s route.  -> (rot_all, trans_all), or with ``activations`` the operands
+        (x0, a1, a2) of fc1, fc2 and the heads, in the bits the route contracts, without launching the heads."""
+        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
+        rot, trans = self.rotation_pred, self.translation_pred
+        parts = y.shape[0] if y.dim() == 5 else 1
+        m, hw = y.shape[-4], y.shape[-2] * y.shape[-1]
+        feat = y.shape[-3] * hw
+        if feat != fc1.in_features:
+            raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {feat}')
+        s1, s2 = self.fc_plan()
+        if s1:
+            # GroupNorm + ReLU: applied by fc1's operand load, which also adds the partial tensors of a K-sliced launch
+            yv, gn = y.view(parts, m, feat), (last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps)
+            x0 = ops.fc_operand(yv, gn=gn) if activations else None
+            p1 = ops.fc_splitk(yv, fc1.weight, gn=gn, slices=s1)
+            a1 = ops.fc_operand(p1, x_bias=fc1.bias, x_relu=True) if activations else None
+            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
+            if activations:
+                return x0, a1, ops.fc_operand(p2, x_bias=fc2.bias, x_relu=True)
+            return ops.fc_splitk(p2, rot.weight, rot.bias, x_bias=fc2.bias, x_relu=True, weight2=trans.weight,
+                                 bias2=trans.bias)
+        x0 = ops.group_norm_relu(y[0] if y.dim() == 5 and parts == 1 else y, last.gn.weight, last.gn.bias, last.groups,
+                                 last.gn.eps).view(m, feat)
+        a1 = ops.linear(x0, fc1.weight, fc1.bias, ACT_RELU)
+        a2 = ops.linear(a1, fc2.weight, fc2.bias, ACT_RELU)
+        return (x0, a1, a2) if activations else ops.linear_pair(a2, rot.weight, rot.bias, trans.weight, trans.bias)
+
+    def features(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tuple[Tensor, Tensor]:
+        """(rot_all, trans_all) of the head, whose three blocks must be convolution + GroupNorm + ReLU."""
+        return self._tail(self._conv_outputs(x0, x1)[2])
+
+    def tail_input(self, x0: Tensor, x1: Optional[Tensor] = None) -> Tensor:
+        """What ``features()`` computes up to and including the last convolution: its raw output ``y`` (N, 128, h', w'), or
+        the (S, N, 128, h', w') partial tensors of a K-sliced launch -- the input of the fully connected tail (GroupNorm +
+        ReLU, fc1, fc2, the two heads) and all ``tail_backward`` needs of an iteration."""
+        return self._conv_outputs(x0, x1)[2]
 
     def conv_backward(self, saved: dict, g_ys: Sequence[Tensor], param_grads: Optional[dict] = None
                       ) -> Tuple[list, list, dict]:
@@ -648,12 +663,8 @@ class MultiClassPoseHead(HipModule):
         names = ('conv_layers.2.conv.weight', 'conv_layers.1.gn.weight', 'conv_layers.1.gn.bias',
                  'conv_layers.1.conv.weight', 'conv_layers.0.gn.weight', 'conv_layers.0.gn.bias',
                  'conv_layers.0.conv.weight')
-        grads = {} if param_grads is None else param_grads
-        have = [k in grads for k in names]
-        if any(have) and not all(have):
-            raise _lib_error('conv_backward: param_grads holds some of the convolutions\' gradients but not all')
-        acc = all(have)
-        dst = [grads.get(k) for k in names]
+        grads, dst, acc = _grad_slots('conv_backward: param_grads holds some of the convolutions\' gradients', names,
+                                      param_grads)
 
         def act(y, blk, hw_):       # the forward's launch on the stacked samples
             yv = y.view(y.shape[0], m, blk.conv.out_channels, *hw_)
@@ -684,49 +695,6 @@ class MultiClassPoseHead(HipModule):
         g_hv, g_dm = g_hv.view(T, n, c0, h, w), g_dm.view(T, n, dm.shape[2], h, w)
         return [g_hv[t] for t in range(T)], [g_dm[t] for t in range(T)], grads
 
-    def _features_from_tail_input(self, y: Tensor) -> Tuple[Tensor, Tensor]:
-        """``features()`` from ``tail_input()``'s result on: the same launches in the same order, so the same bits, without
-        running the convolutions a second time (the decoder's loop under ``keep_pose_tail_input``)."""
-        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
-        ks = y.shape[0] if y.dim() == 5 else 1
-        n, hw = y.shape[-4], y.shape[-2] * y.shape[-1]
-        feat = y.shape[-3] * hw
-        s1, s2 = self.fc_plan()
-        if s1:
-            if feat != fc1.in_features:
-                raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {feat}')
-            yv = y.view(ks, n, feat) if ks > 1 else y.view(n, feat)
-            p1 = ops.fc_splitk(yv, fc1.weight, gn=(last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps), slices=s1)
-            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
-            return ops.fc_splitk(p2, self.rotation_pred.weight, self.rotation_pred.bias, x_bias=fc2.bias, x_relu=True,
-                                 weight2=self.translation_pred.weight, bias2=self.translation_pred.bias)
-        x = ops.group_norm_relu(y, last.gn.weight, last.gn.bias, last.groups, last.gn.eps)
-        x = x.view(x.shape[0], -1)
-        for fc in self.fc_layers:
-            x = ops.linear(x, fc[0].weight, fc[0].bias, ACT_RELU)
-        return ops.linear_pair(x, self.rotation_pred.weight, self.rotation_pred.bias,
-                               self.translation_pred.weight, self.translation_pred.bias)
-
-    def _tail_activations(self, y: Tensor, m: int) -> Tuple[Tensor, Tensor, Tensor]:
-        """(x0, a1, a2) of the stacked tail inputs ``y`` (parts, M, C, h, w), by the route -- and so in the bits -- of
-        ``features()``."""
-        last, fc1, fc2 = self.conv_layers[2], self.fc_layers[0][0], self.fc_layers[1][0]
-        hw = y.shape[-2] * y.shape[-1]
-        feat = y.shape[-3] * hw
-        s1, s2 = self.fc_plan()
-        if s1:
-            yv = y.view(y.shape[0], m, feat)
-            gn = (last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps)
-            x0 = ops.fc_operand(yv, gn=gn)
-            p1 = ops.fc_splitk(yv, fc1.weight, gn=gn, slices=s1)
-            a1 = ops.fc_operand(p1, x_bias=fc1.bias, x_relu=True)
-            p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
-            return x0, a1, ops.fc_operand(p2, x_bias=fc2.bias, x_relu=True)
-        x0 = ops.group_norm_relu(y if y.shape[0] > 1 else y[0], last.gn.weight, last.gn.bias, last.groups, last.gn.eps)
-        x0 = x0.view(m, feat)
-        a1 = ops.linear(x0, fc1.weight, fc1.bias, ACT_RELU)
-        return x0, a1, ops.linear(a1, fc2.weight, fc2.bias, ACT_RELU)
-
     def tail_backward(self, ys: Sequence[Tensor], label: Tensor, g_delta_rotations: Sequence[Tensor],
                       g_delta_translations: Sequence[Tensor], label_mode: Optional[int] = None,
                       param_grads: Optional[dict] = None) -> Tuple[list, dict]:
@@ -752,24 +720,16 @@ class MultiClassPoseHead(HipModule):
             raise _lib_error('tail_backward: ys are the (N, C, h, w) or (S, N, C, h, w) tensors of tail_input()')
         y5 = [y if y.dim() == 5 else y.unsqueeze(0) for y in ys]
         parts, n, c, h, w = y5[0].shape
-        if c * h * w != fc1.in_features:
-            raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {c * h * w}')
         m = T * n
         y = y5[0].contiguous() if T == 1 else torch.stack(y5, 1).view(parts, m, c, h, w)
         g_rot = g_delta_rotations[0].contiguous() if T == 1 else torch.cat(list(g_delta_rotations))
         g_trans = g_delta_translations[0].contiguous() if T == 1 else torch.cat(list(g_delta_translations))
         mode = self.label_mode if label_mode is None else label_mode
-        x0, a1, a2 = self._tail_activations(y, m)
-
+        x0, a1, a2 = self._tail(y, activations=True)
         names = ('rotation_pred.weight', 'rotation_pred.bias', 'translation_pred.weight', 'translation_pred.bias',
                  'fc_layers.1.0.weight', 'fc_layers.1.0.bias', 'fc_layers.0.0.weight', 'fc_layers.0.0.bias',
                  'conv_layers.2.gn.weight', 'conv_layers.2.gn.bias')
-        grads = {} if param_grads is None else param_grads
-        have = [k in grads for k in names]
-        if any(have) and not all(have):
-            raise _lib_error('tail_backward: param_grads holds some of the tail\'s gradients but not all')
-        acc = all(have)
-        dst = [grads.get(k) for k in names]
+        grads, dst, acc = _grad_slots('tail_backward: param_grads holds some of the tail\'s gradients', names, param_grads)
         g_s2, heads = ops.pose_select_grad(g_rot, g_trans, self.rotation_pred.weight, self.translation_pred.weight, a2,
                                            label, n, mode, grads=dst[0:4] if acc else None, accumulate=acc)
         dw2, db2 = ops.fc_wgrad(g_s2, a1, dst[4], dst[5], accumulate=acc)
@@ -934,16 +894,9 @@ class SCFlowDecoder(HipModule):
             with br:
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
-            if self.keep_pose_head_input:      # features() in steps, the launches and their order unchanged
-                ys = self.pose_pred._conv_outputs(hv, dm)
-                self._keep_pose_head_input(len(outs[0]), hv, dm, ys)
-                self.pose_tail_inputs.append(ys[2])
-                rot_all, trans_all = self.pose_pred._features_from_tail_input(ys[2])
-            elif self.keep_pose_tail_input:    # features() in two steps, the launches and their order unchanged
-                self.pose_tail_inputs.append(self.pose_pred.tail_input(hv, dm))
-                rot_all, trans_all = self.pose_pred._features_from_tail_input(self.pose_tail_inputs[-1])
-            else:
-                rot_all, trans_all = self.pose_pred.features(hv, dm)               # :218-219
+            ys = self.pose_pred._conv_outputs(hv, dm)                              # :218-219
+            self._keep_pose_inputs(len(outs[0]), hv, dm, ys)
+            rot_all, trans_all = self.pose_pred._tail(ys[2])
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
                 self.pose_flags())
@@ -954,24 +907,26 @@ class SCFlowDecoder(HipModule):
                 lst.append(v)
         return outs
 
-
-def _scflow_keep_pose_head_input(self, t: int, hv: Tensor, dm: Tensor, ys) -> None:
-    """iteration ``t`` of ``pose_head_inputs``: the buffers for all iterations are allocated by the first one."""
-    kept = self.pose_head_inputs
-    if t == 0:
-        f32 = dict(dtype=torch.float32, device=hv.device)
-        kept['hv'] = torch.empty((self.iters,) + tuple(hv.shape), **f32)
-        kept['dm'] = torch.empty((self.iters,) + tuple(dm.shape), **f32)
-        for i, y in enumerate(ys):
-            s_ = y.shape[0] if y.dim() == 5 else 1
-            kept[f'y{i}'] = torch.empty((s_, self.iters) + tuple(y.shape[-4:]), **f32)
-    kept['hv'][t].copy_(hv)
-    kept['dm'][t].copy_(dm)
-    for i, y in enumerate(ys):
-        kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
-
-
-SCFlowDecoder._keep_pose_head_input = _scflow_keep_pose_head_input
+    def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False) -> None:
+        """What the keep flags ask for of iteration ``t``, copies only; neither flag: nothing.  ``keep_pose_head_input``:
+        ``hv``, ``dm`` and the raw convolution outputs ``ys`` into ``pose_head_inputs``, whose buffers for all iterations
+        the first one allocates.  Either flag: the last of ``ys`` onto ``pose_tail_inputs`` -- a ``clone`` where later
+        iterations rewrite that buffer."""
+        if self.keep_pose_head_input:
+            kept = self.pose_head_inputs
+            if t == 0:
+                f32 = dict(dtype=torch.float32, device=hv.device)
+                kept['hv'] = torch.empty((self.iters,) + tuple(hv.shape), **f32)
+                kept['dm'] = torch.empty((self.iters,) + tuple(dm.shape), **f32)
+                for i, y in enumerate(ys):
+                    s_ = y.shape[0] if y.dim() == 5 else 1
+                    kept[f'y{i}'] = torch.empty((s_, self.iters) + tuple(y.shape[-4:]), **f32)
+            kept['hv'][t].copy_(hv)
+            kept['dm'][t].copy_(dm)
+            for i, y in enumerate(ys):
+                kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
+        if self.keep_pose_tail_input or self.keep_pose_head_input:
+            self.pose_tail_inputs.append(ys[2].clone() if clone else ys[2])
 
 
 def _scflow_tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translation: Tensor, depth: Tensor,
@@ -1120,7 +1075,6 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         keep += [y, g]
         raw_ys.append(y)
         x0, x1 = g, None
-    tail_input = y                  # the last convolution's raw output: rewritten by every iteration
     fc1, fc2 = ph.fc_layers[0][0], ph.fc_layers[1][0]
     if fc1.in_features != x0[0].numel():
         raise _lib_error(f'pose head expects {fc1.in_features} features, the maps give {x0[0].numel()}')
@@ -1154,11 +1108,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        if self.keep_pose_head_input:
-            self._keep_pose_head_input(i, hv, dm, raw_ys)
-            self.pose_tail_inputs.append(tail_input.clone())
-        elif self.keep_pose_tail_input:
-            self.pose_tail_inputs.append(tail_input.clone())
+        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True)
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already

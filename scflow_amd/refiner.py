@@ -227,6 +227,10 @@ class _RenderingRefiner:
         return OrderedDict((k, float(x)) for (k, _), x in zip(named, host))
 
 
+# how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do
+_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head')
+
+
 @REFINERS.register_module()
 class SCFlowRefiner(_RenderingRefiner, HipModule):
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int,
@@ -367,7 +371,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         has the reference's keys in the reference's order (the ``init_add_*`` pair only when the data carries it) and
         reaches the host in one transfer.  ``data``: an already formatted dict (``format_data_train_sup``'s), the only
         way to call this without an attached renderer; it needs ``gt_masks`` when ``filter_invalid_flow`` is set."""
-        return self._loss(data_batch, data, False)
+        return self._loss(data_batch, data, 'none')
 
     def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
         """``loss()`` plus the training signal at the network's outputs -> (loss, None, log_vars, seq_rotations,
@@ -376,7 +380,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         list of d loss / d prediction per iteration (``loss = loss_pose + loss_flow + loss_mask``), from the
         value-and-gradient launches: the values are the bits ``loss()`` returns and ``log_vars`` still costs one
         transfer.  The network itself has no backward yet."""
-        return self._loss(data_batch, data, True)
+        return self._loss(data_batch, data, 'outputs')
 
     def loss_and_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
         """``loss_and_grads()`` carried through the parameter-free tail of every iteration -> (loss, None, log_vars,
@@ -408,16 +412,19 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         the XHeads, the GRU, the lookup and the encoders; none of those has a backward yet."""
         return self._loss(data_batch, data, 'pose_head')
 
-    def _loss(self, data_batch, data, with_grads):
+    def _loss(self, data_batch, data, depth):
         from . import losses as L
+        at = _GRAD_DEPTHS.index
+        level = at(depth)
+        with_grads = level >= at('outputs')
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
         dec = self.decoder
         kept, kept_head = dec.keep_pose_tail_input, dec.keep_pose_head_input
-        dec.keep_pose_tail_input = kept or with_grads == 'pose_tail'
-        dec.keep_pose_head_input = kept_head or with_grads == 'pose_head'
+        dec.keep_pose_tail_input = kept or level >= at('pose_tail')
+        dec.keep_pose_head_input = kept_head or level >= at('pose_head')
         try:
             outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
                                  data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
@@ -456,15 +463,15 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             grads['seq_rotations'] = pose_out[2][0]
             if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
                 grads['seq_translations'] = pose_out[2][1]
-        if with_grads in ('head', 'pose_tail', 'pose_head'):
+        if level >= at('head'):
             grads = self.decoder.tail_backward(outs, grads, data['ref_rotations'], data['ref_translations'],
                                                data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
-        if with_grads in ('pose_tail', 'pose_head'):
+        if level >= at('pose_tail'):
             head = dec.pose_pred
             g_ys, params = head.tail_backward(dec.pose_tail_inputs, labels, grads['delta_rotation_preds'],
                                               grads['delta_translation_preds'])
             grads['pose_tail_inputs'] = g_ys
-            if with_grads == 'pose_head':
+            if level >= at('pose_head'):
                 g_hvs, g_dms, params = head.conv_backward(dec.pose_head_inputs, g_ys, params)
                 grads['pose_head_inputs'] = (g_hvs, g_dms)
             grads['params'] = {'decoder.pose_pred.' + key: val for key, val in params.items()}

@@ -262,7 +262,7 @@ def _tail_refs(head, ys, label, g_rots, g_trans, mode):
     gsz = k // last.groups
     p32 = {key: cpu(dict(head.named_parameters())[name]) for key, name in HF.TAIL_NAMES.items()}
     p = {key: f64(v) for key, v in p32.items()}
-    x0, a1, a2 = (cpu(t) for t in head._tail_activations(D(parts).view(parts.shape[0], m, -1, *ys[0].shape[-2:]), m))
+    x0, a1, a2 = (cpu(t) for t in head._tail(D(parts).view(parts.shape[0], m, -1, *ys[0].shape[-2:]), activations=True))
     masks = tuple(f64(t) > 0 for t in (x0, a1, a2))
     ysum = fc_operand(parts)
     cls = HF.clamp_class(cpu(label).numpy(), m, n, head.num_class, mode)

@@ -237,6 +237,66 @@ def test_pose_head_tail_against_float64_of_the_read_back_map(feat_size):
         assert worst <= 1.0
 
 
+@pytest.mark.parametrize('feat_size, kslices', [((8, 8), True), ((8, 24), True), ((8, 8), False)],
+                         ids=['8x8', '8x24', '8x8-unsliced'])
+def test_pose_head_stages_make_the_written_out_launches(feat_size, kslices):
+    """The head's launch list written out with ops calls only, against its two stages and what is composed of them:
+    bit equality throughout.  (8, 8): 128 features, the fused route, the last convolution in 4 K-slices (the parts path)
+    or unsliced; (8, 24): 384 features, which ``fc_plan()`` refuses, so the linear route whatever ``fused_fc`` says."""
+    head = _head(feat_size)
+    g = torch.Generator().manual_seed(29)
+    n = 2
+    x0, x1 = (torch.randn((n, c, *feat_size), generator=g).to(DEV) for c in (128, 96))
+    last, fc1, fc2 = head.conv_layers[2], head.fc_layers[0][0], head.fc_layers[1][0]
+    rot, trans = head.rotation_pred, head.translation_pred
+    prev = ops.set_conv_kslices(kslices)
+    try:
+        ys, x, xb = [], x0, x1
+        for i, blk in enumerate(head.conv_layers):
+            ys.append(ops.conv2d(blk.packed, x, xb, kslices=ops.conv_kslices_for(blk.packed, x, xb)))
+            if i < 2:
+                x, xb = ops.group_norm_relu(ys[-1], blk.gn.weight, blk.gn.bias, blk.groups, blk.gn.eps), None
+        y = ys[2]
+        if not kslices:
+            assert all(v.dim() == 4 for v in ys)
+        elif feat_size == (8, 8):
+            assert y.dim() == 5 and y.shape[0] == 4
+        hw = y.shape[-2] * y.shape[-1]
+        feat = y.shape[-3] * hw
+        assert feat == fc1.in_features
+        for got, want in zip(head._conv_outputs(x0, x1), ys):
+            assert got.shape == want.shape and same_bits(got, want)
+        assert same_bits(head.tail_input(x0, x1), y)
+        for fused in (True, False):
+            head.fused_fc = fused
+            s1, s2 = head.fc_plan()
+            assert (s1 > 0) == (fused and feat_size == (8, 8))
+            if s1:
+                gn = (last.groups, hw, last.gn.weight, last.gn.bias, last.gn.eps)
+                yv = y.view(y.shape[0], n, feat) if y.dim() == 5 else y.view(n, feat)
+                p1 = ops.fc_splitk(yv, fc1.weight, gn=gn, slices=s1)
+                p2 = ops.fc_splitk(p1, fc2.weight, x_bias=fc1.bias, x_relu=True, slices=s2)
+                want = ops.fc_splitk(p2, rot.weight, rot.bias, x_bias=fc2.bias, x_relu=True, weight2=trans.weight,
+                                     bias2=trans.bias)
+                acts = (ops.fc_operand(yv, gn=gn), ops.fc_operand(p1, x_bias=fc1.bias, x_relu=True),
+                        ops.fc_operand(p2, x_bias=fc2.bias, x_relu=True))
+            else:
+                a0 = ops.group_norm_relu(y, last.gn.weight, last.gn.bias, last.groups, last.gn.eps).view(n, feat)
+                a1 = ops.linear(a0, fc1.weight, fc1.bias, ACT_RELU)
+                a2 = ops.linear(a1, fc2.weight, fc2.bias, ACT_RELU)
+                want = ops.linear_pair(a2, rot.weight, rot.bias, trans.weight, trans.bias)
+                acts = (a0, a1, a2)
+            for name, got in (('features', head.features(x0, x1)), ('_tail', head._tail(head.tail_input(x0, x1)))):
+                assert same_bits(got[0], want[0]) and same_bits(got[1], want[1]), (name, fused)
+            # the (parts, M, C, h, w) form tail_backward hands over: one part for an unsliced convolution
+            got = head._tail(y if y.dim() == 5 else y.unsqueeze(0), activations=True)
+            assert len(got) == 3
+            for a, b in zip(got, acts):
+                assert a.shape == b.shape and torch.equal(a > 0, b > 0) and same_bits(a, b), fused
+    finally:
+        ops.set_conv_kslices(prev)
+
+
 # ================================================================================================== 2d: two heads
 @pytest.mark.parametrize('n', [1, 33])
 @pytest.mark.parametrize('o, o2', FC_TWO_HEADS)

@@ -371,7 +371,7 @@ def _tail_check(head, ys, label, g_rots, g_trans, g_ys, grads, mode):
     gsz = k // last.groups
     p32 = {key: cpu(dict(head.named_parameters())[name]) for key, name in NAMES.items()}
     p = {key: f64(v) for key, v in p32.items()}
-    x0, a1, a2 = (cpu(t) for t in head._tail_activations(D(parts).view(parts.shape[0], m, -1, *ys[0].shape[-2:]), m))
+    x0, a1, a2 = (cpu(t) for t in head._tail(D(parts).view(parts.shape[0], m, -1, *ys[0].shape[-2:]), activations=True))
     masks = tuple(f64(t) > 0 for t in (x0, a1, a2))
     ysum = fc_operand(parts)
     nc = head.num_class

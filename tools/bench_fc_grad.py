@@ -93,7 +93,7 @@ def hip_backward():
 
 
 ystack = torch.stack(ys, 0).view(1, M, C, hh, ww)
-acts = head._tail_activations(ystack, M)
+acts = head._tail(ystack, activations=True)
 gr, gt = torch.cat(g_rot), torch.cat(g_trans)
 
 
