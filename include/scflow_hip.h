@@ -980,6 +980,46 @@ int scf_conv_wgrad(const float* g, const float* x0, int C0, const float* x1, int
                    float* workspace, int64_t workspace_floats, int M, int Cout, int Ho, int Wo, int Hin, int Win, int KH,
                    int KW, int stride, int pad, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Backward of a stride-1, same-padding convolution with bias (scflow_decoder.py:210-217: the XHeads and the delta-flow /
+ * mask encoders; the family also covers the GRU's 1x5 / 5x1 gates and the motion encoder's layers): input gradient with
+ * a fused second cotangent and activation backward, weight + bias gradient, and the elementwise activation backward.
+ * fp32; no atomics, allocation, synchronisation or read-back; every sum has one order fixed by the shapes
+ * (conv_s1_grad.hip), so results are bit-identical from run to run.
+ * Geometry: stride 1, pad = (KH / 2, KW / 2), KH and KW each in {1, 3, 5, 7}, any H, W >= 1; an even or larger kernel:
+ * SCF_EUNSUPPORTED; a null required pointer, a non-positive size, an unknown act, act != NONE without a, a sample stride
+ * smaller than C H W: SCF_EINVAL; all with nothing launched or written.  Sample strides are in elements, so a channel
+ * slice of a wider tensor is an operand.  w / dW are the raw (Cout, Cin, KH, KW) parameter in the torch layout.
+ * Route: min(Cout, Cin) >= 32 runs on v_mfma_f32_32x32x2_f32, everything else on the vector ALU; a function of
+ * (Cout, Cin) only.  Added without a version bump; the presence of scf_conv_s1_dgrad marks the feature.
+ * --------------------------------------------------------------------------------- */
+
+/* out[m, i] = g[m, i] act'(a[m, i]), i < n: RELU a > 0 ? g : +0, SIGMOID g (a (1 - a)), TANH g fma(-a, a, 1), NONE g;
+ * a: the forward's post-activation value (required exactly when act != SCF_ACT_NONE). */
+int scf_act_grad(const float* g, int64_t g_stride, const float* a, int64_t a_stride, int act, float* out,
+                 int64_t out_stride, int M, int64_t n, scf_stream_t stream);
+
+/* gx[m, ci, iy, ix] = act'(a) (sum_{ky, kx, co} g[m, co, iy + KH / 2 - ky, ix + KW / 2 - kx] w[co, ci, ky, kx] + add)
+ * g (M, Cout, H, W), add / a / gx (M, Cin, H, W), each with its sample stride; add NULL: none.  Per element ONE fma chain
+ * from +0, taps in ascending (ky, kx), inside a tap co ascending (MFMA route: padded with zeros to a multiple of 32, taps
+ * outside the map contribute zeros; vector route: such taps are skipped); then + add, then the factor as scf_act_grad.
+ * w_scratch: NULL, or KH KW Cout Cin floats of device memory: the MFMA route then reads w through a [tap][co][ci] copy
+ * that a launch in front writes (same bits, coalesced loads); unused on the vector route.  A sample's result depends
+ * on that sample alone, whatever M is. */
+int scf_conv_s1_dgrad(const float* g, int64_t g_stride, const float* w, const float* add, int64_t add_stride,
+                      const float* a, int64_t a_stride, int act, float* gx, int64_t gx_stride, float* w_scratch, int M,
+                      int Cout, int Cin, int H, int W, int KH, int KW, scf_stream_t stream);
+
+/* dW[co][ci][ky][kx] = sum_{m, y, x} g[m, co, y, x] x[m, ci, y - KH / 2 + ky, x - KW / 2 + kx]  (zero outside the map),
+ * db[co] = sum_{m, y, x} g[m, co, y, x] from the same pass (db NULL: none).  The contraction is cut into S splits
+ * (conv_s1_grad.hip: s1_wgrad_plan), a partial each in the workspace; the second launch takes partial 0, adds partials
+ * 1 .. S - 1 in ascending order and, with accumulate != 0, the previous value of dW / db last.
+ * workspace: scf_conv_s1_wgrad_workspace(...) floats of device memory (-1: invalid sizes or kernel); fewer: SCF_EINVAL. */
+int64_t scf_conv_s1_wgrad_workspace(int M, int Cout, int Cin, int H, int W, int KH, int KW);
+int scf_conv_s1_wgrad(const float* g, int64_t g_stride, const float* x, int64_t x_stride, float* dW, float* db,
+                      int accumulate, float* workspace, int64_t workspace_floats, int M, int Cout, int Cin, int H, int W,
+                      int KH, int KW, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

@@ -301,6 +301,12 @@ SIGNATURES = {
     'scf_conv_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'scf_conv_wgrad': (C.c_int, [_fp, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_act_grad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, _fp, C.c_int64, C.c_int, C.c_int64, _fp]),
+    'scf_conv_s1_dgrad': (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int64, C.c_int, _fp, C.c_int64, _fp,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_conv_s1_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_conv_s1_wgrad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),

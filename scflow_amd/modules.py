@@ -808,6 +808,10 @@ class SCFlowDecoder(HipModule):
         # False: nothing is kept, allocated or launched
         self.keep_pose_head_input = False
         self.pose_head_inputs = {}
+        # True: every forward also keeps, per iteration, the XHeads' outputs d_flow (T, N, 2, h, w) and the post-sigmoid
+        # mask (T, N, 1, h, w) in pose_head_inputs, what heads_backward needs next to hv and dm; implies
+        # keep_pose_head_input.  False: nothing is kept, allocated or launched
+        self.keep_head_inputs = False
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -836,9 +840,9 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
-        if self.keep_pose_tail_input or self.keep_pose_head_input:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs:
             self.pose_tail_inputs = []
-        if self.keep_pose_head_input:
+        if self.keep_pose_head_input or self.keep_head_inputs:
             self.pose_head_inputs = {}
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
@@ -895,7 +899,7 @@ class SCFlowDecoder(HipModule):
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
             ys = self.pose_pred._conv_outputs(hv, dm)                              # :218-219
-            self._keep_pose_inputs(len(outs[0]), hv, dm, ys)
+            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask)
             rot_all, trans_all = self.pose_pred._tail(ys[2])
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
@@ -907,12 +911,21 @@ class SCFlowDecoder(HipModule):
                 lst.append(v)
         return outs
 
-    def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False) -> None:
-        """What the keep flags ask for of iteration ``t``, copies only; neither flag: nothing.  ``keep_pose_head_input``:
+    def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False, d_flow: Optional[Tensor] = None,
+                          mask: Optional[Tensor] = None) -> None:
+        """What the keep flags ask for of iteration ``t``, copies only; no flag: nothing.  ``keep_pose_head_input``:
         ``hv``, ``dm`` and the raw convolution outputs ``ys`` into ``pose_head_inputs``, whose buffers for all iterations
-        the first one allocates.  Either flag: the last of ``ys`` onto ``pose_tail_inputs`` -- a ``clone`` where later
-        iterations rewrite that buffer."""
-        if self.keep_pose_head_input:
+        the first one allocates; ``keep_head_inputs``: ``d_flow`` and ``mask`` as well.  Any flag: the last of ``ys`` onto
+        ``pose_tail_inputs`` -- a ``clone`` where later iterations rewrite that buffer."""
+        if self.keep_head_inputs:
+            kept = self.pose_head_inputs
+            if t == 0:
+                f32 = dict(dtype=torch.float32, device=hv.device)
+                kept['d_flow'] = torch.empty((self.iters,) + tuple(d_flow.shape), **f32)
+                kept['mask'] = torch.empty((self.iters,) + tuple(mask.shape), **f32)
+            kept['d_flow'][t].copy_(d_flow)
+            kept['mask'][t].copy_(mask)
+        if self.keep_pose_head_input or self.keep_head_inputs:
             kept = self.pose_head_inputs
             if t == 0:
                 f32 = dict(dtype=torch.float32, device=hv.device)
@@ -925,7 +938,7 @@ class SCFlowDecoder(HipModule):
             kept['dm'][t].copy_(dm)
             for i, y in enumerate(ys):
                 kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
-        if self.keep_pose_tail_input or self.keep_pose_head_input:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs:
             self.pose_tail_inputs.append(ys[2].clone() if clone else ys[2])
 
 
@@ -993,6 +1006,123 @@ def _scflow_tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translati
 
 
 SCFlowDecoder.tail_backward = _scflow_tail_backward
+
+_HEAD_PARAMS = tuple(f'{m}.{p}' for m in ('flow_pred.layers.0.conv', 'flow_pred.predict_layer', 'mask_pred.layers.0.conv',
+                                          'mask_pred.predict_layer', 'delta_flow_encoder.0.conv', 'delta_flow_encoder.1.conv',
+                                          'mask_encoder.0.conv', 'mask_encoder.1.conv') for p in ('weight', 'bias'))
+
+
+def _scflow_heads_backward(self, saved: dict, g_hvs: Sequence[Tensor], g_dms: Sequence[Tensor],
+                           g_delta_flows: Sequence[Tensor], g_masks: Sequence[Tensor], param_grads: Optional[dict] = None):
+    """Backward of the two XHeads and the delta-flow / mask encoders (scflow_decoder.py:210-217: seven stride-1
+    convolutions with bias) for the T iterations of a pass at once, M = T N stacked samples, one launch per stage.
+
+    ``saved``: what a forward under ``keep_head_inputs`` left in ``pose_head_inputs`` (``hv`` (T, N, 128, h, w), ``dm``
+    (T, N, 96, h, w), ``d_flow`` (T, N, 2, h, w), the post-sigmoid ``mask`` (T, N, 1, h, w)).  ``g_hvs``, ``g_dms``: the
+    cotangents at ``hv`` and ``dm`` that ``MultiClassPoseHead.conv_backward`` returns; ``g_delta_flows``, ``g_masks``: those
+    at ``d_flow`` and at the post-sigmoid mask that ``tail_backward`` returns.  -> (``g_hidden_states``: the cotangents at
+    ``hv`` through iteration t's own heads, encoders and pose head; ``g_delta_flow_totals``: the complete cotangents at
+    ``d_flow``; ``g_mask_logits``: those at the mask head's pre-sigmoid output; T tensors each; ``param_grads``: the
+    gradients of the 16 parameters summed over all T N samples, keyed as in ``named_parameters()``).  A dict passed in
+    is accumulated into (entries it lacks are created; some but not all of these entries: an error).
+
+    The hidden activations -- ``heads`` (512 channels), ``d1`` (128), ``m1`` (64): wgrad operands and activation masks --
+    are recomputed into stacked buffers by the forward's OWN launches, one iteration at a time at the forward's batch,
+    so dispatch and bits are the forward's.  Chain per stacked sample: act_grad on ``g_dm``; wgrad + dgrad of the
+    encoders' last layers; wgrad of their first layers and dgrad with the tail's cotangents added (the mask's with the
+    sigmoid factor); wgrad of the predict layers and their dgrads into the two halves of one (M, 512, h, w) tensor
+    with the ReLU mask of ``heads``; wgrad and dgrad of the packed hidden layer with ``g_hv`` added."""
+    what = 'heads_backward'
+    T = len(g_hvs)
+    if T == 0 or T > ops.TAIL_MAX_T or any(len(s_) != T for s_ in (g_dms, g_delta_flows, g_masks)):
+        raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent of each kind per iteration')
+    try:
+        hv, dm, d_flow, mask = (saved[k] for k in ('hv', 'dm', 'd_flow', 'mask'))
+    except (KeyError, TypeError):
+        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_head_inputs (hv, dm, d_flow, mask)') from None
+    if hv.dim() != 5 or hv.shape[0] != T or not hv.is_contiguous():
+        raise _lib_error(f'{what}: hv must be a contiguous ({T}, N, C, h, w) tensor, got {tuple(hv.shape)}')
+    n, hc, h, w = hv.shape[1:]
+    fp, mp, de, me = self.flow_pred, self.mask_pred, self.delta_flow_encoder, self.mask_encoder
+    ch = fp.layers[0].conv.out_channels                     # 256: the flow head's rows of the packed hidden layer
+    c_h = ch + mp.layers[0].conv.out_channels
+    c_d1, c_df, c_m1, c_mf = (b.conv.out_channels for b in (de[0], de[1], me[0], me[1]))
+    for name, t_, c in (('dm', dm, c_df + c_mf), ('d_flow', d_flow, 2), ('mask', mask, 1)):
+        if tuple(t_.shape) != (T, n, c, h, w) or not t_.is_contiguous():
+            raise _lib_error(f'{what}: {name} must be a contiguous {(T, n, c, h, w)} tensor, got {tuple(t_.shape)}')
+    for name, seq, c in (('g_hvs', g_hvs, hc), ('g_dms', g_dms, c_df + c_mf), ('g_delta_flows', g_delta_flows, 2),
+                         ('g_masks', g_masks, 1)):
+        if any(tuple(g.shape) != (n, c, h, w) for g in seq):
+            raise _lib_error(f'{what}: {name} are {(n, c, h, w)} tensors')
+    enc_act = de[0].act
+    if any(b.act != enc_act for b in (de[1], me[0], me[1])) or enc_act not in (ACT_NONE, ACT_RELU):
+        raise NotImplementedError('heads_backward: encoders with ReLU or no activation')
+    grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the heads\' and encoders\' gradients', _HEAD_PARAMS,
+                                  param_grads)
+    dst = dict(zip(_HEAD_PARAMS, dst))
+    m = T * n
+    f32 = dict(dtype=torch.float32, device=hv.device)
+    E = lambda *shape: torch.empty(shape, **f32)       # noqa: E731
+    # ---- the forward's own launches, an iteration at a time: heads, d1, m1 in the forward's bits
+    heads, d1, m1 = E(T, n, c_h, h, w), E(T, n, c_d1, h, w), E(T, n, c_m1, h, w)
+    for t in range(T):
+        ops.conv2d(self.packed, hv[t], out=heads[t], act=ACT_RELU)
+        de[0](d_flow[t], out=d1[t])
+        me[0](mask[t], out=m1[t])
+    stack = lambda seq, c: (seq[0].contiguous() if T == 1 else torch.stack(list(seq))).view(m, c, h, w)   # noqa: E731
+    g_hv, g_dm, g_df, g_mk = stack(g_hvs, hc), stack(g_dms, c_df + c_mf), stack(g_delta_flows, 2), stack(g_masks, 1)
+    hv_, dm_, df_, mk_ = hv.view(m, hc, h, w), dm.view(m, c_df + c_mf, h, w), d_flow.view(m, 2, h, w), mask.view(m, 1, h, w)
+    heads_, d1_, m1_ = heads.view(m, c_h, h, w), d1.view(m, c_d1, h, w), m1.view(m, c_m1, h, w)
+    layers = ((c_df, c_d1, de[1].conv), (c_mf, c_m1, me[1].conv), (c_d1, 2, de[0].conv), (c_m1, 1, me[0].conv),
+              (2, ch, fp.predict_layer), (1, c_h - ch, mp.predict_layer), (c_h, hc, None))
+    ks = lambda conv: (3, 3) if conv is None else tuple(conv.kernel_size)      # noqa: E731
+    ws = E(max(ops.conv_s1_wgrad_workspace(m, co, ci, h, w, *ks(cv)) for co, ci, cv in layers))
+    a_or_none = lambda a: a if enc_act != ACT_NONE else None                    # noqa: E731
+
+    def wgrad(g, x, name, conv):
+        return ops.conv_s1_wgrad(g, x, tuple(conv.kernel_size), dw=dst[f'{name}.weight'], db=dst[f'{name}.bias'],
+                                 accumulate=acc, workspace=ws)
+
+    out = {}
+    # 1. encoders, last layers
+    u = ops.act_grad(g_dm, a_or_none(dm_), enc_act)
+    u_df, u_mf = u[:, :c_df], u[:, c_df:]
+    out['delta_flow_encoder.1.conv'] = wgrad(u_df, d1_, 'delta_flow_encoder.1.conv', de[1].conv)
+    g_d1 = ops.conv_s1_dgrad(u_df, de[1].conv.weight, a=a_or_none(d1_), act=enc_act)
+    out['mask_encoder.1.conv'] = wgrad(u_mf, m1_, 'mask_encoder.1.conv', me[1].conv)
+    g_m1 = ops.conv_s1_dgrad(u_mf, me[1].conv.weight, a=a_or_none(m1_), act=enc_act)
+    # 2. encoders, first layers: the tail's cotangents join here
+    out['delta_flow_encoder.0.conv'] = wgrad(g_d1, df_, 'delta_flow_encoder.0.conv', de[0].conv)
+    g_df_total = ops.conv_s1_dgrad(g_d1, de[0].conv.weight, add=g_df)
+    out['mask_encoder.0.conv'] = wgrad(g_m1, mk_, 'mask_encoder.0.conv', me[0].conv)
+    g_logit = ops.conv_s1_dgrad(g_m1, me[0].conv.weight, add=g_mk, a=mk_, act=ACT_SIGMOID)
+    del g_d1, g_m1, u
+    # 3. predict layers: their dgrads write the two halves of one tensor, ReLU mask of heads in the epilogue
+    out['flow_pred.predict_layer'] = wgrad(g_df_total, heads_[:, :ch], 'flow_pred.predict_layer', fp.predict_layer)
+    out['mask_pred.predict_layer'] = wgrad(g_logit, heads_[:, ch:], 'mask_pred.predict_layer', mp.predict_layer)
+    g_heads = E(m, c_h, h, w)
+    ops.conv_s1_dgrad(g_df_total, fp.predict_layer.weight, a=heads_[:, :ch], act=ACT_RELU, out=g_heads[:, :ch])
+    ops.conv_s1_dgrad(g_logit, mp.predict_layer.weight, a=heads_[:, ch:], act=ACT_RELU, out=g_heads[:, ch:])
+    # 4. the packed hidden layer: rows :ch are the flow head's, the rest the mask head's
+    a_, b_ = fp.layers[0].conv, mp.layers[0].conv
+    w_hidden = torch.cat([a_.weight, b_.weight], 0)
+    names_h = ('flow_pred.layers.0.conv', 'mask_pred.layers.0.conv')
+    dw_h = torch.cat([dst[f'{k}.weight'] for k in names_h], 0) if acc else None      # the kernel adds the previous value LAST
+    db_h = torch.cat([dst[f'{k}.bias'] for k in names_h], 0) if acc else None
+    dw_h, db_h = ops.conv_s1_wgrad(g_heads, hv_, (3, 3), dw=dw_h, db=db_h, accumulate=acc, workspace=ws)
+    for name, rows in zip(names_h, (slice(0, ch), slice(ch, c_h))):
+        if acc:
+            out[name] = (dst[f'{name}.weight'].copy_(dw_h[rows]), dst[f'{name}.bias'].copy_(db_h[rows]))
+        else:
+            out[name] = (dw_h[rows].contiguous(), db_h[rows].contiguous())
+    g_hidden = ops.conv_s1_dgrad(g_heads, w_hidden, add=g_hv, w_scratch=E(w_hidden.numel()))
+    for name, (dw_, db_) in out.items():
+        grads[f'{name}.weight'], grads[f'{name}.bias'] = dw_, db_
+    g_hidden, g_df_total, g_logit = g_hidden.view(T, n, hc, h, w), g_df_total.view(T, n, 2, h, w), g_logit.view(T, n, 1, h, w)
+    return ([g_hidden[t] for t in range(T)], [g_df_total[t] for t in range(T)], [g_logit[t] for t in range(T)], grads)
+
+
+SCFlowDecoder.heads_backward = _scflow_heads_backward
 
 
 def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
@@ -1108,7 +1238,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True)
+        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask)
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already

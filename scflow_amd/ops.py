@@ -2233,3 +2233,125 @@ def conv_wgrad(g: Tensor, x0: Tensor, x1: Optional[Tensor] = None, dw: Optional[
                                           dw.data_ptr(), int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m,
                                           cout, ho, wo, hin, win, 3, 3, stride, padding, _stream()), 'scf_conv_wgrad')
     return dw
+
+
+# ------------------------------------------------- backward of the stride-1 convolutions with bias (conv_s1_grad.hip)
+S1_KERNELS = (1, 3, 5, 7)                        # KH and KW, chosen independently; pad = (KH // 2, KW // 2)
+_S1_ACTS = (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH)
+
+
+def _s1_map(t: Tensor, what: str, name: str, shape=None) -> Tuple[int, int]:
+    """(pointer, sample stride) of a (M, C, H, W) float32 tensor that is contiguous up to a channel slice."""
+    ptr, n, c, h, w, sn = _nchw(t, f'{what}: {name}')
+    if shape is not None and (n, c, h, w) != tuple(shape):
+        raise _lib.ScflowHipError(f'{what}: {name} must be {tuple(shape)}, got {(n, c, h, w)}')
+    if sn < c * h * w:
+        raise _lib.ScflowHipError(f'{what}: {name} has a sample stride {sn} below its {c * h * w} elements a sample')
+    return ptr, sn
+
+
+def _s1_weight_shape(what: str, shape) -> Tuple[int, int, int, int]:
+    if len(shape) != 4:
+        raise _lib.ScflowHipError(f'{what}: the weight must be (Cout, Cin, KH, KW), got {tuple(shape)}')
+    cout, cin, kh, kw = (int(v) for v in shape)
+    if kh not in S1_KERNELS or kw not in S1_KERNELS:
+        raise _lib.ScflowHipError(f'{what}: KH and KW must each be one of {S1_KERNELS}, got {kh}x{kw}')
+    if cout < 1 or cin < 1:
+        raise _lib.ScflowHipError(f'{what}: the weight must hold channels, got {tuple(shape)}')
+    return cout, cin, kh, kw
+
+
+def _s1_act(what: str, act: int, a: Optional[Tensor]) -> None:
+    if act not in _S1_ACTS:
+        raise _lib.ScflowHipError(f'{what}: unknown activation code {act}')
+    if (act != ACT_NONE) != (a is not None):
+        raise _lib.ScflowHipError(f'{what}: a (the post-activation value) is needed exactly when act != ACT_NONE')
+
+
+def act_grad(g: Tensor, a: Optional[Tensor], act: int, out: Optional[Tensor] = None) -> Tensor:
+    """``g * act'(a)`` elementwise (``scf_act_grad``): ``g``, ``a``, ``out`` (M, C, H, W), each contiguous up to a channel
+    slice; ``a`` the forward's post-activation value (None exactly with ``ACT_NONE``)."""
+    what = 'act_grad'
+    _s1_act(what, act, a)
+    pg, gs = _s1_map(g, what, 'g')
+    shape = tuple(g.shape)
+    pa, sa = (None, 0) if a is None else _s1_map(a, what, 'a', shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=g.device)
+    po, so = _s1_map(out, what, 'out', shape)
+    m, c, h, w = shape
+    if m * c * h * w == 0:
+        raise _lib.ScflowHipError(f'{what}: empty tensor {shape}')
+    _lib.check(_lib.load().scf_act_grad(pg, gs, pa, sa, act, po, so, m, c * h * w, _stream()), 'scf_act_grad')
+    return out
+
+
+def conv_s1_dgrad(g: Tensor, weight: Tensor, add: Optional[Tensor] = None, a: Optional[Tensor] = None,
+                  act: int = ACT_NONE, out: Optional[Tensor] = None, w_scratch: Optional[Tensor] = None) -> Tensor:
+    """Input gradient of ``F.conv2d(x, weight, padding=(KH // 2, KW // 2))`` with a second cotangent and the activation
+    backward of the layer in front fused (``scf_conv_s1_dgrad``): ``act'(a) * (dgrad(g, weight) + add)``.  ``g`` (M, Cout,
+    H, W); ``weight`` (Cout, Cin, KH, KW) the raw parameter; ``add``, ``a``, ``out`` (M, Cin, H, W); all maps contiguous up to
+    a channel slice.  ``w_scratch``: at least ``weight.numel()`` floats for the transposed copy the MFMA route reads."""
+    what = 'conv_s1_dgrad'
+    _dev(weight, f'{what}: weight')
+    if not weight.is_contiguous():
+        raise _lib.ScflowHipError(f'{what}: weight must be contiguous')
+    cout, cin, kh, kw = _s1_weight_shape(what, tuple(weight.shape))
+    _s1_act(what, act, a)
+    pg, gs = _s1_map(g, what, 'g')
+    m, gc, h, w = g.shape
+    if gc != cout or m * h * w == 0:
+        raise _lib.ScflowHipError(f'{what}: g must be (M, {cout}, H, W) with M, H, W >= 1, got {tuple(g.shape)}')
+    shape = (m, cin, h, w)
+    padd, sadd = (None, 0) if add is None else _s1_map(add, what, 'add', shape)
+    pa, sa = (None, 0) if a is None else _s1_map(a, what, 'a', shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=g.device)
+    po, so = _s1_map(out, what, 'out', shape)
+    ps = None
+    if w_scratch is not None:
+        ps = _dense(w_scratch, f'{what}: w_scratch')
+        _fc_vector(w_scratch, weight.numel(), what, 'w_scratch', at_least=True)
+    _lib.check(_lib.load().scf_conv_s1_dgrad(pg, gs, weight.data_ptr(), padd, sadd, pa, sa, act, po, so, ps, m, cout, cin,
+                                             h, w, kh, kw, _stream()), 'scf_conv_s1_dgrad')
+    return out
+
+
+def conv_s1_wgrad_workspace(m: int, cout: int, cin: int, h: int, w: int, kh: int, kw: int) -> int:
+    """floats of workspace ``conv_s1_wgrad`` needs (``scf_conv_s1_wgrad_workspace``)."""
+    n = int(_lib.load().scf_conv_s1_wgrad_workspace(m, cout, cin, h, w, kh, kw))
+    if n < 0:
+        raise _lib.ScflowHipError(f'conv_s1_wgrad_workspace: invalid sizes {(m, cout, cin, h, w, kh, kw)}')
+    return n
+
+
+def conv_s1_wgrad(g: Tensor, x: Tensor, kernel_size, dw: Optional[Tensor] = None, db: Optional[Tensor] = None,
+                  bias: bool = True, accumulate: bool = False, workspace: Optional[Tensor] = None):
+    """Weight and bias gradient of ``F.conv2d(x, weight, bias, padding=(KH // 2, KW // 2))`` (``scf_conv_s1_wgrad``): ``g``
+    (M, Cout, H, W), ``x`` (M, Cin, H, W), both contiguous up to a channel slice, ``kernel_size`` (KH, KW) -> (dw (Cout, Cin,
+    KH, KW), db (Cout,) or None with ``bias=False``); ``accumulate``: added to ``dw`` / ``db``.  ``workspace``: a float32
+    tensor of at least ``conv_s1_wgrad_workspace`` elements (allocated when None)."""
+    what = 'conv_s1_wgrad'
+    pg, gs = _s1_map(g, what, 'g')
+    m, cout, h, w = g.shape
+    px, xs = _s1_map(x, what, 'x')
+    if x.shape[0] != m or tuple(x.shape[2:]) != (h, w):
+        raise _lib.ScflowHipError(f'{what}: x {tuple(x.shape)} does not match g {tuple(g.shape)}')
+    cin = x.shape[1]
+    kh, kw = (kernel_size, kernel_size) if isinstance(kernel_size, int) else tuple(kernel_size)
+    _s1_weight_shape(what, (cout, cin, kh, kw))
+    if m * h * w == 0:
+        raise _lib.ScflowHipError(f'{what}: empty maps {tuple(g.shape)}')
+    dw = _fc_grad_out(dw, (cout, cin, kh, kw), g, what, 'dw', accumulate)
+    if bias or db is not None:
+        db = _fc_grad_out(db, (cout,), g, what, 'db', accumulate)
+    need = conv_s1_wgrad_workspace(m, cout, cin, h, w, kh, kw)
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=g.device)
+    _dev(workspace, f'{what}: workspace')
+    if not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.ScflowHipError(f'{what}: workspace must be contiguous with at least {need} floats, got {workspace.numel()}')
+    _lib.check(_lib.load().scf_conv_s1_wgrad(pg, gs, px, xs, dw.data_ptr(), None if db is None else db.data_ptr(),
+                                             int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m, cout, cin,
+                                             h, w, kh, kw, _stream()), 'scf_conv_s1_wgrad')
+    return dw, db

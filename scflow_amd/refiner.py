@@ -228,7 +228,7 @@ class _RenderingRefiner:
 
 
 # how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do
-_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head')
+_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head', 'decoder_heads')
 
 
 @REFINERS.register_module()
@@ -412,6 +412,22 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         the XHeads, the GRU, the lookup and the encoders; none of those has a backward yet."""
         return self._loss(data_batch, data, 'pose_head')
 
+    def loss_and_decoder_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_pose_head_grads()`` carried through the two XHeads and the delta-flow / mask encoders
+        (``SCFlowDecoder.heads_backward``) -> the same tuple, ``grads`` with one more key: ``decoder_heads`` =
+        ``dict(hidden_states, delta_flow_preds, mask_logits)``, a list per key over the iterations.  ``hidden_states[t]`` is
+        d loss / d ``hv_t`` (N, 128, h, w) through iteration t's OWN heads, encoders and pose head: the cotangent the GRU
+        backward will add the next iteration's to.  ``delta_flow_preds[t]`` is the complete d loss / d ``d_flow_t`` (the
+        tail's plus the delta-flow encoder's), ``mask_logits[t]`` the complete d loss / d (pre-sigmoid mask) of iteration t --
+        except that under ``mask_flow`` / ``mask_corr`` without ``detach_mask`` the path from ``mask_t`` into iteration
+        t + 1's motion encoder is still missing.  ``params`` is extended by the 16 weights and biases of
+        ``decoder.flow_pred``, ``decoder.mask_pred``, ``decoder.delta_flow_encoder`` and ``decoder.mask_encoder``, summed over
+        the iterations: every parameter downstream of the GRU state now has a gradient.  The values are the bits of
+        ``loss()``; every entry ``loss_and_pose_head_grads()`` returns keeps its bits and its key (the top-level
+        ``delta_flow_preds`` / ``masks`` stay the tail's partial cotangents).  The GRU, the lookup, the motion encoder
+        and the image encoders have no backward yet."""
+        return self._loss(data_batch, data, 'decoder_heads')
+
     def _loss(self, data_batch, data, depth):
         from . import losses as L
         at = _GRAD_DEPTHS.index
@@ -422,14 +438,15 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
         dec = self.decoder
-        kept, kept_head = dec.keep_pose_tail_input, dec.keep_pose_head_input
+        kept, kept_head, kept_heads = dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs
         dec.keep_pose_tail_input = kept or level >= at('pose_tail')
         dec.keep_pose_head_input = kept_head or level >= at('pose_head')
+        dec.keep_head_inputs = kept_heads or level >= at('decoder_heads')
         try:
             outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
                                  data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
         finally:
-            dec.keep_pose_tail_input, dec.keep_pose_head_input = kept, kept_head
+            dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs = kept, kept_head, kept_heads
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
@@ -475,6 +492,11 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                 g_hvs, g_dms, params = head.conv_backward(dec.pose_head_inputs, g_ys, params)
                 grads['pose_head_inputs'] = (g_hvs, g_dms)
             grads['params'] = {'decoder.pose_pred.' + key: val for key, val in params.items()}
+            if level >= at('decoder_heads'):
+                g_h, g_df, g_ml, head_params = dec.heads_backward(dec.pose_head_inputs, g_hvs, g_dms,
+                                                                  grads['delta_flow_preds'], grads['masks'])
+                grads['decoder_heads'] = dict(hidden_states=g_h, delta_flow_preds=g_df, mask_logits=g_ml)
+                grads['params'].update(('decoder.' + key, val) for key, val in head_params.items())
         return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):
@@ -483,7 +505,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                       'returns the loss values and their gradients at the network outputs, '
                                       'loss_and_head_grads() carries them to the head outputs of every iteration, '
                                       'loss_and_pose_tail_grads() through the fully connected tail of the pose head, '
-                                      'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm')
+                                      'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm, '
+                                      'loss_and_decoder_head_grads() through the XHeads and the delta-flow / mask encoders to hv')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
