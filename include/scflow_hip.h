@@ -1020,6 +1020,45 @@ int scf_conv_s1_wgrad(const float* g, int64_t g_stride, const float* x, int64_t 
                       int accumulate, float* workspace, int64_t workspace_floats, int M, int Cout, int Cin, int H, int W,
                       int KH, int KW, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Gate arithmetic of the ConvGRU backward (raft_decoder.py:168-253; gru_grad.hip), between the convolution gradients
+ * above.  One pass of the forward: z = sigmoid(conv_z([h|x])), r = sigmoid(conv_r([h|x])), q = tanh(conv_q([r h|x])),
+ * h' = (1 - z) h + z q.  With g = d loss / d h':  u_q = g z (1 - q^2), u_z = g (q - h) z (1 - z), [g_rh | g_x] =
+ * dgrad_q(u_q), u_r = g_rh h r (1 - r), g_h = g (1 - z) + g_rh r + the h columns of dgrad_zr([u_z | u_r]).
+ * Every operand is (M, n): rows of n floats with a row stride in elements (a channel slice of a wider NCHW tensor is
+ * an operand).  Elementwise, fp32, no atomics / allocation / synchronisation; each line below is ONE rounding:
+ *   grad_q: t1 = g z, dq = fma(-q, q, 1), u_q = t1 dq;  d = q - h, t2 = g d, dz = z (1 - z), u_z = t2 dz + 0
+ *   grad_r: t3 = g_rh h, dr = r (1 - r), u_r = t3 dr + 0;  a = 1 - z, b = g a, g_h_direct = fma(g_rh, r, b)
+ * dq / dz / dr are scf_act_grad's factors applied the same way: u_q == scf_act_grad(g z, q, TANH) bit for bit, and so
+ * on.  "+ 0" turns a -0 product into +0: a zero cotangent gives +0 everywhere.
+ * sum_* (optional, NULL: none): running sums over the calls of a scan, sum = first ? u : sum + u.
+ * A null required pointer, M <= 0, n <= 0 or a stride below n: SCF_EINVAL with nothing launched or written.
+ * Added without a version bump; the presence of scf_gru_gate_grad_q marks the feature.
+ * --------------------------------------------------------------------------------- */
+
+/* (g, h, z, q) -> u_q, u_z (u_z usually rows [0, Ch) of the (M, 2 Ch, H, W) tensor [u_z | u_r]). */
+int scf_gru_gate_grad_q(const float* g, int64_t g_stride, const float* h, int64_t h_stride, const float* z,
+                        int64_t z_stride, const float* q, int64_t q_stride, float* u_q, int64_t u_q_stride, float* u_z,
+                        int64_t u_z_stride, float* sum_q, int64_t sum_q_stride, float* sum_z, int64_t sum_z_stride,
+                        int first, int M, int64_t n, scf_stream_t stream);
+
+/* (g, z, g_rh, h, r) -> u_r, and g_h_direct = g (1 - z) + g_rh r written IN PLACE over g_rh (the first Ch channels
+ * of the q convolution's input gradient: that buffer is then the `add` operand of the z|r convolution's dgrad). */
+int scf_gru_gate_grad_r(const float* g, int64_t g_stride, const float* z, int64_t z_stride, float* g_rh,
+                        int64_t g_rh_stride, const float* h, int64_t h_stride, const float* r, int64_t r_stride,
+                        float* u_r, int64_t u_r_stride, float* sum_r, int64_t sum_r_stride, int first, int M, int64_t n,
+                        scf_stream_t stream);
+
+/* The carried cotangent of the reverse scan: out = src + add (add NULL: out = src), one rounding; clear != 0: src is
+ * then set to +0 (a pass hands its g_h over and leaves [0 | g_x] behind as the next dgrad's `add` operand). */
+int scf_gru_carry(float* src, int64_t src_stride, const float* add, int64_t add_stride, float* out, int64_t out_stride,
+                  int clear, int M, int64_t n, scf_stream_t stream);
+
+/* What the backward recomputes of the forward's gate epilogues next to the convolutions: q NULL: out = gate h (the
+ * q convolution's input r h); else a = 1 - gate, b = a h, out = fma(gate, q, b) (the state update (1 - z) h + z q). */
+int scf_gru_gate_state(const float* h, int64_t h_stride, const float* gate, int64_t gate_stride, const float* q,
+                       int64_t q_stride, float* out, int64_t out_stride, int M, int64_t n, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

@@ -307,6 +307,13 @@ SIGNATURES = {
     'scf_conv_s1_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'scf_conv_s1_wgrad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_gru_gate_grad_q': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,
+                                      C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
+    'scf_gru_gate_grad_r': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,
+                                      C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
+    'scf_gru_carry': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
+    'scf_gru_gate_state': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int64,
+                                     _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),

@@ -473,6 +473,163 @@ class ConvGRU(HipModule):
         ops.copy_channels(x, hx[:, self.h_channels:])
         return self.forward_inplace(hx)
 
+    # ---- backward: a reverse scan over the iterations, the passes of an iteration in reverse ----
+    def param_names(self) -> Tuple[str, ...]:
+        """the GRU's parameters as ``named_parameters()`` keys them: per pass conv_z, conv_r, conv_q, weight and bias"""
+        return tuple(f'{g}.{p}.conv.{k}' for p in range(len(self.conv_z)) for g in ('conv_z', 'conv_r', 'conv_q')
+                     for k in ('weight', 'bias'))
+
+    def _saved(self, what: str, saved, T: Optional[int] = None):
+        try:
+            h0, c, x, hv = (saved[k] for k in ('h0', 'c', 'x', 'hv'))
+        except (KeyError, TypeError):
+            raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_gru_inputs (h0, c, x, hv)') from None
+        if hv.dim() != 5 or (T is not None and hv.shape[0] != T) or hv.shape[0] == 0 or not hv.is_contiguous():
+            raise _lib_error(f'{what}: hv must be a contiguous ({"T" if T is None else T}, N, C, h, w) tensor, got {tuple(hv.shape)}')
+        T, n, hc, h, w = hv.shape
+        if hc != self.h_channels:
+            raise _lib_error(f'{what}: hv has {hc} channels, the GRU state has {self.h_channels}')
+        cc = c.shape[1] if c.dim() == 4 else -1
+        cx = self.x_channels - cc
+        for name, t_, shape in (('h0', h0, (n, hc, h, w)), ('c', c, (n, cc, h, w)), ('x', x, (T, n, cx, h, w))):
+            if tuple(t_.shape) != shape or not t_.is_contiguous() or cc < 0 or cx < 1:
+                raise _lib_error(f'{what}: {name} must be a contiguous {shape} tensor, got {tuple(t_.shape)}')
+        return h0, c, x, hv
+
+    def recompute_gates(self, saved: dict) -> dict:
+        """What the backward needs of the forward and the forward does not emit, from the forward's own convolution
+        launches (``ops.conv2d`` on the packs of ``_pack``, sigmoid / tanh epilogue), one iteration at a time at the
+        forward's batch: per pass the stacked (T, N, C, h, w) tensors ``h_in`` (the pass's input state: ``h0`` / the kept
+        ``hv[t - 1]`` for the first pass, the recomputed intermediate state for the second), ``zr`` = [z | r], ``rh`` =
+        r h, ``q``, and ``h_out`` (T, N, Ch, h, w), the recomputed ``hv`` (a check value: the scan reads the kept one)."""
+        what = 'ConvGRU.recompute_gates'
+        h0, c, x, hv = self._saved(what, saved)
+        T, n, hc, h, w = hv.shape
+        cc, cx = c.shape[1], x.shape[2]
+        packs = self.packed
+        P = len(packs)
+        E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=hv.device)       # noqa: E731
+        hxb = E(n, hc + cc + cx, h, w)
+        ops.copy_channels(c, hxb[:, hc:hc + cc])
+        h_in = [E(T, n, hc, h, w) for _ in range(P)]
+        h_in[0][0].copy_(h0)
+        if T > 1:
+            h_in[0][1:].copy_(hv[:-1])
+        zr, rh, q = [E(T, n, 2 * hc, h, w) for _ in range(P)], [E(T, n, hc, h, w) for _ in range(P)], [E(T, n, hc, h, w) for _ in range(P)]
+        h_out = E(T, n, hc, h, w)
+        for t in range(T):
+            ops.copy_channels(x[t], hxb[:, hc + cc:])
+            for p, (pzr, pq) in enumerate(packs):
+                ops.copy_channels(h_in[p][t], hxb[:, :hc])
+                ops.conv2d(pzr, hxb, out=zr[p][t], act=ACT_SIGMOID)
+                ops.gru_gate_state(h_in[p][t], zr[p][t][:, hc:], out=rh[p][t])
+                ops.conv2d(pq, rh[p][t], hxb[:, hc:], out=q[p][t], act=ACT_TANH)
+                ops.gru_gate_state(h_in[p][t], zr[p][t][:, :hc], q[p][t], out=h_in[p + 1][t] if p + 1 < P else h_out[t])
+        return dict(h_in=h_in, zr=zr, rh=rh, q=q, h_out=h_out)
+
+    def backward(self, saved: dict, g_hidden_states: Sequence[Tensor], param_grads: Optional[dict] = None,
+                 intermediates: Optional[dict] = None):
+        """Backward of the T iterations of the GRU (raft_decoder.py:235-253, both ``net_type``s): a reverse scan, t = T - 1
+        ... 0, the passes of an iteration in reverse; the carried cotangent is ``g_hidden_states[t]`` plus the ``g_h`` of
+        iteration t + 1.
+
+        ``saved``: ``h0`` (N, Ch, h, w), the context ``c`` (N, Cc, h, w), the motion features ``x`` (T, N, Cx', h, w) and
+        the kept states ``hv`` (T, N, Ch, h, w) -- ``SCFlowDecoder.pose_head_inputs`` under ``keep_gru_inputs``.
+        ``g_hidden_states``: T cotangents at ``hv_t`` (``SCFlowDecoder.heads_backward`` returns them).  -> (``g_h0``: d loss
+        / d ``h0``; ``g_context``: d loss / d ``c`` summed over iterations and passes; ``g_motion_features``: T cotangents
+        at ``x_t`` (N, Cx', h, w), channel slices of one stacked buffer; ``param_grads``: the gradients of the GRU's
+        parameters summed over all T N samples, keyed as in ``named_parameters()``).  A dict passed in is accumulated
+        into (entries it lacks are created; some but not all of the GRU's entries: an error).
+
+        Per pass (``scf_gru_gate_grad_q`` -> dgrad of conv_q -> ``scf_gru_gate_grad_r`` -> dgrad of the stacked z | r
+        convolution with [g_h_direct | g_x] added) over the [h | x'] columns only; the context columns once per pass
+        after the scan on the running sums of the u's (one dgrad and one wgrad at M = N each); the weight gradients
+        after the scan over the M = T N stacked samples.  No atomics: every sum has one order.
+
+        ``intermediates``: a dict that receives every launch's operands, for inspection and for the tests that check the
+        scan launch by launch (None: nothing is kept or copied): per (pass, iteration) copies of the carried cotangent
+        ``g``, the q dgrad's output ``g_q``, the z | r dgrad's ``add`` operand and its output ``out``; the stacked ``u_zr``,
+        ``u_q``, the running sums ``s_zr``, ``s_q`` and the recomputed ``gates``."""
+        what = 'ConvGRU.backward'
+        T = len(g_hidden_states)
+        if T == 0 or T > ops.TAIL_MAX_T:
+            raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at hv per iteration')
+        h0, c, x, hv = self._saved(what, saved, T)
+        n, hc, h, w = hv.shape[1:]
+        cc, cx = c.shape[1], x.shape[2]
+        if any(tuple(g.shape) != (n, hc, h, w) for g in g_hidden_states):
+            raise _lib_error(f'{what}: g_hidden_states are {(n, hc, h, w)} tensors')
+        names = self.param_names()
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the GRU\'s gradients', names, param_grads)
+        dst = dict(zip(names, dst))
+        gt = self.recompute_gates(saved)
+        P = len(self.conv_z)
+        E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=hv.device)       # noqa: E731
+        # ---- the weights by column block: [h | x'] for the scan, c for the hoisted launches
+        hx_cols = lambda wt: torch.cat([wt[:, :hc], wt[:, hc + cc:]], 1).contiguous()       # noqa: E731
+        c_cols = lambda wt: wt[:, hc:hc + cc].contiguous()                                 # noqa: E731
+        w_zr = [torch.cat([z.conv.weight.detach(), r.conv.weight.detach()], 0) for z, r in zip(self.conv_z, self.conv_r)]
+        w_q = [q.conv.weight.detach() for q in self.conv_q]
+        w_zr_hx, w_q_hx, w_zr_c, w_q_c = ([f(wt) for wt in ws_] for f, ws_ in ((hx_cols, w_zr), (hx_cols, w_q),
+                                                                                (c_cols, w_zr), (c_cols, w_q)))
+        w_scratch = E(max(wt.numel() for wt in w_zr_hx))
+        # ---- the scan
+        u_zr, u_q = [E(T, n, 2 * hc, h, w) for _ in range(P)], [E(T, n, hc, h, w) for _ in range(P)]
+        s_zr, s_q = [E(n, 2 * hc, h, w) for _ in range(P)], [E(n, hc, h, w) for _ in range(P)]
+        out = E(T, n, hc + cx, h, w)                   # per iteration [g_h | g_x'] of its first pass: the pass's complete result
+        g_q, carry = E(n, hc + cx, h, w), E(n, hc, h, w)
+        rec = (lambda *a: None) if intermediates is None else (                            # noqa: E731
+            lambda key, p, t, v: intermediates.setdefault(key, {}).__setitem__((p, t), v.clone()))
+        for t in reversed(range(T)):
+            first = t == T - 1
+            g = g_hidden_states[t] if first else ops.gru_carry(out[t + 1][:, :hc], g_hidden_states[t], out=carry)
+            add_x = None
+            for p in reversed(range(P)):
+                h_in, z, r, q = gt['h_in'][p][t], gt['zr'][p][t][:, :hc], gt['zr'][p][t][:, hc:], gt['q'][p][t]
+                rec('g', p, t, g)
+                ops.gru_gate_grad_q(g, h_in, z, q, u_q=u_q[p][t], u_z=u_zr[p][t][:, :hc], sum_q=s_q[p], sum_z=s_zr[p][:, :hc],
+                                    first=first)
+                ops.conv_s1_dgrad(u_q[p][t], w_q_hx[p], add=add_x, out=g_q, w_scratch=w_scratch)        # [g_rh | g_x']
+                rec('g_q', p, t, g_q)
+                ops.gru_gate_grad_r(g, z, g_q[:, :hc], h_in, r, u_r=u_zr[p][t][:, hc:], sum_r=s_zr[p][:, hc:], first=first)
+                rec('add', p, t, g_q)
+                ops.conv_s1_dgrad(u_zr[p][t], w_zr_hx[p], add=g_q, out=out[t], w_scratch=w_scratch)      # [g_h | g_x']
+                rec('out', p, t, out[t])
+                if p > 0:          # hand g_h over to the pass in front; [0 | g_x'] stays behind as its q dgrad's `add`
+                    g, add_x = ops.gru_carry(out[t][:, :hc], out=carry, clear=True), out[t]
+        g_h0 = ops.gru_carry(out[0][:, :hc])
+        if intermediates is not None:
+            intermediates.update(u_zr=u_zr, u_q=u_q, s_zr=s_zr, s_q=s_q, gates=gt)
+        # ---- the context columns, once per pass on the running sums
+        g_c = None
+        for p in range(P):
+            g_c = ops.conv_s1_dgrad(s_zr[p], w_zr_c[p], add=g_c, w_scratch=w_scratch)
+            g_c = ops.conv_s1_dgrad(s_q[p], w_q_c[p], add=g_c, w_scratch=w_scratch)
+        # ---- weight gradients over the M = T N stacked samples, by column block of the raw (Cout, Ch + Cc + Cx', KH, KW)
+        m = T * n
+        xs = x.view(m, cx, h, w)
+        ks = [tuple(z.conv.kernel_size) for z in self.conv_z]
+        ws = E(max(ops.conv_s1_wgrad_workspace(mm, co, ci, h, w, *k) for k in ks for co in (2 * hc, hc)
+                   for mm, ci in ((m, hc), (m, cx), (n, cc))))
+        for p in range(P):
+            groups = ((u_zr[p].view(m, 2 * hc, h, w), s_zr[p], gt['h_in'][p].view(m, hc, h, w), (f'conv_z.{p}.conv', f'conv_r.{p}.conv')),
+                      (u_q[p].view(m, hc, h, w), s_q[p], gt['rh'][p].view(m, hc, h, w), (f'conv_q.{p}.conv',)))
+            for u, s_, state, mods in groups:
+                prev_w = [dst[f'{k}.weight'] for k in mods] if acc else None
+                old = lambda cols: torch.cat([d[:, cols] for d in prev_w], 0).contiguous() if acc else None    # noqa: E731
+                db = torch.cat([dst[f'{k}.bias'] for k in mods], 0) if acc else None
+                dw_h, db = ops.conv_s1_wgrad(u, state, ks[p], dw=old(slice(0, hc)), db=db, accumulate=acc, workspace=ws)
+                dw_c, _ = ops.conv_s1_wgrad(s_, c, ks[p], dw=old(slice(hc, hc + cc)), bias=False, accumulate=acc, workspace=ws)
+                dw_x, _ = ops.conv_s1_wgrad(u, xs, ks[p], dw=old(slice(hc + cc, None)), bias=False, accumulate=acc, workspace=ws)
+                dw = torch.cat([dw_h, dw_c, dw_x], 1)
+                for i, k in enumerate(mods):
+                    rows = slice(i * hc, (i + 1) * hc)
+                    if acc:
+                        grads[f'{k}.weight'], grads[f'{k}.bias'] = dst[f'{k}.weight'].copy_(dw[rows]), dst[f'{k}.bias'].copy_(db[rows])
+                    else:
+                        grads[f'{k}.weight'], grads[f'{k}.bias'] = dw[rows].contiguous(), db[rows].contiguous()
+        return g_h0, g_c, [out[t][:, hc:] for t in range(T)], grads
+
 
 class XHead(HipModule):
     """decoder/raft_decoder.py:256-294."""
@@ -812,6 +969,10 @@ class SCFlowDecoder(HipModule):
         # mask (T, N, 1, h, w) in pose_head_inputs, what heads_backward needs next to hv and dm; implies
         # keep_pose_head_input.  False: nothing is kept, allocated or launched
         self.keep_head_inputs = False
+        # True: every forward also keeps what ConvGRU.backward needs next to hv, in pose_head_inputs: the initial state h0
+        # (N, Ch, h, w), the context c (N, Cc, h, w) and the motion encoder's output x (T, N, 128, h, w) of every
+        # iteration; implies keep_head_inputs.  False: nothing is kept, allocated or launched
+        self.keep_gru_inputs = False
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -840,9 +1001,9 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
             self.pose_tail_inputs = []
-        if self.keep_pose_head_input or self.keep_head_inputs:
+        if self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
             self.pose_head_inputs = {}
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
@@ -850,6 +1011,9 @@ class SCFlowDecoder(HipModule):
         # refiner says it may be consumed (_consume_state); the public forward never mutates
         # its inputs (the reference decoder does not either)
         hx = _as_gru_buffer(h_feat, cxt_feat, hc + cc + 128, _consume_state)
+        if self.keep_gru_inputs:      # before the first iteration rewrites h in place
+            for key, part in (('h0', hx[:, :hc]), ('c', hx[:, hc:hc + cc])):
+                self.pose_head_inputs[key] = torch.empty(part.shape, **f32).copy_(part)
         rot, trans = ref_rotation.contiguous(), ref_translation.contiguous()
         rot0, trans0 = rot, trans
         flow = init_flow
@@ -899,7 +1063,7 @@ class SCFlowDecoder(HipModule):
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
             ys = self.pose_pred._conv_outputs(hv, dm)                              # :218-219
-            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask)
+            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask, xm=hx[:, hc + cc:])
             rot_all, trans_all = self.pose_pred._tail(ys[2])
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
@@ -912,12 +1076,18 @@ class SCFlowDecoder(HipModule):
         return outs
 
     def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False, d_flow: Optional[Tensor] = None,
-                          mask: Optional[Tensor] = None) -> None:
+                          mask: Optional[Tensor] = None, xm: Optional[Tensor] = None) -> None:
         """What the keep flags ask for of iteration ``t``, copies only; no flag: nothing.  ``keep_pose_head_input``:
         ``hv``, ``dm`` and the raw convolution outputs ``ys`` into ``pose_head_inputs``, whose buffers for all iterations
-        the first one allocates; ``keep_head_inputs``: ``d_flow`` and ``mask`` as well.  Any flag: the last of ``ys`` onto
-        ``pose_tail_inputs`` -- a ``clone`` where later iterations rewrite that buffer."""
-        if self.keep_head_inputs:
+        the first one allocates; ``keep_head_inputs``: ``d_flow`` and ``mask`` as well; ``keep_gru_inputs``: the motion
+        features ``xm`` (the GRU buffer's last 128 channels, rewritten by every iteration) as ``x`` as well.  Any flag: the
+        last of ``ys`` onto ``pose_tail_inputs`` -- a ``clone`` where later iterations rewrite that buffer."""
+        if self.keep_gru_inputs:
+            kept = self.pose_head_inputs
+            if t == 0:
+                kept['x'] = torch.empty((self.iters,) + tuple(xm.shape), dtype=torch.float32, device=hv.device)
+            kept['x'][t].copy_(xm)
+        if self.keep_head_inputs or self.keep_gru_inputs:
             kept = self.pose_head_inputs
             if t == 0:
                 f32 = dict(dtype=torch.float32, device=hv.device)
@@ -925,7 +1095,7 @@ class SCFlowDecoder(HipModule):
                 kept['mask'] = torch.empty((self.iters,) + tuple(mask.shape), **f32)
             kept['d_flow'][t].copy_(d_flow)
             kept['mask'][t].copy_(mask)
-        if self.keep_pose_head_input or self.keep_head_inputs:
+        if self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
             kept = self.pose_head_inputs
             if t == 0:
                 f32 = dict(dtype=torch.float32, device=hv.device)
@@ -938,7 +1108,7 @@ class SCFlowDecoder(HipModule):
             kept['dm'][t].copy_(dm)
             for i, y in enumerate(ys):
                 kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
             self.pose_tail_inputs.append(ys[2].clone() if clone else ys[2])
 
 
@@ -1125,6 +1295,24 @@ def _scflow_heads_backward(self, saved: dict, g_hvs: Sequence[Tensor], g_dms: Se
 SCFlowDecoder.heads_backward = _scflow_heads_backward
 
 
+def _scflow_gru_backward(self, saved: dict, g_hidden_states: Sequence[Tensor], param_grads: Optional[dict] = None):
+    """``ConvGRU.backward`` of ``self.gru`` on what a forward under ``keep_gru_inputs`` left in ``pose_head_inputs``, with
+    the decoder's channel split checked (``c``: ``cxt_channels``, ``x``: the motion encoder's 126 + 2) -> (``g_h0``,
+    ``g_context``, ``g_motion_features``, ``param_grads``), the parameter names relative to ``self.gru``."""
+    what = 'gru_backward'
+    try:
+        c, x = saved['c'], saved['x']
+    except (KeyError, TypeError):
+        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_gru_inputs (h0, c, x, hv)') from None
+    want = (self.cxt_channels, self.gru.x_channels - self.cxt_channels)
+    if c.dim() != 4 or x.dim() != 5 or (c.shape[1], x.shape[2]) != want:
+        raise _lib_error(f'{what}: c and x must hold {want[0]} and {want[1]} channels, got {tuple(c.shape)} and {tuple(x.shape)}')
+    return self.gru.backward(saved, g_hidden_states, param_grads)
+
+
+SCFlowDecoder.gru_backward = _scflow_gru_backward
+
+
 def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
                       invalid_flow_num, overlap):
     """the refinement loop through ``scf_scflow_iteration``: every scratch buffer and convolution
@@ -1238,7 +1426,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask)
+        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask, xm=xm)
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already

@@ -2355,3 +2355,76 @@ def conv_s1_wgrad(g: Tensor, x: Tensor, kernel_size, dw: Optional[Tensor] = None
                                              int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m, cout, cin,
                                              h, w, kh, kw, _stream()), 'scf_conv_s1_wgrad')
     return dw, db
+
+
+# ------------------------------------------------- gate arithmetic of the ConvGRU backward (gru_grad.hip)
+def _gg_rows(what: str, shape, named) -> list:
+    """(pointer, sample stride) of every (M, C, H, W) operand of a gate kernel; None stays (None, 0)."""
+    out = []
+    for name, t in named:
+        out.extend((None, 0) if t is None else _s1_map(t, what, name, shape))
+    return out
+
+
+def _gg_shape(what: str, g: Tensor) -> Tuple[int, int]:
+    if g.dim() != 4 or g.numel() == 0:
+        raise _lib.ScflowHipError(f'{what}: g must be a non-empty (M, C, H, W) tensor, got {tuple(g.shape)}')
+    return g.shape[0], g.shape[1] * g.shape[2] * g.shape[3]
+
+
+def gru_gate_grad_q(g: Tensor, h: Tensor, z: Tensor, q: Tensor, u_q: Optional[Tensor] = None, u_z: Optional[Tensor] = None,
+                    sum_q: Optional[Tensor] = None, sum_z: Optional[Tensor] = None, first: bool = True
+                    ) -> Tuple[Tensor, Tensor]:
+    """``u_q = g z (1 - q^2)``, ``u_z = g (q - h) z (1 - z)`` of one GRU pass (``scf_gru_gate_grad_q``; the order of
+    operations is the header's).  Every operand (M, C, H, W), contiguous up to a channel slice.  ``sum_q`` / ``sum_z``:
+    running sums, ``sum = u`` with ``first`` and ``sum + u`` otherwise."""
+    what = 'gru_gate_grad_q'
+    m, n = _gg_shape(what, g)
+    shape = tuple(g.shape)
+    if u_q is None:
+        u_q = torch.empty(shape, dtype=torch.float32, device=g.device)
+    if u_z is None:
+        u_z = torch.empty(shape, dtype=torch.float32, device=g.device)
+    args = _gg_rows(what, shape, (('g', g), ('h', h), ('z', z), ('q', q), ('u_q', u_q), ('u_z', u_z), ('sum_q', sum_q),
+                                  ('sum_z', sum_z)))
+    _lib.check(_lib.load().scf_gru_gate_grad_q(*args, int(bool(first)), m, n, _stream()), 'scf_gru_gate_grad_q')
+    return u_q, u_z
+
+
+def gru_gate_grad_r(g: Tensor, z: Tensor, g_rh: Tensor, h: Tensor, r: Tensor, u_r: Optional[Tensor] = None,
+                    sum_r: Optional[Tensor] = None, first: bool = True) -> Tuple[Tensor, Tensor]:
+    """``u_r = g_rh h r (1 - r)`` and ``g_h_direct = g (1 - z) + g_rh r``, the latter written IN PLACE over ``g_rh``
+    (``scf_gru_gate_grad_r``) -> (u_r, g_rh).  Operands as in ``gru_gate_grad_q``."""
+    what = 'gru_gate_grad_r'
+    m, n = _gg_shape(what, g)
+    shape = tuple(g.shape)
+    if u_r is None:
+        u_r = torch.empty(shape, dtype=torch.float32, device=g.device)
+    args = _gg_rows(what, shape, (('g', g), ('z', z), ('g_rh', g_rh), ('h', h), ('r', r), ('u_r', u_r), ('sum_r', sum_r)))
+    _lib.check(_lib.load().scf_gru_gate_grad_r(*args, int(bool(first)), m, n, _stream()), 'scf_gru_gate_grad_r')
+    return u_r, g_rh
+
+
+def gru_carry(src: Tensor, add: Optional[Tensor] = None, out: Optional[Tensor] = None, clear: bool = False) -> Tensor:
+    """``out = src + add`` (``add`` None: a copy); ``clear``: ``src`` is then set to +0 (``scf_gru_carry``)."""
+    what = 'gru_carry'
+    m, n = _gg_shape(what, src)
+    shape = tuple(src.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=src.device)
+    args = _gg_rows(what, shape, (('src', src), ('add', add), ('out', out)))
+    _lib.check(_lib.load().scf_gru_carry(*args, int(bool(clear)), m, n, _stream()), 'scf_gru_carry')
+    return out
+
+
+def gru_gate_state(h: Tensor, gate: Tensor, q: Optional[Tensor] = None, out: Optional[Tensor] = None) -> Tensor:
+    """``gate * h`` (``q`` None: the forward's ``r h``) or ``(1 - gate) h + gate q`` (its state update), as the backward
+    recomputes them (``scf_gru_gate_state``)."""
+    what = 'gru_gate_state'
+    m, n = _gg_shape(what, h)
+    shape = tuple(h.shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=h.device)
+    args = _gg_rows(what, shape, (('h', h), ('gate', gate), ('q', q), ('out', out)))
+    _lib.check(_lib.load().scf_gru_gate_state(*args, m, n, _stream()), 'scf_gru_gate_state')
+    return out

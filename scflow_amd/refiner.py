@@ -228,7 +228,7 @@ class _RenderingRefiner:
 
 
 # how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do
-_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head', 'decoder_heads')
+_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head', 'decoder_heads', 'gru')
 
 
 @REFINERS.register_module()
@@ -417,16 +417,31 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         (``SCFlowDecoder.heads_backward``) -> the same tuple, ``grads`` with one more key: ``decoder_heads`` =
         ``dict(hidden_states, delta_flow_preds, mask_logits)``, a list per key over the iterations.  ``hidden_states[t]`` is
         d loss / d ``hv_t`` (N, 128, h, w) through iteration t's OWN heads, encoders and pose head: the cotangent the GRU
-        backward will add the next iteration's to.  ``delta_flow_preds[t]`` is the complete d loss / d ``d_flow_t`` (the
+        backward adds the next iteration's to.  ``delta_flow_preds[t]`` is the complete d loss / d ``d_flow_t`` (the
         tail's plus the delta-flow encoder's), ``mask_logits[t]`` the complete d loss / d (pre-sigmoid mask) of iteration t --
         except that under ``mask_flow`` / ``mask_corr`` without ``detach_mask`` the path from ``mask_t`` into iteration
         t + 1's motion encoder is still missing.  ``params`` is extended by the 16 weights and biases of
         ``decoder.flow_pred``, ``decoder.mask_pred``, ``decoder.delta_flow_encoder`` and ``decoder.mask_encoder``, summed over
         the iterations: every parameter downstream of the GRU state now has a gradient.  The values are the bits of
         ``loss()``; every entry ``loss_and_pose_head_grads()`` returns keeps its bits and its key (the top-level
-        ``delta_flow_preds`` / ``masks`` stay the tail's partial cotangents).  The GRU, the lookup, the motion encoder
-        and the image encoders have no backward yet."""
+        ``delta_flow_preds`` / ``masks`` stay the tail's partial cotangents).  ``loss_and_gru_grads()`` carries
+        ``hidden_states`` through the GRU; the lookup, the motion encoder and the image encoders have no backward yet."""
         return self._loss(data_batch, data, 'decoder_heads')
+
+    def loss_and_gru_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_decoder_head_grads()`` carried through the GRU by a reverse scan over the iterations
+        (``SCFlowDecoder.gru_backward``) -> the same tuple, ``grads`` with one more key: ``gru`` =
+        ``dict(initial_hidden, context, motion_features)``: d loss / d ``h0`` (N, 128, h, w), the hidden state the context
+        encoder hands the decoder; d loss / d ``c`` (N, 128, h, w), its context features, summed over iterations and
+        passes; and the list over the iterations of d loss / d ``x_t`` (N, 128, h, w), the motion encoder's 126 channels
+        and the 2 flow channels behind them.  ``params`` is extended by the ``decoder.gru.*`` gradients (12 for
+        ``'SeqConv'``, 6 for ``'Conv'``), summed over the iterations.  The values are the bits of ``loss()``; every entry
+        ``loss_and_decoder_head_grads()`` returns keeps its bits and its key.  Still missing: the backward of the motion
+        encoder, the lookup and the image encoders -- ``initial_hidden``, ``context`` and ``motion_features`` are where
+        they will start -- and, under ``detach_flow=False`` and under ``mask_flow`` / ``mask_corr`` without
+        ``detach_mask``, the path from ``motion_features[t]`` back into iteration t - 1 (its flow and its mask), which
+        belongs to the motion-encoder backward: ``decoder_heads`` and the head gradients do not contain it."""
+        return self._loss(data_batch, data, 'gru')
 
     def _loss(self, data_batch, data, depth):
         from . import losses as L
@@ -439,6 +454,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         labels, valid = data['labels'], data['rendered_masks']
         dec = self.decoder
         kept, kept_head, kept_heads = dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs
+        kept_gru = dec.keep_gru_inputs
+        dec.keep_gru_inputs = kept_gru or level >= at('gru')
         dec.keep_pose_tail_input = kept or level >= at('pose_tail')
         dec.keep_pose_head_input = kept_head or level >= at('pose_head')
         dec.keep_head_inputs = kept_heads or level >= at('decoder_heads')
@@ -447,6 +464,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                  data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
         finally:
             dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs = kept, kept_head, kept_heads
+            dec.keep_gru_inputs = kept_gru
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
@@ -497,6 +515,10 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                                                   grads['delta_flow_preds'], grads['masks'])
                 grads['decoder_heads'] = dict(hidden_states=g_h, delta_flow_preds=g_df, mask_logits=g_ml)
                 grads['params'].update(('decoder.' + key, val) for key, val in head_params.items())
+                if level >= at('gru'):
+                    g_h0, g_c, g_x, gru_params = dec.gru_backward(dec.pose_head_inputs, g_h)
+                    grads['gru'] = dict(initial_hidden=g_h0, context=g_c, motion_features=g_x)
+                    grads['params'].update(('decoder.gru.' + key, val) for key, val in gru_params.items())
         return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):
@@ -506,7 +528,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                       'loss_and_head_grads() carries them to the head outputs of every iteration, '
                                       'loss_and_pose_tail_grads() through the fully connected tail of the pose head, '
                                       'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm, '
-                                      'loss_and_decoder_head_grads() through the XHeads and the delta-flow / mask encoders to hv')
+                                      'loss_and_decoder_head_grads() through the XHeads and the delta-flow / mask encoders to hv, '
+                                      'loss_and_gru_grads() through the GRU to h0, the context and the motion features')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
