@@ -1059,6 +1059,29 @@ int scf_gru_carry(float* src, int64_t src_stride, const float* add, int64_t add_
 int scf_gru_gate_state(const float* h, int64_t h_stride, const float* gate, int64_t gate_stride, const float* q,
                        int64_t q_stride, float* out, int64_t out_stride, int M, int64_t n, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Adjoint of scf_corr_lookup with respect to the pyramid, carried back to level 0 through the 2x2 / stride-2 average
+ * pools of scf_corr_build (corr_lookup_grad.hip).  g_corr (T, N, L (2r+1)^2, h, w): the cotangents of the lookup outputs
+ * of T iterations in the forward's channel order (channel (2r+1)^2 l + (2r+1) a + b: x-offset a - r, y-offset b - r);
+ * flow (T, N, 2, h, w): the flow each lookup was taken at; mask: NULL or (T, N, 1, h, w), a per-query factor on g_corr
+ * (one rounding); g_vol (N h w, h, w) row-major: d loss / d level 0, summed over T -- every element is written (no
+ * pre-zeroing), with accumulate != 0 the previous value is added last.  The pyramid is not read.
+ * With x0, y0, nw, ne, sw, se of the forward's window centre of (query, level, iteration), i = jx - x0, k = jy - y0 and
+ * G[a, b] = mask g_corr of tap (a, b), +0 outside [0, 2r]^2:
+ *   S_l[jy, jx] = sum_t  nw G[i, k] + ne G[i - 1, k] + sw G[i, k - 1] + se G[i - 1, k - 1]
+ *   g_vol[q, jy, jx] = sum_l 4^-l S_l[jy >> l, jx >> l]   over the l with (jy >> l) < (h >> l) and (jx >> l) < (w >> l)
+ * A size-1 axis: cell 0 takes every offset of that axis.  A query with a NaN / inf flow at iteration t contributes zero
+ * at t (its window is all padding).  Order: S_l from +0, t ascending, offsets of a size-1 x axis then of a size-1 y
+ * axis ascending, the four terms as one fma chain in nw, ne, sw, se order; levels ascending, v = fma(4^-l, S_l, v)
+ * from v = S_0.  No atomics, allocation or synchronisation; bit-identical from run to run; a sample's result does not
+ * depend on N.  r <= 4 with a query's accumulators inside 64 KB of LDS: staged through LDS; else one thread per element.
+ * A null g_corr / flow / g_vol, a non-positive size, r < 1, an empty level: SCF_EINVAL; L > SCF_MAX_LEVELS or
+ * T > SCF_TAIL_MAX_T: SCF_EUNSUPPORTED; nothing launched or written.  Added without a version bump; the presence of
+ * the symbol marks the feature.
+ * --------------------------------------------------------------------------------- */
+int scf_corr_lookup_grad(const float* g_corr, const float* flow, const float* mask, float* g_vol, int accumulate, int T,
+                         int N, int h, int w, int r, int L, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

@@ -371,26 +371,130 @@ class MotionEncoder(HipModule):
             if overlap:
                 raise ValueError('overlap=True needs a cf buffer allocated before the fork point')
             cf = torch.empty((n, 256, h, w), dtype=torch.float32, device=dev)
+        self.branches(corr, flow, cf, overlap=overlap, fork=fork)
+        self.out_net[0](cf, out=out[:, :126])
+        ops.copy_channels(flow, out[:, 126:128])
+        return out
+
+    def branches(self, corr: Tensor, flow: Tensor, cf: Tensor, overlap: bool = False, fork=None,
+                 c1: Optional[Tensor] = None, f1: Optional[Tensor] = None) -> Tensor:
+        """the correlation and the flow branch of ``forward`` into ``cf`` (N, 256, h, w) = [corr_net (192) | flow_net (64)];
+        ``c1`` (N, 256, h, w) / ``f1`` (N, 128, h, w): where the first layers' outputs go when the caller wants them (the
+        backward's recomputation), else scratch"""
         if not overlap and 'flow' in ops.PAIR_BRANCHES and ops._CONV_EVENTS is None:
             # r6: the flow branch rides in the correlation branch's launches, layer by layer (ops.conv2d_pair: one launch where
             # the two grids need fewer rounds of resident blocks together, else one after the other; same bits)
             cn, fn = self.corr_net, self.flow_net
-            c1, f1 = ops.conv2d_pair((cn[0].packed, corr, dict(act=cn[0].act)), (fn[0].packed, flow, dict(act=fn[0].act)))
+            kc, kf = dict(act=cn[0].act), dict(act=fn[0].act)
+            if c1 is not None:
+                kc['out'] = c1
+            if f1 is not None:
+                kf['out'] = f1
+            c1, f1 = ops.conv2d_pair((cn[0].packed, corr, kc), (fn[0].packed, flow, kf))
             ops.conv2d_pair((cn[1].packed, c1, dict(out=cf[:, :192], act=cn[1].act)),
                             (fn[1].packed, f1, dict(out=cf[:, 192:], act=fn[1].act)))
             del c1, f1
         else:
             br = ops.side_stream(overlap, after=fork)
             with br:
-                f1 = self.flow_net[0](flow)
+                f1 = self.flow_net[0](flow, out=f1)
                 self.flow_net[1](f1, out=cf[:, 192:])
                 del f1
-            c1 = self.corr_net[0](corr)
+            c1 = self.corr_net[0](corr, out=c1)
             self.corr_net[1](c1, out=cf[:, :192])
             br.join()
-        self.out_net[0](cf, out=out[:, :126])
-        ops.copy_channels(flow, out[:, 126:128])
-        return out
+        return cf
+
+    # ---- backward (DESIGN.md 4.12): five stride-1 convolutions, no recurrence ----
+    def param_names(self, prefix: str = '') -> Tuple[str, ...]:
+        """the encoder's ten parameters as ``named_parameters()`` keys them, behind ``prefix``"""
+        return tuple(f'{prefix}{m}.conv.{k}' for m in ('corr_net.0', 'corr_net.1', 'flow_net.0', 'flow_net.1', 'out_net.0')
+                     for k in ('weight', 'bias'))
+
+    def backward(self, saved: dict, g_motion_features: Sequence[Tensor], param_grads: Optional[dict] = None,
+                 intermediates: Optional[dict] = None, prefix: str = ''):
+        """Backward of the motion encoder (raft_decoder.py:152-166) for the T iterations of a pass at once, M = T N stacked
+        samples, one launch per stage.
+
+        ``saved``: ``corr`` (T, N, L (2r+1)^2, h, w), the looked-up (and, under ``mask_corr``, masked) correlation of every
+        iteration, and ``x`` (T, N, 128, h, w), the encoder's output [out_net (126, post-activation) | flow_in (2)] that
+        ``SCFlowDecoder.keep_gru_inputs`` keeps.  ``g_motion_features``: T cotangents at ``x_t`` (``ConvGRU.backward`` returns
+        them).  -> (``g_corr`` (T, N, L (2r+1)^2, h, w): the cotangents at ``corr``; ``g_flow_inputs``: T cotangents at the
+        encoder's flow input (N, 2, h, w), the pass-through channels included; ``param_grads``: the gradients of the ten
+        parameters summed over all T N samples, keyed as in ``named_parameters()`` behind ``prefix``).  A dict passed in is
+        accumulated into (entries it lacks are created; some but not all of these entries: an error).
+
+        The hidden activations ``c1`` (256), ``f1`` (128) and ``cf`` (256) are recomputed into stacked buffers by the
+        forward's OWN launches (``branches``), one iteration at a time at the forward's batch, so dispatch and bits are the
+        forward's.  Chain per stacked sample: act_grad on ``g_x[:, :126]``; wgrad + dgrad of out_net (ReLU mask of ``cf``
+        in the epilogue); corr_net.1 and flow_net.1 on the two column blocks of ``g_cf``; corr_net.0 (1x1) down to
+        ``g_corr``; flow_net.0 (7x7) with the pass-through cotangent ``g_x[:, 126:128]`` added.
+
+        ``intermediates``: a dict that receives every launch's operands and results (None: nothing is kept)."""
+        what = 'MotionEncoder.backward'
+        T = len(g_motion_features)
+        if T == 0 or T > ops.TAIL_MAX_T:
+            raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at x per iteration')
+        try:
+            corr, x = saved['corr'], saved['x']
+        except (KeyError, TypeError):
+            raise _lib_error(f'{what}: saved holds corr (T, N, K, h, w) and x (T, N, 128, h, w)') from None
+        cn, fn, on = self.corr_net, self.flow_net, self.out_net
+        co = on[0].conv.out_channels                                  # 126
+        if x.dim() != 5 or x.shape[0] != T or x.shape[2] != co + 2 or not x.is_contiguous():
+            raise _lib_error(f'{what}: x must be a contiguous ({T}, N, {co + 2}, h, w) tensor, got {tuple(x.shape)}')
+        n, _, h, w = x.shape[1:]
+        kc = cn[0].conv.in_channels
+        if tuple(corr.shape) != (T, n, kc, h, w) or not corr.is_contiguous():
+            raise _lib_error(f'{what}: corr must be a contiguous {(T, n, kc, h, w)} tensor, got {tuple(corr.shape)}')
+        if any(tuple(g.shape) != (n, co + 2, h, w) for g in g_motion_features):
+            raise _lib_error(f'{what}: g_motion_features are {(n, co + 2, h, w)} tensors')
+        act = cn[0].act
+        if any(b.act != act for b in (cn[1], fn[0], fn[1], on[0])) or act not in (ACT_NONE, ACT_RELU):
+            raise NotImplementedError('MotionEncoder.backward: ReLU or no activation')
+        names = self.param_names(prefix)
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the motion encoder\'s gradients', names, param_grads)
+        dst = dict(zip(names, dst))
+        m = T * n
+        E = lambda *shape: torch.empty(shape, dtype=torch.float32, device=x.device)       # noqa: E731
+        c_c1, c_f1 = cn[0].conv.out_channels, fn[0].conv.out_channels
+        c_cc, c_cf = cn[1].conv.out_channels, fn[1].conv.out_channels
+        # ---- the forward's own launches, an iteration at a time: c1, f1, cf in the forward's bits
+        c1, f1, cf = E(T, n, c_c1, h, w), E(T, n, c_f1, h, w), E(T, n, c_cc + c_cf, h, w)
+        for t in range(T):
+            self.branches(corr[t], x[t][:, co:], cf[t], c1=c1[t], f1=f1[t])
+        g_x = (g_motion_features[0].contiguous() if T == 1 else torch.stack(list(g_motion_features))).view(m, co + 2, h, w)
+        x_, corr_ = x.view(m, co + 2, h, w), corr.view(m, kc, h, w)
+        c1_, f1_, cf_ = c1.view(m, c_c1, h, w), f1.view(m, c_f1, h, w), cf.view(m, c_cc + c_cf, h, w)
+        convs = (on[0].conv, cn[1].conv, cn[0].conv, fn[1].conv, fn[0].conv)
+        ws = E(max(ops.conv_s1_wgrad_workspace(m, cv.out_channels, cv.in_channels, h, w, *cv.kernel_size) for cv in convs))
+        w_scratch = E(max(cv.weight.numel() for cv in convs))
+        a_or_none = lambda a: a if act != ACT_NONE else None                              # noqa: E731
+
+        def wgrad(g, xin, name, conv):
+            key = f'{prefix}{name}.conv'
+            dw, db = ops.conv_s1_wgrad(g, xin, tuple(conv.kernel_size), dw=dst[f'{key}.weight'], db=dst[f'{key}.bias'],
+                                       accumulate=acc, workspace=ws)
+            grads[f'{key}.weight'], grads[f'{key}.bias'] = dw, db
+
+        # 1. out_net
+        u = ops.act_grad(g_x[:, :co], a_or_none(x_[:, :co]), act)
+        wgrad(u, cf_, 'out_net.0', on[0].conv)
+        g_cf = ops.conv_s1_dgrad(u, on[0].conv.weight, a=a_or_none(cf_), act=act, w_scratch=w_scratch)
+        # 2. correlation branch
+        wgrad(g_cf[:, :c_cc], c1_, 'corr_net.1', cn[1].conv)
+        g_c1 = ops.conv_s1_dgrad(g_cf[:, :c_cc], cn[1].conv.weight, a=a_or_none(c1_), act=act, w_scratch=w_scratch)
+        wgrad(g_c1, corr_, 'corr_net.0', cn[0].conv)
+        g_corr = ops.conv_s1_dgrad(g_c1, cn[0].conv.weight, w_scratch=w_scratch)
+        # 3. flow branch: the pass-through channels' cotangent joins at the flow input
+        wgrad(g_cf[:, c_cc:], f1_, 'flow_net.1', fn[1].conv)
+        g_f1 = ops.conv_s1_dgrad(g_cf[:, c_cc:], fn[1].conv.weight, a=a_or_none(f1_), act=act, w_scratch=w_scratch)
+        wgrad(g_f1, x_[:, co:], 'flow_net.0', fn[0].conv)
+        g_fl = ops.conv_s1_dgrad(g_f1, fn[0].conv.weight, add=g_x[:, co:])
+        if intermediates is not None:
+            intermediates.update(c1=c1, f1=f1, cf=cf, g_x=g_x, u=u, g_cf=g_cf, g_c1=g_c1, g_f1=g_f1, g_corr=g_corr, g_flow_in=g_fl)
+        g_fl = g_fl.view(T, n, 2, h, w)
+        return g_corr.view(T, n, kc, h, w), [g_fl[t] for t in range(T)], grads
 
 
 class ConvGRU(HipModule):
@@ -929,6 +1033,7 @@ class SCFlowDecoder(HipModule):
         self.mask_flow, self.mask_corr = bool(mask_flow), bool(mask_corr)      # scflow_decoder.py:199-205
         # scflow_decoder.py:192-193, 232-233: autograd only -- the forward ignores them, tail_backward reads them
         self.detach_flow, self.detach_pose = bool(detach_flow), bool(detach_pose)
+        self.detach_mask = bool(detach_mask)      # scflow_decoder.py:188-190: autograd only, loss_and_motion_grads reads it
         # pose.py:137-141: 'exp' -> t_z / exp(d_z); ANY other value takes the reference's else branch t_z * (d_z + 1)
         self.depth_transform = depth_transform
         self.detach_depth_for_xy = detach_depth_for_xy      # autograd only (pose.py:142-147): tail_backward reads it
@@ -973,6 +1078,13 @@ class SCFlowDecoder(HipModule):
         # (N, Ch, h, w), the context c (N, Cc, h, w) and the motion encoder's output x (T, N, 128, h, w) of every
         # iteration; implies keep_head_inputs.  False: nothing is kept, allocated or launched
         self.keep_gru_inputs = False
+        # True: every forward also keeps what motion_backward needs next to x and mask, in pose_head_inputs: the low-resolution
+        # flow flow_lr (T, N, 2, h, w) every lookup was taken at, the pyramid (the list itself: no copy, nothing rewrites
+        # it) and its layout mask tiled; implies keep_gru_inputs.  False: nothing is kept, allocated or launched
+        self.keep_motion_inputs = False
+
+    def _keeps_gru(self) -> bool:
+        return self.keep_gru_inputs or self.keep_motion_inputs
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -1001,17 +1113,19 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
             self.pose_tail_inputs = []
-        if self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
+        if self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
             self.pose_head_inputs = {}
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
+        if self.keep_motion_inputs:
+            self.pose_head_inputs['pyramid'], self.pose_head_inputs['tiled'] = pyramid, tiled
         # GRU buffer [h | cxt | motion(126) | flow(2)]: the caller's own buffer only when the
         # refiner says it may be consumed (_consume_state); the public forward never mutates
         # its inputs (the reference decoder does not either)
         hx = _as_gru_buffer(h_feat, cxt_feat, hc + cc + 128, _consume_state)
-        if self.keep_gru_inputs:      # before the first iteration rewrites h in place
+        if self._keeps_gru():      # before the first iteration rewrites h in place
             for key, part in (('h0', hx[:, :hc]), ('c', hx[:, hc:hc + cc])):
                 self.pose_head_inputs[key] = torch.empty(part.shape, **f32).copy_(part)
         rot, trans = ref_rotation.contiguous(), ref_translation.contiguous()
@@ -1063,7 +1177,7 @@ class SCFlowDecoder(HipModule):
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
             ys = self.pose_pred._conv_outputs(hv, dm)                              # :218-219
-            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask, xm=hx[:, hc + cc:])
+            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask, xm=hx[:, hc + cc:], flow_lr=flow_lr)
             rot_all, trans_all = self.pose_pred._tail(ys[2])
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
@@ -1076,18 +1190,24 @@ class SCFlowDecoder(HipModule):
         return outs
 
     def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False, d_flow: Optional[Tensor] = None,
-                          mask: Optional[Tensor] = None, xm: Optional[Tensor] = None) -> None:
+                          mask: Optional[Tensor] = None, xm: Optional[Tensor] = None, flow_lr: Optional[Tensor] = None) -> None:
         """What the keep flags ask for of iteration ``t``, copies only; no flag: nothing.  ``keep_pose_head_input``:
         ``hv``, ``dm`` and the raw convolution outputs ``ys`` into ``pose_head_inputs``, whose buffers for all iterations
         the first one allocates; ``keep_head_inputs``: ``d_flow`` and ``mask`` as well; ``keep_gru_inputs``: the motion
-        features ``xm`` (the GRU buffer's last 128 channels, rewritten by every iteration) as ``x`` as well.  Any flag: the
+        features ``xm`` (the GRU buffer's last 128 channels, rewritten by every iteration) as ``x`` as well;
+        ``keep_motion_inputs``: ``flow_lr`` (the C loop's scratch buffer of that name) as well.  Any flag: the
         last of ``ys`` onto ``pose_tail_inputs`` -- a ``clone`` where later iterations rewrite that buffer."""
-        if self.keep_gru_inputs:
+        if self.keep_motion_inputs:
+            kept = self.pose_head_inputs
+            if t == 0:
+                kept['flow_lr'] = torch.empty((self.iters,) + tuple(flow_lr.shape), dtype=torch.float32, device=hv.device)
+            kept['flow_lr'][t].copy_(flow_lr)
+        if self._keeps_gru():
             kept = self.pose_head_inputs
             if t == 0:
                 kept['x'] = torch.empty((self.iters,) + tuple(xm.shape), dtype=torch.float32, device=hv.device)
             kept['x'][t].copy_(xm)
-        if self.keep_head_inputs or self.keep_gru_inputs:
+        if self.keep_head_inputs or self._keeps_gru():
             kept = self.pose_head_inputs
             if t == 0:
                 f32 = dict(dtype=torch.float32, device=hv.device)
@@ -1095,7 +1215,7 @@ class SCFlowDecoder(HipModule):
                 kept['mask'] = torch.empty((self.iters,) + tuple(mask.shape), **f32)
             kept['d_flow'][t].copy_(d_flow)
             kept['mask'][t].copy_(mask)
-        if self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
+        if self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
             kept = self.pose_head_inputs
             if t == 0:
                 f32 = dict(dtype=torch.float32, device=hv.device)
@@ -1108,7 +1228,7 @@ class SCFlowDecoder(HipModule):
             kept['dm'][t].copy_(dm)
             for i, y in enumerate(ys):
                 kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self.keep_gru_inputs:
+        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
             self.pose_tail_inputs.append(ys[2].clone() if clone else ys[2])
 
 
@@ -1313,6 +1433,64 @@ def _scflow_gru_backward(self, saved: dict, g_hidden_states: Sequence[Tensor], p
 SCFlowDecoder.gru_backward = _scflow_gru_backward
 
 
+def _scflow_motion_backward(self, saved: dict, g_motion_features: Sequence[Tensor], param_grads: Optional[dict] = None,
+                            intermediates: Optional[dict] = None):
+    """Backward of the motion encoder and of the correlation lookup with respect to the pyramid (scflow_decoder.py:196-206)
+    for the T iterations of a pass at once.
+
+    ``saved``: what a forward under ``keep_motion_inputs`` left in ``pose_head_inputs``: ``x`` (T, N, 128, h, w), ``flow_lr``
+    (T, N, 2, h, w), the ``pyramid`` list with its layout mask ``tiled`` and, under ``mask_corr``, ``mask`` (T, N, 1, h, w).
+    ``g_motion_features``: the T cotangents at ``x_t`` that ``gru_backward`` returns.  -> (``g_vol`` (N h w, h, w): d loss / d
+    level 0 of the correlation pyramid, summed over the iterations, the pooling adjoints of the other levels folded in;
+    ``g_flow_inputs``: T cotangents at the encoder's flow input (``flow_lr``, times the previous mask under ``mask_flow``) --
+    where a backward through the flow recurrence (``detach_flow=False``) would start; ``param_grads``: the ten
+    ``encoder.*`` gradients summed over all T N samples, keyed as in ``named_parameters()``; a dict passed in is accumulated
+    into, a partial one is an error).
+
+    ``corr_t`` is recomputed by the forward's own lookup launch on the kept pyramid (and ``mul_mask`` under ``mask_corr``),
+    then ``MotionEncoder.backward``, then ``ops.corr_lookup_grad`` on the stacked ``g_corr`` (with the previous iteration's
+    mask -- ones before the first -- as its per-query factor under ``mask_corr``: the product's adjoint under
+    ``detach_mask``).  The lookup's derivative with respect to its coordinates is NOT taken: under ``detach_flow`` nothing
+    reads it."""
+    what = 'motion_backward'
+    T = len(g_motion_features)
+    if T == 0 or T > ops.TAIL_MAX_T:
+        raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at x per iteration')
+    try:
+        x, flow_lr, pyramid, tiled = (saved[k] for k in ('x', 'flow_lr', 'pyramid', 'tiled'))
+        mask = saved['mask'] if self.mask_corr else None
+    except (KeyError, TypeError):
+        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_motion_inputs (x, flow_lr, pyramid, '
+                         'tiled, mask)') from None
+    if x.dim() != 5 or x.shape[0] != T or not x.is_contiguous():
+        raise _lib_error(f'{what}: x must be a contiguous ({T}, N, 128, h, w) tensor, got {tuple(x.shape)}')
+    n, _, h, w = x.shape[1:]
+    if tuple(flow_lr.shape) != (T, n, 2, h, w) or not flow_lr.is_contiguous():
+        raise _lib_error(f'{what}: flow_lr must be a contiguous {(T, n, 2, h, w)} tensor, got {tuple(flow_lr.shape)}')
+    if len(pyramid) != self.num_levels:
+        raise _lib_error(f'{what}: the pyramid has {len(pyramid)} levels, the decoder {self.num_levels}')
+    kch = self.num_levels * (2 * self.radius + 1) ** 2
+    corr = torch.empty((T, n, kch, h, w), dtype=torch.float32, device=x.device)
+    mask_prev = None
+    if self.mask_corr:
+        if tuple(mask.shape) != (T, n, 1, h, w) or not mask.is_contiguous():
+            raise _lib_error(f'{what}: mask must be a contiguous {(T, n, 1, h, w)} tensor, got {tuple(mask.shape)}')
+        mask_prev = torch.cat([torch.ones_like(mask[:1]), mask[:-1]], 0)
+    for t in range(T):
+        ops.corr_lookup(pyramid, flow_lr[t], self.radius, out=corr[t], tiled_levels=tiled)
+        if self.mask_corr:
+            ops.mul_mask(corr[t], mask_prev[t], out=corr[t])
+    g_corr, g_flow_inputs, grads = self.encoder.backward(dict(corr=corr, x=x), g_motion_features, param_grads, intermediates,
+                                                         prefix='encoder.')
+    g_vol = ops.corr_lookup_grad(g_corr, flow_lr, mask_prev, self.radius, self.num_levels)
+    if intermediates is not None:
+        intermediates.update(corr=corr, mask_prev=mask_prev)
+    return g_vol, g_flow_inputs, grads
+
+
+SCFlowDecoder.motion_backward = _scflow_motion_backward
+
+
 def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
                       invalid_flow_num, overlap):
     """the refinement loop through ``scf_scflow_iteration``: every scratch buffer and convolution
@@ -1426,7 +1604,7 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask, xm=xm)
+        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask, xm=xm, flow_lr=flow_lr)
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already

@@ -1026,6 +1026,50 @@ def corr_lookup(pyramid: Sequence[Tensor], flow: Tensor, radius: int = 4,
     return out
 
 
+def corr_lookup_grad(g_corr: Tensor, flow: Tensor, mask: Optional[Tensor] = None, radius: int = 4, num_levels: int = 4,
+                     out: Optional[Tensor] = None, accumulate: bool = False) -> Tensor:
+    """Adjoint of ``corr_lookup`` with respect to the pyramid, folded through the average pools to level 0
+    (``scf_corr_lookup_grad``): ``g_corr`` (T, N, L (2r+1)^2, h, w), the cotangents of the lookup outputs of T iterations;
+    ``flow`` (T, N, 2, h, w), the flow of each lookup; ``mask`` None or (T, N, 1, h, w), a per-query factor on ``g_corr``
+    -> ``g_vol`` (N h w, h, w), d loss / d level 0 summed over T, every element written; ``accumulate``: added to
+    ``out``.  A single iteration may be passed without the leading axis.  The order of every sum is the header's."""
+    what = 'corr_lookup_grad'
+    if isinstance(g_corr, torch.Tensor) and g_corr.dim() == 4:
+        g_corr, flow = g_corr.unsqueeze(0), flow.unsqueeze(0) if isinstance(flow, torch.Tensor) and flow.dim() == 4 else flow
+        mask = mask.unsqueeze(0) if isinstance(mask, torch.Tensor) and mask.dim() == 4 else mask
+    pg = _dense(g_corr, f'{what}: g_corr')
+    pf = _dense(flow, f'{what}: flow')
+    if g_corr.dim() != 5 or flow.dim() != 5 or flow.shape[2] != 2:
+        raise _lib.ScflowHipError(f'{what}: g_corr (T, N, K, h, w) and flow (T, N, 2, h, w), got {tuple(g_corr.shape)} and '
+                                  f'{tuple(flow.shape)}')
+    T, n, k, h, w = g_corr.shape
+    if radius < 1 or num_levels < 1 or num_levels > _lib.MAX_LEVELS:
+        raise _lib.ScflowHipError(f'{what}: radius >= 1 and 1 .. {_lib.MAX_LEVELS} levels, got {radius} and {num_levels}')
+    if T == 0 or T > TAIL_MAX_T or n * h * w == 0:
+        raise _lib.ScflowHipError(f'{what}: 1 .. {TAIL_MAX_T} iterations of non-empty maps, got {tuple(g_corr.shape)}')
+    if k != num_levels * (2 * radius + 1) ** 2 or tuple(flow.shape) != (T, n, 2, h, w):
+        raise _lib.ScflowHipError(f'{what}: g_corr must hold {num_levels * (2 * radius + 1) ** 2} channels and flow be '
+                                  f'{(T, n, 2, h, w)}, got {tuple(g_corr.shape)} and {tuple(flow.shape)}')
+    if (h >> (num_levels - 1)) == 0 or (w >> (num_levels - 1)) == 0:
+        raise _lib.ScflowHipError(f'{what}: level {num_levels - 1} of a {h} x {w} map is empty')
+    pm = None
+    if mask is not None:
+        pm = _dense(mask, f'{what}: mask')
+        if tuple(mask.shape) != (T, n, 1, h, w):
+            raise _lib.ScflowHipError(f'{what}: mask must be {(T, n, 1, h, w)}, got {tuple(mask.shape)}')
+    shape = (n * h * w, h, w)
+    if out is None:
+        if accumulate:
+            raise _lib.ScflowHipError(f'{what}: accumulate needs out')
+        out = torch.empty(shape, dtype=torch.float32, device=g_corr.device)
+    po = _dense(out, f'{what}: out')
+    if tuple(out.shape) != shape:
+        raise _lib.ScflowHipError(f'{what}: out must be {shape}, got {tuple(out.shape)}')
+    _lib.check(_lib.load().scf_corr_lookup_grad(pg, pf, pm, po, int(bool(accumulate)), T, n, h, w, radius, num_levels,
+                                                _stream()), 'scf_corr_lookup_grad')
+    return out
+
+
 class _TimerPool:
     """launch-bound timers (scf_timer_*), created up front so that a timed loop only takes one
     from the pool; ``read()`` returns the durations of the timers used since the last reset."""

@@ -436,12 +436,49 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         passes; and the list over the iterations of d loss / d ``x_t`` (N, 128, h, w), the motion encoder's 126 channels
         and the 2 flow channels behind them.  ``params`` is extended by the ``decoder.gru.*`` gradients (12 for
         ``'SeqConv'``, 6 for ``'Conv'``), summed over the iterations.  The values are the bits of ``loss()``; every entry
-        ``loss_and_decoder_head_grads()`` returns keeps its bits and its key.  Still missing: the backward of the motion
-        encoder, the lookup and the image encoders -- ``initial_hidden``, ``context`` and ``motion_features`` are where
-        they will start -- and, under ``detach_flow=False`` and under ``mask_flow`` / ``mask_corr`` without
+        ``loss_and_decoder_head_grads()`` returns keeps its bits and its key.  ``loss_and_motion_grads()`` carries
+        ``motion_features`` through the motion encoder and the lookup; still missing: the backward of the correlation
+        build and the image encoders -- ``initial_hidden`` and ``context`` are where the context encoder's will start --
+        and, under ``detach_flow=False`` and under ``mask_flow`` / ``mask_corr`` without
         ``detach_mask``, the path from ``motion_features[t]`` back into iteration t - 1 (its flow and its mask), which
         belongs to the motion-encoder backward: ``decoder_heads`` and the head gradients do not contain it."""
         return self._loss(data_batch, data, 'gru')
+
+    def loss_and_motion_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_gru_grads()`` carried through the motion encoder and through the correlation lookup to the pyramid
+        (``SCFlowDecoder.motion_backward``) -> the same tuple, ``grads`` with one more key: ``motion`` =
+        ``dict(correlation, flow_inputs)``: d loss / d (level 0 of the correlation pyramid) (N h w, h, w), summed over the
+        iterations with the pooling adjoints of the coarser levels folded in -- where the correlation-build backward and
+        the image encoders will start -- and the list over the iterations of d loss / d (the encoder's flow input)
+        (N, 2, h, w).  ``params`` is extended by the ten ``decoder.encoder.*`` gradients, summed over the iterations: every
+        parameter of the decoder now has a gradient.  The values are the bits of ``loss()``; every entry
+        ``loss_and_gru_grads()`` returns keeps its bits and its key.  The depth ladder of ``_loss`` ends at ``'gru'``; this
+        stage runs beside it, on what a forward under ``keep_motion_inputs`` keeps.
+
+        Only where nothing flows from ``x_t`` back into iteration t - 1: ``detach_flow=True``, and ``detach_mask=True``
+        whenever ``mask_flow`` or ``mask_corr`` is set (the shipped configuration).  Otherwise the cotangent re-enters the
+        previous iteration through ``flow_lr`` (which needs the lookup's derivative with respect to its coordinates) or
+        through the mask, a reverse scan over whole iterations: NotImplementedError."""
+        dec = self.decoder
+        if not dec.detach_flow:
+            raise NotImplementedError('loss_and_motion_grads: detach_flow=False needs the path from flow_lr of iteration t into '
+                                      'iteration t - 1 (the lookup\'s derivative with respect to its coordinates and a reverse '
+                                      'scan over whole iterations), which has no backward yet')
+        if (dec.mask_flow or dec.mask_corr) and not dec.detach_mask:
+            raise NotImplementedError('loss_and_motion_grads: mask_flow / mask_corr without detach_mask needs the path from the '
+                                      'mask of iteration t - 1 into iteration t\'s motion encoder (a reverse scan over whole '
+                                      'iterations), which has no backward yet')
+        kept = dec.keep_motion_inputs
+        dec.keep_motion_inputs = True
+        try:
+            out = self._loss(data_batch, data, 'gru')
+        finally:
+            dec.keep_motion_inputs = kept
+        grads = out[5]
+        g_vol, g_flow_inputs, params = dec.motion_backward(dec.pose_head_inputs, grads['gru']['motion_features'])
+        grads['motion'] = dict(correlation=g_vol, flow_inputs=g_flow_inputs)
+        grads['params'].update(('decoder.' + key, val) for key, val in params.items())
+        return out
 
     def _loss(self, data_batch, data, depth):
         from . import losses as L
@@ -529,7 +566,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                       'loss_and_pose_tail_grads() through the fully connected tail of the pose head, '
                                       'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm, '
                                       'loss_and_decoder_head_grads() through the XHeads and the delta-flow / mask encoders to hv, '
-                                      'loss_and_gru_grads() through the GRU to h0, the context and the motion features')
+                                      'loss_and_gru_grads() through the GRU to h0, the context and the motion features, '
+                                      'loss_and_motion_grads() through the motion encoder and the lookup to the correlation volume')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
