@@ -113,7 +113,7 @@ def correlation_pyramid(feat1: Tensor, feat2: Tensor, num_levels: int = 4) -> Li
     n, c, h, w = feat1.shape
     a = feat1.reshape(n, c, h * w).transpose(1, 2)
     b = feat2.reshape(n, c, h * w)
-    corr = torch.matmul(a, b).reshape(n * h * w, 1, h, w) / torch.sqrt(torch.tensor(float(c)))
+    corr = torch.matmul(a, b).reshape(n * h * w, 1, h, w) / torch.sqrt(torch.tensor(float(c), dtype=feat1.dtype))
     pyr = [corr]
     for _ in range(num_levels - 1):
         pyr.append(F.avg_pool2d(pyr[-1], kernel_size=2, stride=2))
@@ -133,9 +133,9 @@ def corr_lookup(pyramid: Sequence[Tensor], flow: Tensor, radius: int = 4) -> Ten
     n, _, h, w = flow.shape
     r = radius
     ys, xs = torch.meshgrid(torch.arange(h), torch.arange(w), indexing='ij')
-    base = torch.stack([xs, ys], dim=0).float()[None]          # (1,2,h,w) = (x, y)
+    base = torch.stack([xs, ys], dim=0).to(flow.dtype)[None]   # (1,2,h,w) = (x, y)
     centre = (base + flow).permute(0, 2, 3, 1).reshape(n * h * w, 1, 1, 2)
-    d = torch.linspace(-r, r, 2 * r + 1)
+    d = torch.linspace(-r, r, 2 * r + 1, dtype=flow.dtype)
     da, db = torch.meshgrid(d, d, indexing='ij')
     delta = torch.stack([da, db], dim=-1)[None]                # (1,9,9,2): [...,0] -> x slot
     outs = []
@@ -147,21 +147,22 @@ def corr_lookup(pyramid: Sequence[Tensor], flow: Tensor, radius: int = 4) -> Ten
         samp = F.grid_sample(corr, torch.stack([gx, gy], dim=-1), mode='bilinear',
                              padding_mode='zeros', align_corners=True)
         outs.append(samp.view(n, h, w, -1))
-    return torch.cat(outs, dim=-1).permute(0, 3, 1, 2).contiguous().float()
+    return torch.cat(outs, dim=-1).permute(0, 3, 1, 2).contiguous().to(flow.dtype)
 
 
 # --------------------------------------------------------------------------
 # update block
 # --------------------------------------------------------------------------
-def motion_encoder(corr: Tensor, flow: Tensor, sd: SD, p: str) -> Tensor:
+def motion_encoder(corr: Tensor, flow: Tensor, sd: SD, p: str, conv=conv_act) -> Tensor:
     """decoder/raft_decoder.py:152-166, 'Basic' shapes (:76-86): corr 1x1
     324->256, 3x3 256->192; flow 7x7 2->128, 3x3 128->64; out 3x3 256->126;
-    all ReLU (scflow.py:74); result cat [out(126), flow(2)]."""
-    c = conv_act(corr, sd, p + 'corr_net.0', padding=0)
-    c = conv_act(c, sd, p + 'corr_net.1', padding=1)
-    f = conv_act(flow, sd, p + 'flow_net.0', padding=3)
-    f = conv_act(f, sd, p + 'flow_net.1', padding=1)
-    o = conv_act(torch.cat([c, f], dim=1), sd, p + 'out_net.0', padding=1)
+    all ReLU (scflow.py:74); result cat [out(126), flow(2)].  ``conv``: what
+    stands for ``conv_act`` (``scflow_decoder``'s ``conv``)."""
+    c = conv(corr, sd, p + 'corr_net.0', padding=0)
+    c = conv(c, sd, p + 'corr_net.1', padding=1)
+    f = conv(flow, sd, p + 'flow_net.0', padding=3)
+    f = conv(f, sd, p + 'flow_net.1', padding=1)
+    o = conv(torch.cat([c, f], dim=1), sd, p + 'out_net.0', padding=1)
     return torch.cat([o, flow], dim=1)
 
 
@@ -182,11 +183,11 @@ def sepconv_gru(h: Tensor, x: Tensor, sd: SD, p: str) -> Tensor:
     return h
 
 
-def xhead(h: Tensor, sd: SD, p: str, kind: str) -> Tensor:
+def xhead(h: Tensor, sd: SD, p: str, kind: str, conv=conv_act) -> Tensor:
     """decoder/raft_decoder.py:292-294; one 3x3 ConvModule(ReLU) to 256 ch
     (the feat_channels tuple check at scflow_decoder.py:73-74 always yields
     [256]) then predict_layer: 3x3 for 'flow', 1x1 for 'mask' (:279-287)."""
-    y = conv_act(h, sd, p + 'layers.0', padding=1)
+    y = conv(h, sd, p + 'layers.0', padding=1)
     pad = 1 if kind == 'flow' else 0
     return F.conv2d(y, sd[p + 'predict_layer.weight'], sd[p + 'predict_layer.bias'], padding=pad)
 
@@ -238,18 +239,22 @@ def rotation_from_ortho6d(o6: Tensor) -> Tensor:
 
 
 def pose_from_delta_pose(d_rot: Tensor, d_trans: Tensor, rot: Tensor, trans: Tensor,
-                         weight: float = 10., depth_transform: str = 'exp') -> Tuple[Tensor, Tensor]:
+                         weight: float = 10., depth_transform: str = 'exp',
+                         detach_depth_for_xy: bool = False) -> Tuple[Tensor, Tensor]:
     """utils/pose.py:124-149, ortho6d branch (scflow.py:68; decoder default
     depth_transform 'exp' scflow_decoder.py:60):
     R' = R_delta @ R; z' = z / exp(dz)  ('exp', :137-138)  or  z * (dz + 1)
-    (any other value, :139-141); x' = z' * (dx / 10 + x / z), same y."""
+    (any other value, :139-141); x' = z' * (dx / 10 + x / z), same y.
+    ``detach_depth_for_xy`` (:142-144, autograd only): x' and y' take z' as a
+    constant, so d_trans[:, 2] is reached through z' alone."""
     r_new = torch.bmm(rotation_from_ortho6d(d_rot), rot)
     if depth_transform == 'exp':
         vz = trans[:, 2] / torch.exp(d_trans[:, 2])
     else:
         vz = trans[:, 2] * (d_trans[:, 2] + 1)
-    vx = vz * torch.addcdiv(d_trans[:, 0] / weight, trans[:, 0], trans[:, 2])
-    vy = vz * torch.addcdiv(d_trans[:, 1] / weight, trans[:, 1], trans[:, 2])
+    vz_xy = vz.detach() if detach_depth_for_xy else vz
+    vx = vz_xy * torch.addcdiv(d_trans[:, 0] / weight, trans[:, 0], trans[:, 2])
+    vy = vz_xy * torch.addcdiv(d_trans[:, 1] / weight, trans[:, 1], trans[:, 2])
     return r_new, torch.stack([vx, vy, vz], dim=-1)
 
 
@@ -259,10 +264,10 @@ def unproject_depth(depth: Tensor, k: Tensor, rot: Tensor, trans: Tensor) -> Tup
     P_obj = R^-1 (P_cam - t).  Returns (M,2) xy pixel coords and (M,3) points."""
     ys, xs = torch.nonzero(depth > 0, as_tuple=True)
     d = depth[ys, xs]
-    homo = torch.stack([xs.float(), ys.float(), torch.ones_like(d)], dim=-1) * d[:, None]
+    homo = torch.stack([xs.to(d.dtype), ys.to(d.dtype), torch.ones_like(d)], dim=-1) * d[:, None]
     cam = torch.mm(torch.inverse(k), homo.t()).t()
     obj = torch.mm(torch.inverse(rot), (cam - trans[None]).t()).t()
-    return torch.stack([xs, ys], dim=-1).float(), obj
+    return torch.stack([xs, ys], dim=-1).to(d.dtype), obj
 
 
 def flow_from_pose_and_points(rot: Tensor, trans: Tensor, k: Tensor, pts2d: Sequence[Tensor],
@@ -291,11 +296,37 @@ def scflow_decoder(feat_render: Tensor, feat_real: Tensor, h_feat: Tensor, cxt_f
                    prefix: str = 'decoder.', iters: int = 8, num_levels: int = 4,
                    radius: int = 4, invalid_flow_num: float = 0.,
                    mask_flow: bool = False, mask_corr: bool = False,
-                   depth_transform: str = 'exp', label_mode: int = 0):
-    """decoder/scflow_decoder.py:150-251 (inference: the detach_* flags only
-    affect autograd).  ``label_mode=1``: see ``multiclass_pose_head`` (not the reference)."""
+                   depth_transform: str = 'exp', label_mode: int = 0,
+                   detach_flow: bool = True, detach_mask: bool = True, detach_pose: bool = True,
+                   detach_depth_for_xy: bool = True, tap=None, conv=None):
+    """decoder/scflow_decoder.py:150-251.  ``label_mode=1``: see ``multiclass_pose_head`` (not the reference).
+
+    The ``detach_*`` flags only affect autograd: no forward value depends on them.  They default to the shipped
+    configuration (configs/refine_models/scflow.py, restated by ``scflow_amd.scflow_model_cfg()``: all four set) and
+    each ``.detach()`` stands where the reference's stands: ``detach_flow`` / ``detach_mask`` on the carried flow and
+    mask at the top of every iteration (:192-195), ``detach_pose`` on the source pose handed to the pose update
+    (:232-233), ``detach_depth_for_xy`` inside it (``pose_from_delta_pose``, :235).  Every tensor follows the dtype of
+    its inputs, so float64 inputs and a float64 state dict give a float64 graph.
+
+    ``tap``: None, or ``tap(name, t, value) -> value``, called once per named intermediate of iteration ``t`` (``t`` None
+    for the pyramid, a list) with what the next operation is about to consume; what it returns is consumed instead.  A
+    gradient test records a tensor, or hands back an alias (``value.view_as(value)``) to receive the cotangent of that ONE
+    use; a planted defect hands back ``value.detach()``.  The names, in order of use: 'pyramid', then per iteration 'sd'
+    (the state dict this iteration's layers read), 'flow_lr', 'corr', 'flow_in' (the motion encoder's flow input), 'x',
+    'h_in' (the hidden state the GRU starts from; h0 at t = 0), 'hv' (the GRU's output, all uses), 'hv_flow' /
+    'hv_mask' / 'hv_pose' (its use by the flow head, the mask head, the pose head), 'd_flow' (all uses),
+    'mask_logit', 'mask' (post-sigmoid, all uses), 'dm' (the delta-flow and mask features), 'd_rot', 'd_trans',
+    'd_flow_tail' / 'mask_tail' (the uses by the up-sampled outputs), 'flow_pred', 'up_mask', 'rotation',
+    'translation', 'flow_from_pose'.  With the identity every value keeps its bits.
+
+    ``conv``: None, or what stands for ``conv_act`` (same signature) at the ten conv + ReLU layers of the motion encoder,
+    the two XHeads' hidden layers and the delta-flow / mask encoders: a gradient test that has to choose the derivative
+    of a ReLU unit at zero itself."""
+    conv = conv_act if conv is None else conv
+    if tap is None:
+        tap = lambda name, t, value: value                                     # noqa: E731
     p = prefix
-    pyramid = correlation_pyramid(feat_render, feat_real, num_levels)           # :172
+    pyramid = tap('pyramid', None, correlation_pyramid(feat_render, feat_real, num_levels))     # :172
     rot, trans = ref_rotation, ref_translation
     scale = 2 ** (num_levels - 1)
     n, H, W = depth.shape
@@ -308,30 +339,47 @@ def scflow_decoder(feat_render: Tensor, feat_real: Tensor, h_feat: Tensor, cxt_f
                          align_corners=True)                                    # :188-190
     outs = dict(flow_from_pose=[], flow_from_pred=[], rotation=[], translation=[],
                 mask=[], delta_rotation=[], delta_translation=[])
-    for _ in range(iters):
-        flow = 1 / scale * F.interpolate(flow, scale_factor=(1 / scale, 1 / scale),
-                                         mode='bilinear', align_corners=True)   # :196-197
+    for t in range(iters):
+        w = tap('sd', t, sd)
+        if detach_flow:
+            flow = flow.detach()                                                # :192-193
+        if detach_mask:
+            mask = mask.detach()                                                # :194-195
+        flow = tap('flow_lr', t, 1 / scale * F.interpolate(flow, scale_factor=(1 / scale, 1 / scale),
+                                                           mode='bilinear', align_corners=True))   # :196-197
         corr = corr_lookup(pyramid, flow, radius)                               # :198
         if mask_corr:
             corr = corr * mask
-        motion = motion_encoder(corr, flow * mask if mask_flow else flow, sd, p + 'encoder.')
-        h_feat = sepconv_gru(h_feat, torch.cat([cxt_feat, motion], dim=1), sd, p + 'gru.')
-        d_flow = xhead(h_feat, sd, p + 'flow_pred.', 'flow')                    # :210
-        mask = torch.sigmoid(xhead(h_feat, sd, p + 'mask_pred.', 'mask'))       # :212-213
-        df = conv_act(d_flow, sd, p + 'delta_flow_encoder.0', padding=3)        # :216
-        df = conv_act(df, sd, p + 'delta_flow_encoder.1', padding=1)
-        mf = conv_act(mask, sd, p + 'mask_encoder.0', padding=1)                # :217
-        mf = conv_act(mf, sd, p + 'mask_encoder.1', padding=1)
-        d_rot, d_trans = multiclass_pose_head(torch.cat([h_feat, df, mf], dim=1), label,
-                                              sd, p + 'pose_pred.', label_mode=label_mode)   # :218-219
-        flow_pred = scale * F.interpolate(flow + d_flow, scale_factor=(scale, scale),
+        corr = tap('corr', t, corr)
+        flow_in = tap('flow_in', t, flow * mask if mask_flow else flow)
+        motion = tap('x', t, motion_encoder(corr, flow_in, w, p + 'encoder.', conv))
+        h_feat = tap('h_in', t, h_feat)
+        h_feat = tap('hv', t, sepconv_gru(h_feat, torch.cat([cxt_feat, motion], dim=1), w, p + 'gru.'))
+        d_flow = tap('d_flow', t, xhead(tap('hv_flow', t, h_feat), w, p + 'flow_pred.', 'flow', conv))    # :210
+        logit = tap('mask_logit', t, xhead(tap('hv_mask', t, h_feat), w, p + 'mask_pred.', 'mask', conv))
+        mask = tap('mask', t, torch.sigmoid(logit))                             # :212-213
+        df = conv(d_flow, w, p + 'delta_flow_encoder.0', padding=3)             # :216
+        df = conv(df, w, p + 'delta_flow_encoder.1', padding=1)
+        mf = conv(mask, w, p + 'mask_encoder.0', padding=1)                     # :217
+        mf = conv(mf, w, p + 'mask_encoder.1', padding=1)
+        dm = tap('dm', t, torch.cat([df, mf], dim=1))
+        d_rot, d_trans = multiclass_pose_head(torch.cat([tap('hv_pose', t, h_feat), dm], dim=1), label,
+                                              w, p + 'pose_pred.', label_mode=label_mode)    # :218-219
+        d_rot, d_trans = tap('d_rot', t, d_rot), tap('d_trans', t, d_trans)
+        flow_pred = scale * F.interpolate(flow + tap('d_flow_tail', t, d_flow), scale_factor=(scale, scale),
                                           mode='bilinear', align_corners=True)  # :222-224
-        up_mask = F.interpolate(mask, scale_factor=(scale, scale), mode='bilinear',
+        flow_pred = tap('flow_pred', t, flow_pred)
+        up_mask = F.interpolate(tap('mask_tail', t, mask), scale_factor=(scale, scale), mode='bilinear',
                                 align_corners=True)                             # :226-227
-        rot, trans = pose_from_delta_pose(d_rot, d_trans, rot, trans,
-                                          depth_transform=depth_transform)      # :230-236
+        up_mask = tap('up_mask', t, up_mask)
+        rot, trans = pose_from_delta_pose(d_rot, d_trans, rot.detach() if detach_pose else rot,
+                                          trans.detach() if detach_pose else trans,
+                                          depth_transform=depth_transform,
+                                          detach_depth_for_xy=detach_depth_for_xy)   # :230-236
+        rot, trans = tap('rotation', t, rot), tap('translation', t, trans)
         flow = flow_from_pose_and_points(rot, trans, internel_k, pts2d, pts3d, H, W,
                                          invalid_num=invalid_flow_num)          # :239-243
+        flow = tap('flow_from_pose', t, flow)
         outs['rotation'].append(rot)
         outs['translation'].append(trans)
         outs['delta_rotation'].append(d_rot)
@@ -364,19 +412,23 @@ def get_pose(render_images: Tensor, real_images: Tensor, ref_rotation: Tensor,
              sd: SD, *, iters: int = 8, init_flow: Tensor | None = None,
              mask_flow: bool = False, mask_corr: bool = False,
              depth_transform: str = 'exp', label_mode: int = 0, radius: int = 4,
-             feat_kind: str = 'IN', cxt_kind: str = 'BN'):
+             feat_kind: str = 'IN', cxt_kind: str = 'BN', detach_flow: bool = True,
+             detach_mask: bool = True, detach_pose: bool = True, detach_depth_for_xy: bool = True):
     """refiner/scflow_refiner.py:112-142 ``SCFlowRefiner.get_pose``
     (invalid_flow_num = 0 at inference, :142); ``mask_flow`` / ``mask_corr``: the decoder's
     constructor switches (scflow_decoder.py:199-205, both False in configs/refine_models/scflow.py);
-    ``feat_kind`` / ``cxt_kind``: the encoders' norm kinds (``extract_feat``)."""
+    ``feat_kind`` / ``cxt_kind``: the encoders' norm kinds (``extract_feat``); the ``detach_*`` flags: autograd
+    only, handed to ``scflow_decoder``."""
     fr, fl, h, c = extract_feat(render_images, real_images, sd, feat_kind=feat_kind, cxt_kind=cxt_kind)
     if init_flow is None:
         n, _, H, W = real_images.shape
-        init_flow = torch.zeros((n, 2, H, W), dtype=torch.float32)
+        init_flow = torch.zeros((n, 2, H, W), dtype=real_images.dtype)
     return scflow_decoder(fr, fl, h, c, ref_rotation, ref_translation, depth, internel_k,
                           label, init_flow, sd, iters=iters, invalid_flow_num=0.,
                           mask_flow=mask_flow, mask_corr=mask_corr, radius=radius,
-                          depth_transform=depth_transform, label_mode=label_mode)
+                          depth_transform=depth_transform, label_mode=label_mode,
+                          detach_flow=detach_flow, detach_mask=detach_mask, detach_pose=detach_pose,
+                          detach_depth_for_xy=detach_depth_for_xy)
 
 
 def end_point_error(flow_a: Tensor, flow_b: Tensor, valid: Tensor | None = None) -> float:
