@@ -13,6 +13,8 @@ parameters' device and dropped whenever the module is moved or re-loaded.
 """
 from __future__ import annotations
 
+import contextlib
+from functools import partial
 from typing import Dict, List, Optional, Sequence, Tuple, Union
 
 import torch
@@ -34,6 +36,44 @@ def _act_code(act_cfg: Optional[dict]) -> int:
     if kind not in _ACTS:
         raise NotImplementedError(f'activation {kind} has no HIP epilogue')
     return _ACTS[kind]
+
+
+def _lib_error(msg):
+    from ._lib import ScflowHipError
+    return ScflowHipError(msg)
+
+
+# what SCFlowDecoder.keep asks a forward to leave in SCFlowDecoder.kept: a level keeps what the levels before it keep
+KEEP_LEVELS = ('none', 'pose_tail', 'pose_head', 'decoder_heads', 'gru', 'motion')
+_KEEP = {name: i for i, name in enumerate(KEEP_LEVELS)}
+# how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do; from 'head' on the chain is
+# SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  No backward yet: the
+# correlation build and the image and context encoders (they start from grads['motion']['correlation'],
+# grads['gru']['initial_hidden'] and grads['gru']['context']), and the path from iteration t into iteration t - 1 under
+# detach_flow=False or under mask_flow / mask_corr without detach_mask (SCFlowDecoder.check_backward refuses it at 'motion')
+_GRAD_DEPTHS = ('none', 'outputs', 'head') + KEEP_LEVELS[1:]
+
+
+def _kept(what: str, saved, keys: Sequence[str], level: Optional[str]) -> list:
+    """the entries ``keys`` of ``saved``, or the error that names the keep level whose forward leaves them in
+    ``SCFlowDecoder.kept``"""
+    try:
+        return [saved[k] for k in keys]
+    except (KeyError, TypeError):
+        where = f": SCFlowDecoder.kept after a forward at keep level '{level}' or above" if level else ''
+        raise _lib_error(f"{what}: saved holds {', '.join(keys)}{where}") from None
+
+
+def _stacked(seq: Sequence[Tensor], m: int, c: int, h: int, w: int) -> Tensor:
+    """the T per-iteration (N, c, h, w) tensors of ``seq`` as one (m = T N, c, h, w) tensor: a copy, none for T = 1"""
+    return (seq[0].contiguous() if len(seq) == 1 else torch.stack(list(seq))).view(m, c, h, w)
+
+
+def _layer_wgrad(grads: dict, dst: dict, acc: bool, ws: Tensor, key: str, g: Tensor, x: Tensor, conv) -> None:
+    """``conv``'s weight and bias gradient from (``g``, ``x``) into ``grads`` under ``key``.weight / .bias, written to (with
+    ``acc``: added to) the ``_grad_slots`` destinations ``dst``"""
+    grads[f'{key}.weight'], grads[f'{key}.bias'] = ops.conv_s1_wgrad(
+        g, x, tuple(conv.kernel_size), dw=dst[f'{key}.weight'], db=dst[f'{key}.bias'], accumulate=acc, workspace=ws)
 
 
 class HipModule(nn.Module):
@@ -418,7 +458,7 @@ class MotionEncoder(HipModule):
 
         ``saved``: ``corr`` (T, N, L (2r+1)^2, h, w), the looked-up (and, under ``mask_corr``, masked) correlation of every
         iteration, and ``x`` (T, N, 128, h, w), the encoder's output [out_net (126, post-activation) | flow_in (2)] that
-        ``SCFlowDecoder.keep_gru_inputs`` keeps.  ``g_motion_features``: T cotangents at ``x_t`` (``ConvGRU.backward`` returns
+        ``SCFlowDecoder`` keeps from ``'gru'`` on.  ``g_motion_features``: T cotangents at ``x_t`` (``ConvGRU.backward`` returns
         them).  -> (``g_corr`` (T, N, L (2r+1)^2, h, w): the cotangents at ``corr``; ``g_flow_inputs``: T cotangents at the
         encoder's flow input (N, 2, h, w), the pass-through channels included; ``param_grads``: the gradients of the ten
         parameters summed over all T N samples, keyed as in ``named_parameters()`` behind ``prefix``).  A dict passed in is
@@ -435,10 +475,7 @@ class MotionEncoder(HipModule):
         T = len(g_motion_features)
         if T == 0 or T > ops.TAIL_MAX_T:
             raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at x per iteration')
-        try:
-            corr, x = saved['corr'], saved['x']
-        except (KeyError, TypeError):
-            raise _lib_error(f'{what}: saved holds corr (T, N, K, h, w) and x (T, N, 128, h, w)') from None
+        corr, x = _kept(what, saved, ('corr', 'x'), None)      # x is kept['x']; SCFlowDecoder.motion_backward recomputes corr
         cn, fn, on = self.corr_net, self.flow_net, self.out_net
         co = on[0].conv.out_channels                                  # 126
         if x.dim() != 5 or x.shape[0] != T or x.shape[2] != co + 2 or not x.is_contiguous():
@@ -463,33 +500,27 @@ class MotionEncoder(HipModule):
         c1, f1, cf = E(T, n, c_c1, h, w), E(T, n, c_f1, h, w), E(T, n, c_cc + c_cf, h, w)
         for t in range(T):
             self.branches(corr[t], x[t][:, co:], cf[t], c1=c1[t], f1=f1[t])
-        g_x = (g_motion_features[0].contiguous() if T == 1 else torch.stack(list(g_motion_features))).view(m, co + 2, h, w)
+        g_x = _stacked(g_motion_features, m, co + 2, h, w)
         x_, corr_ = x.view(m, co + 2, h, w), corr.view(m, kc, h, w)
         c1_, f1_, cf_ = c1.view(m, c_c1, h, w), f1.view(m, c_f1, h, w), cf.view(m, c_cc + c_cf, h, w)
         convs = (on[0].conv, cn[1].conv, cn[0].conv, fn[1].conv, fn[0].conv)
         ws = E(max(ops.conv_s1_wgrad_workspace(m, cv.out_channels, cv.in_channels, h, w, *cv.kernel_size) for cv in convs))
         w_scratch = E(max(cv.weight.numel() for cv in convs))
         a_or_none = lambda a: a if act != ACT_NONE else None                              # noqa: E731
-
-        def wgrad(g, xin, name, conv):
-            key = f'{prefix}{name}.conv'
-            dw, db = ops.conv_s1_wgrad(g, xin, tuple(conv.kernel_size), dw=dst[f'{key}.weight'], db=dst[f'{key}.bias'],
-                                       accumulate=acc, workspace=ws)
-            grads[f'{key}.weight'], grads[f'{key}.bias'] = dw, db
-
+        wgrad = partial(_layer_wgrad, grads, dst, acc, ws)
         # 1. out_net
         u = ops.act_grad(g_x[:, :co], a_or_none(x_[:, :co]), act)
-        wgrad(u, cf_, 'out_net.0', on[0].conv)
+        wgrad(f'{prefix}out_net.0.conv', u, cf_, on[0].conv)
         g_cf = ops.conv_s1_dgrad(u, on[0].conv.weight, a=a_or_none(cf_), act=act, w_scratch=w_scratch)
         # 2. correlation branch
-        wgrad(g_cf[:, :c_cc], c1_, 'corr_net.1', cn[1].conv)
+        wgrad(f'{prefix}corr_net.1.conv', g_cf[:, :c_cc], c1_, cn[1].conv)
         g_c1 = ops.conv_s1_dgrad(g_cf[:, :c_cc], cn[1].conv.weight, a=a_or_none(c1_), act=act, w_scratch=w_scratch)
-        wgrad(g_c1, corr_, 'corr_net.0', cn[0].conv)
+        wgrad(f'{prefix}corr_net.0.conv', g_c1, corr_, cn[0].conv)
         g_corr = ops.conv_s1_dgrad(g_c1, cn[0].conv.weight, w_scratch=w_scratch)
         # 3. flow branch: the pass-through channels' cotangent joins at the flow input
-        wgrad(g_cf[:, c_cc:], f1_, 'flow_net.1', fn[1].conv)
+        wgrad(f'{prefix}flow_net.1.conv', g_cf[:, c_cc:], f1_, fn[1].conv)
         g_f1 = ops.conv_s1_dgrad(g_cf[:, c_cc:], fn[1].conv.weight, a=a_or_none(f1_), act=act, w_scratch=w_scratch)
-        wgrad(g_f1, x_[:, co:], 'flow_net.0', fn[0].conv)
+        wgrad(f'{prefix}flow_net.0.conv', g_f1, x_[:, co:], fn[0].conv)
         g_fl = ops.conv_s1_dgrad(g_f1, fn[0].conv.weight, add=g_x[:, co:])
         if intermediates is not None:
             intermediates.update(c1=c1, f1=f1, cf=cf, g_x=g_x, u=u, g_cf=g_cf, g_c1=g_c1, g_f1=g_f1, g_corr=g_corr, g_flow_in=g_fl)
@@ -584,10 +615,7 @@ class ConvGRU(HipModule):
                      for k in ('weight', 'bias'))
 
     def _saved(self, what: str, saved, T: Optional[int] = None):
-        try:
-            h0, c, x, hv = (saved[k] for k in ('h0', 'c', 'x', 'hv'))
-        except (KeyError, TypeError):
-            raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_gru_inputs (h0, c, x, hv)') from None
+        h0, c, x, hv = _kept(what, saved, ('h0', 'c', 'x', 'hv'), 'gru')
         if hv.dim() != 5 or (T is not None and hv.shape[0] != T) or hv.shape[0] == 0 or not hv.is_contiguous():
             raise _lib_error(f'{what}: hv must be a contiguous ({"T" if T is None else T}, N, C, h, w) tensor, got {tuple(hv.shape)}')
         T, n, hc, h, w = hv.shape
@@ -638,7 +666,7 @@ class ConvGRU(HipModule):
         iteration t + 1.
 
         ``saved``: ``h0`` (N, Ch, h, w), the context ``c`` (N, Cc, h, w), the motion features ``x`` (T, N, Cx', h, w) and
-        the kept states ``hv`` (T, N, Ch, h, w) -- ``SCFlowDecoder.pose_head_inputs`` under ``keep_gru_inputs``.
+        the kept states ``hv`` (T, N, Ch, h, w) -- ``SCFlowDecoder.kept`` from keep level ``'gru'`` on.
         ``g_hidden_states``: T cotangents at ``hv_t`` (``SCFlowDecoder.heads_backward`` returns them).  -> (``g_h0``: d loss
         / d ``h0``; ``g_context``: d loss / d ``c`` summed over iterations and passes; ``g_motion_features``: T cotangents
         at ``x_t`` (N, Cx', h, w), channel slices of one stacked buffer; ``param_grads``: the gradients of the GRU's
@@ -879,7 +907,7 @@ class MultiClassPoseHead(HipModule):
     def conv_backward(self, saved: dict, g_ys: Sequence[Tensor], param_grads: Optional[dict] = None
                       ) -> Tuple[list, list, dict]:
         """Backward of the three 3x3 / stride-2 convolutions with GroupNorms 0 and 1 for the T iterations of a pass at
-        once.  ``saved``: what a forward under ``SCFlowDecoder.keep_pose_head_input`` left in ``pose_head_inputs`` (``hv``
+        once.  ``saved``: what a forward at keep level ``'pose_head'`` or above left in ``SCFlowDecoder.kept`` (``hv``
         (T, N, 128, h, w), ``dm`` (T, N, 96, h, w), the raw convolution outputs ``y0``, ``y1`` as (S, T, N, 128, h', w')
         partial tensors); ``g_ys``: what ``tail_backward`` returns.  -> (``g_x0s``, ``g_x1s``: T tensors each, the cotangents
         at ``hv`` and at ``dm``; ``param_grads``: the gradients of ``conv_layers.{0,1,2}.conv.weight`` and
@@ -900,10 +928,7 @@ class MultiClassPoseHead(HipModule):
             if blk.groups is None or blk.act != ACT_RELU or c.bias is not None or tuple(c.kernel_size) != (3, 3) or \
                     tuple(c.stride) != (2, 2) or tuple(c.padding) != (1, 1):
                 raise _lib_error('conv_backward: 3x3 / stride-2 / pad-1 convolutions without bias, GroupNorm + ReLU')
-        try:
-            hv, dm, y0, y1 = (saved[k] for k in ('hv', 'dm', 'y0', 'y1'))
-        except (KeyError, TypeError):
-            raise _lib_error('conv_backward: saved is SCFlowDecoder.pose_head_inputs (hv, dm, y0, y1)') from None
+        hv, dm, y0, y1 = _kept('conv_backward', saved, ('hv', 'dm', 'y0', 'y1'), 'pose_head')
         if hv.dim() != 5 or dm.dim() != 5 or hv.shape[0] != T or dm.shape[0] != T or hv.shape[1] != dm.shape[1] or \
                 hv.shape[3:] != dm.shape[3:] or hv.shape[2] + dm.shape[2] != L0.conv.in_channels or \
                 not hv.is_contiguous() or not dm.is_contiguous():
@@ -932,7 +957,7 @@ class MultiClassPoseHead(HipModule):
             return ops.group_norm_relu(yv if y.shape[0] > 1 else yv[0], blk.gn.weight, blk.gn.bias, blk.groups, blk.gn.eps)
 
         a0, a1 = act(y0, L0, sizes[1]), act(y1, L1, sizes[2])
-        g2 = g_ys[0].contiguous() if T == 1 else torch.stack(list(g_ys)).view(m, c2, *sizes[3])
+        g2 = _stacked(g_ys, m, c2, *sizes[3])
         x0, x1 = hv.view(m, c0, h, w), dm.view(m, dm.shape[2], h, w)
         need = max(ops.conv_wgrad_workspace(m, blk.conv.out_channels, blk.conv.in_channels, *hw_)
                    for blk, hw_ in zip((L0, L1, L2), sizes[1:]))
@@ -1014,6 +1039,11 @@ class MultiClassPoseHead(HipModule):
         return d_rot, d_trans
 
 
+_HEAD_PARAMS = tuple(f'{m}.{p}' for m in ('flow_pred.layers.0.conv', 'flow_pred.predict_layer', 'mask_pred.layers.0.conv',
+                                          'mask_pred.predict_layer', 'delta_flow_encoder.0.conv', 'delta_flow_encoder.1.conv',
+                                          'mask_encoder.0.conv', 'mask_encoder.1.conv') for p in ('weight', 'bias'))
+
+
 @DECODERS.register_module()
 class SCFlowDecoder(HipModule):
     """decoder/scflow_decoder.py:18-251."""
@@ -1060,31 +1090,29 @@ class SCFlowDecoder(HipModule):
         # the launch sequence of an iteration issued by ONE C call (scf_scflow_iteration) instead of
         # ~33 Python-sequenced ones: same kernels, same order, same bits; False = sequence from here
         self.c_iteration = True
-        # True: every forward leaves a copy of the pose head's tail input (MultiClassPoseHead.tail_input) of each
-        # iteration in pose_tail_inputs, what MultiClassPoseHead.tail_backward needs; False: nothing is kept or launched
-        self.keep_pose_tail_input = False
-        self.pose_tail_inputs = []
-        # True: every forward also keeps, per iteration, what MultiClassPoseHead.conv_backward needs, in pose_head_inputs:
-        # copies of hv and dm (T, N, C, h, w) and the raw outputs y0, y1, y2 of the head's convolutions as
-        # (S, T, N, 128, h', w') partial tensors (S: the K-slices of the forward's launch); implies keep_pose_tail_input.
-        # False: nothing is kept, allocated or launched
-        self.keep_pose_head_input = False
-        self.pose_head_inputs = {}
-        # True: every forward also keeps, per iteration, the XHeads' outputs d_flow (T, N, 2, h, w) and the post-sigmoid
-        # mask (T, N, 1, h, w) in pose_head_inputs, what heads_backward needs next to hv and dm; implies
-        # keep_pose_head_input.  False: nothing is kept, allocated or launched
-        self.keep_head_inputs = False
-        # True: every forward also keeps what ConvGRU.backward needs next to hv, in pose_head_inputs: the initial state h0
-        # (N, Ch, h, w), the context c (N, Cc, h, w) and the motion encoder's output x (T, N, 128, h, w) of every
-        # iteration; implies keep_head_inputs.  False: nothing is kept, allocated or launched
-        self.keep_gru_inputs = False
-        # True: every forward also keeps what motion_backward needs next to x and mask, in pose_head_inputs: the low-resolution
-        # flow flow_lr (T, N, 2, h, w) every lookup was taken at, the pyramid (the list itself: no copy, nothing rewrites
-        # it) and its layout mask tiled; implies keep_gru_inputs.  False: nothing is kept, allocated or launched
-        self.keep_motion_inputs = False
+        # what every forward leaves in ``kept`` for the backward stages, one of KEEP_LEVELS; a level adds to the one before it:
+        #   'none'           nothing is kept, allocated or launched, and ``kept`` is not touched
+        #   'pose_tail'      tail_inputs: per iteration the pose head's tail input (MultiClassPoseHead.tail_input), a list
+        #   'pose_head'      hv, dm (T, N, C, h, w) and the raw outputs y0, y1, y2 of the head's convolutions as
+        #                    (S, T, N, 128, h', w') partial tensors (S: the K-slices of the forward's launch)
+        #   'decoder_heads'  the XHeads' outputs d_flow (T, N, 2, h, w) and the post-sigmoid mask (T, N, 1, h, w)
+        #   'gru'            the initial state h0 (N, Ch, h, w), the context c (N, Cc, h, w), the motion encoder's output x
+        #                    (T, N, 128, h, w)
+        #   'motion'         flow_lr (T, N, 2, h, w) every lookup was taken at, the pyramid (the list itself: no copy, nothing
+        #                    rewrites it) and its layout mask tiled
+        # copies only; a forward above 'none' replaces ``kept`` with a fresh dict of exactly its level's keys
+        self.keep = 'none'
+        self.kept = {}
 
-    def _keeps_gru(self) -> bool:
-        return self.keep_gru_inputs or self.keep_motion_inputs
+    @contextlib.contextmanager
+    def keeping(self, level: str):
+        """``keep`` raised to at least ``level`` for the body (a higher setting of the caller's stays) and put back after it"""
+        prev = self.keep
+        self.keep = max(prev, level, key=KEEP_LEVELS.index)
+        try:
+            yield self
+        finally:
+            self.keep = prev
 
     def pose_flags(self) -> int:
         """the ``label_mode`` bit set of ``scf_pose_update`` (scflow_hip.h: SCF_POSE_*)."""
@@ -1106,6 +1134,9 @@ class SCFlowDecoder(HipModule):
                 _consume_state: bool = False):
         """scflow_decoder.py:150-251 (inference).  Returns the reference's 7-tuple of
         per-iteration lists."""
+        if self.keep not in KEEP_LEVELS:
+            raise ValueError(f'SCFlowDecoder.keep is {self.keep!r}: it must be one of KEEP_LEVELS = {KEEP_LEVELS}')
+        level = KEEP_LEVELS.index(self.keep)
         hc, cc = self.h_channels, self.cxt_channels
         n, H, W = depth.shape
         scale = 2 ** (self.num_levels - 1)
@@ -1113,21 +1144,19 @@ class SCFlowDecoder(HipModule):
         dev = depth.device
         f32 = dict(dtype=torch.float32, device=dev)
 
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
-            self.pose_tail_inputs = []
-        if self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
-            self.pose_head_inputs = {}
+        if level:
+            self.kept = {'tail_inputs': []}
         tiled = _pyramid_layout(feat_render, self.radius, self.num_levels, self.tiled_pyramid)
         pyramid = self.corr_block(feat_render, feat_real, tiled_levels=tiled)      # :172
-        if self.keep_motion_inputs:
-            self.pose_head_inputs['pyramid'], self.pose_head_inputs['tiled'] = pyramid, tiled
+        if level >= _KEEP['motion']:
+            self.kept['pyramid'], self.kept['tiled'] = pyramid, tiled
         # GRU buffer [h | cxt | motion(126) | flow(2)]: the caller's own buffer only when the
         # refiner says it may be consumed (_consume_state); the public forward never mutates
         # its inputs (the reference decoder does not either)
         hx = _as_gru_buffer(h_feat, cxt_feat, hc + cc + 128, _consume_state)
-        if self._keeps_gru():      # before the first iteration rewrites h in place
+        if level >= _KEEP['gru']:      # before the first iteration rewrites h in place
             for key, part in (('h0', hx[:, :hc]), ('c', hx[:, hc:hc + cc])):
-                self.pose_head_inputs[key] = torch.empty(part.shape, **f32).copy_(part)
+                self.kept[key] = torch.empty(part.shape, **f32).copy_(part)
         rot, trans = ref_rotation.contiguous(), ref_translation.contiguous()
         rot0, trans0 = rot, trans
         flow = init_flow
@@ -1139,7 +1168,7 @@ class SCFlowDecoder(HipModule):
         # small batches: independent branches side by side
         ov_flow, ov_mask, ov_up = (ops.small_work(n, H, W, b) for b in ('flow', 'mask', 'upsample'))
         if self.c_iteration and ops._CONV_EVENTS is None:
-            return self._forward_c(pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
+            return self._forward_c(level, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
                                    invalid_flow_num, tuple(ops.branch_mode(n, H, W, b) for b in ('flow', 'mask', 'upsample')))
         # occlusion mask of the previous iteration (ones before the first: the 1/8 bilinear
         # down-sampling of a ones map, :188-190), used only with mask_flow / mask_corr
@@ -1177,7 +1206,7 @@ class SCFlowDecoder(HipModule):
                 ops.resize_bilinear(flow_lr, (H, W), mul=float(scale), b=d_flow, out=flow_pred)  # :222-224
                 ops.resize_bilinear(mask, (H, W), out=up_mask)                     # :226-227
             ys = self.pose_pred._conv_outputs(hv, dm)                              # :218-219
-            self._keep_pose_inputs(len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask, xm=hx[:, hc + cc:], flow_lr=flow_lr)
+            self._keep_iteration(level, len(outs[0]), hv, dm, ys, d_flow=d_flow, mask=mask, xm=hx[:, hc + cc:], flow_lr=flow_lr)
             rot_all, trans_all = self.pose_pred._tail(ys[2])
             d_rot, d_trans, rot, trans = ops.pose_update(                          # :230-236
                 rot_all, trans_all, label, self.pose_pred.num_class, rot, trans,
@@ -1189,309 +1218,314 @@ class SCFlowDecoder(HipModule):
                 lst.append(v)
         return outs
 
-    def _keep_pose_inputs(self, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False, d_flow: Optional[Tensor] = None,
-                          mask: Optional[Tensor] = None, xm: Optional[Tensor] = None, flow_lr: Optional[Tensor] = None) -> None:
-        """What the keep flags ask for of iteration ``t``, copies only; no flag: nothing.  ``keep_pose_head_input``:
-        ``hv``, ``dm`` and the raw convolution outputs ``ys`` into ``pose_head_inputs``, whose buffers for all iterations
-        the first one allocates; ``keep_head_inputs``: ``d_flow`` and ``mask`` as well; ``keep_gru_inputs``: the motion
-        features ``xm`` (the GRU buffer's last 128 channels, rewritten by every iteration) as ``x`` as well;
-        ``keep_motion_inputs``: ``flow_lr`` (the C loop's scratch buffer of that name) as well.  Any flag: the
-        last of ``ys`` onto ``pose_tail_inputs`` -- a ``clone`` where later iterations rewrite that buffer."""
-        if self.keep_motion_inputs:
-            kept = self.pose_head_inputs
+    def _keep_iteration(self, level: int, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False,
+                        d_flow: Optional[Tensor] = None, mask: Optional[Tensor] = None, xm: Optional[Tensor] = None,
+                        flow_lr: Optional[Tensor] = None) -> None:
+        """What keep level ``level`` (an index into KEEP_LEVELS) asks for of iteration ``t``, copies only; 0: nothing.  One
+        walk over the rows (minimum level, key, this iteration's tensor, where the iteration axis goes): the buffer for all
+        iterations is allocated at the first one.  ``xm``: the motion features (the GRU buffer's last 128 channels, rewritten
+        by every iteration), kept as ``x``; ``flow_lr``: in the C loop its scratch buffer of that name; the raw convolution
+        outputs ``ys`` are kept as (S, T, N, C, h', w') partial tensors.  Any level: the last of ``ys`` onto ``tail_inputs``
+        -- a ``clone`` where later iterations rewrite that buffer."""
+        if not level:
+            return
+        rows = ((_KEEP['motion'], 'flow_lr', flow_lr, 0), (_KEEP['gru'], 'x', xm, 0),
+                (_KEEP['decoder_heads'], 'd_flow', d_flow, 0), (_KEEP['decoder_heads'], 'mask', mask, 0),
+                (_KEEP['pose_head'], 'hv', hv, 0), (_KEEP['pose_head'], 'dm', dm, 0),
+                *((_KEEP['pose_head'], f'y{i}', y if y.dim() == 5 else y.unsqueeze(0), 1) for i, y in enumerate(ys)))
+        for need, key, v, axis in rows:
+            if level < need:
+                continue
             if t == 0:
-                kept['flow_lr'] = torch.empty((self.iters,) + tuple(flow_lr.shape), dtype=torch.float32, device=hv.device)
-            kept['flow_lr'][t].copy_(flow_lr)
-        if self._keeps_gru():
-            kept = self.pose_head_inputs
-            if t == 0:
-                kept['x'] = torch.empty((self.iters,) + tuple(xm.shape), dtype=torch.float32, device=hv.device)
-            kept['x'][t].copy_(xm)
-        if self.keep_head_inputs or self._keeps_gru():
-            kept = self.pose_head_inputs
-            if t == 0:
-                f32 = dict(dtype=torch.float32, device=hv.device)
-                kept['d_flow'] = torch.empty((self.iters,) + tuple(d_flow.shape), **f32)
-                kept['mask'] = torch.empty((self.iters,) + tuple(mask.shape), **f32)
-            kept['d_flow'][t].copy_(d_flow)
-            kept['mask'][t].copy_(mask)
-        if self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
-            kept = self.pose_head_inputs
-            if t == 0:
-                f32 = dict(dtype=torch.float32, device=hv.device)
-                kept['hv'] = torch.empty((self.iters,) + tuple(hv.shape), **f32)
-                kept['dm'] = torch.empty((self.iters,) + tuple(dm.shape), **f32)
-                for i, y in enumerate(ys):
-                    s_ = y.shape[0] if y.dim() == 5 else 1
-                    kept[f'y{i}'] = torch.empty((s_, self.iters) + tuple(y.shape[-4:]), **f32)
-            kept['hv'][t].copy_(hv)
-            kept['dm'][t].copy_(dm)
-            for i, y in enumerate(ys):
-                kept[f'y{i}'][:, t].copy_(y if y.dim() == 5 else y.unsqueeze(0))
-        if self.keep_pose_tail_input or self.keep_pose_head_input or self.keep_head_inputs or self._keeps_gru():
-            self.pose_tail_inputs.append(ys[2].clone() if clone else ys[2])
+                shape = tuple(v.shape)
+                self.kept[key] = torch.empty(shape[:axis] + (self.iters,) + shape[axis:], dtype=torch.float32, device=v.device)
+            self.kept[key].select(axis, t).copy_(v)
+        self.kept['tail_inputs'].append(ys[2].clone() if clone else ys[2])
 
+    def check_backward(self, depth: str) -> None:
+        """refuse, before any launch, what ``backward(depth, ...)`` cannot carry: at ``'motion'`` a configuration in which
+        something flows from ``x_t`` back into iteration t - 1; the depths before it refuse nothing"""
+        if _GRAD_DEPTHS.index(depth) < _GRAD_DEPTHS.index('motion'):
+            return
+        if not self.detach_flow:
+            raise NotImplementedError('loss_and_motion_grads: detach_flow=False needs the path from flow_lr of iteration t into '
+                                      'iteration t - 1 (the lookup\'s derivative with respect to its coordinates and a reverse '
+                                      'scan over whole iterations), which has no backward yet')
+        if (self.mask_flow or self.mask_corr) and not self.detach_mask:
+            raise NotImplementedError('loss_and_motion_grads: mask_flow / mask_corr without detach_mask needs the path from the '
+                                      'mask of iteration t - 1 into iteration t\'s motion encoder (a reverse scan over whole '
+                                      'iterations), which has no backward yet')
 
-def _scflow_tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translation: Tensor, depth: Tensor,
-                          internel_k: Tensor, extra_flow_lr=None):
-    """Vector-Jacobian product of the parameter-free tail of every iteration (scflow_decoder.py:222-249: the x8
-    up-sampling of ``flow_lr + delta_flow`` and of the mask, ``get_pose_from_delta_pose``, the pose-induced flow and,
-    with ``detach_flow=False``, its 1/8 down-sampling into the next iteration).
+    def backward(self, depth: str, outs, grads: dict, label: Tensor, ref_rotation: Tensor, ref_translation: Tensor,
+                 depth_map: Tensor, internel_k: Tensor) -> dict:
+        """The backward stages in order, on ``self.kept`` of the forward that returned ``outs`` (run at keep level ``depth``
+        or above), down to the rung ``depth`` of ``_GRAD_DEPTHS`` (``'head'`` .. ``'motion'``): ``tail_backward``,
+        ``pose_pred.tail_backward``, ``pose_pred.conv_backward``, ``heads_backward``, ``gru_backward``, ``motion_backward``.
+        ``grads``: the cotangents at ``outs`` under the keys of ``SCFlowRefiner.loss_and_grads()``.  -> the gradients at the
+        head outputs (``tail_backward``'s dict) with, rung by rung, ``pose_tail_inputs``, ``pose_head_inputs`` = (``g_hvs``,
+        ``g_dms``), ``decoder_heads`` = dict(hidden_states, delta_flow_preds, mask_logits), ``gru`` = dict(initial_hidden,
+        context, motion_features), ``motion`` = dict(correlation, flow_inputs), and ``params``: every stage's parameter
+        gradients summed over the iterations, keyed as in this module's ``named_parameters()``."""
+        if depth not in _GRAD_DEPTHS[2:]:
+            raise ValueError(f'SCFlowDecoder.backward: depth is one of {_GRAD_DEPTHS[2:]}, got {depth!r}')
+        self.check_backward(depth)
+        head, kept = self.pose_pred, self.kept
+        grads = self.tail_backward(outs, grads, ref_rotation, ref_translation, depth_map, internel_k)
+        if depth == 'head':
+            return grads
+        g_ys, params = head.tail_backward(_kept('backward', kept, ('tail_inputs',), 'pose_tail')[0], label,
+                                          grads['delta_rotation_preds'], grads['delta_translation_preds'])
+        grads['pose_tail_inputs'] = g_ys
+        grads['params'] = {'pose_pred.' + key: val for key, val in params.items()}
+        if depth == 'pose_tail':
+            return grads
+        g_hvs, g_dms, params = head.conv_backward(kept, g_ys)
+        grads['pose_head_inputs'] = (g_hvs, g_dms)
+        grads['params'].update(('pose_pred.' + key, val) for key, val in params.items())
+        if depth == 'pose_head':
+            return grads
+        g_h, g_df, g_ml, params = self.heads_backward(kept, g_hvs, g_dms, grads['delta_flow_preds'], grads['masks'])
+        grads['decoder_heads'] = dict(hidden_states=g_h, delta_flow_preds=g_df, mask_logits=g_ml)
+        grads['params'].update(params)
+        if depth == 'decoder_heads':
+            return grads
+        g_h0, g_c, g_x, params = self.gru_backward(kept, g_h)
+        grads['gru'] = dict(initial_hidden=g_h0, context=g_c, motion_features=g_x)
+        grads['params'].update(('gru.' + key, val) for key, val in params.items())
+        if depth == 'gru':
+            return grads
+        g_vol, g_flow_inputs, params = self.motion_backward(kept, g_x)
+        grads['motion'] = dict(correlation=g_vol, flow_inputs=g_flow_inputs)
+        grads['params'].update(params)
+        return grads
 
-    ``outs``: the 7-tuple ``forward`` returned.  ``grads``: cotangents under the keys of ``loss_and_grads()``
-    (``sequence_flow_from_pose``, ``sequence_flow_from_pred``, ``seq_rotations``, ``seq_translations``,
-    ``sequence_masks``), each a list over the iterations, each optional.  ``extra_flow_lr``: optional list of cotangents
-    of ``flow_lr_i`` (N,2,h,w) from a later lookup / motion-encoder backward.  Returns the gradients at the head outputs:
-    ``dict(delta_flow_preds, masks, delta_rotation_preds, delta_translation_preds)``, a list per key (``masks`` at the
-    post-sigmoid map; the sigmoid's derivative belongs to the head backward).  ``detach_flow`` / ``detach_pose`` /
-    ``detach_depth_for_xy`` / ``depth_transform`` are the decoder's.  Launches: one for all up-sampling adjoints, one for
-    the pose scan; one more when a pose-induced flow has a cotangent, one more under ``detach_flow=False``."""
-    rots, transs, d_rots, d_transs = outs[2], outs[3], outs[5], outs[6]
-    T = len(rots)
-    n, H, W = depth.shape
-    scale = 2 ** (self.num_levels - 1)
-    h, w = H // scale, W // scale
-    seq = lambda key: None if grads.get(key) is None else list(grads[key])       # noqa: E731
-    g_fpose, g_fpred, g_mask = seq('sequence_flow_from_pose'), seq('sequence_flow_from_pred'), seq('sequence_masks')
-    for name, s_ in (('sequence_flow_from_pose', g_fpose), ('sequence_flow_from_pred', g_fpred), ('sequence_masks', g_mask),
-                     ('extra_flow_lr', extra_flow_lr)):
-        if s_ is not None and len(s_) != T:
-            raise ValueError(f'tail_backward: {name} has {len(s_)} entries for {T} iterations')
-    dev = depth.device
-    zeros = lambda *shape: torch.zeros((T,) + shape, dtype=torch.float32, device=dev).unbind(0)   # noqa: E731
-    if g_mask is not None:
-        g_mask = [m.view(n, 1, H, W) for m in g_mask]
-    # ---- up-sampling adjoints: g_delta_flow_i = scale U^T g_flow_pred_i, g_mask_i = U^T g_up_mask_i, one launch
-    if g_fpred is not None and g_mask is not None:
-        g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale), second=(g_mask, 1.0))
-    elif g_fpred is not None:
-        g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale)), list(zeros(n, 1, h, w))
-    elif g_mask is not None:
-        g_dflow, g_m = list(zeros(n, 2, h, w)), ops.resize_bilinear_grad(g_mask, (h, w))
-    else:
-        g_dflow, g_m = list(zeros(n, 2, h, w)), list(zeros(n, 1, h, w))
-    # ---- detach_flow=False: flow_lr_i = D(flow_from_pose_{i-1}) / scale, so g_flow_from_pose_{i-1} += D^T (g_flow_lr_i) / scale
-    if not self.detach_flow and T > 1 and (g_fpred is not None or extra_flow_lr is not None):
-        src = g_dflow[1:]
-        add = None if extra_flow_lr is None else list(extra_flow_lr[1:])
-        if g_fpred is None:                       # only the caller's cotangents of flow_lr
-            src, add = [e if e is not None else z for e, z in zip(add, g_dflow[1:])], None
-        if g_fpose is None:
-            g_fpose = ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add) + [None]
-        else:                                     # the caller's cotangents are not written: accumulate into copies
-            acc = [g.clone() for g in g_fpose[:-1]]
-            ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add, out=acc, accumulate=True)
-            g_fpose = acc + [g_fpose[-1]]
-    # ---- re-projection sums of every iteration, one launch
-    sums = None
-    if g_fpose is not None:
-        sums = ops.reproject_flow_grad(g_fpose, depth, internel_k, ref_rotation.contiguous(), ref_translation.contiguous(),
-                                       rots, transs)
-    # ---- combine + reverse scan over the pose updates, one launch
-    g_drot, g_dtrans = ops.pose_update_grad(d_rots, d_transs, ref_rotation.contiguous(), ref_translation.contiguous(), rots, transs,
-                                            g_rots=seq('seq_rotations'), g_transs=seq('seq_translations'),
-                                            reproject_sums=sums, image_hw=(H, W), detach_pose=self.detach_pose,
-                                            detach_depth_for_xy=self.detach_depth_for_xy, label_mode=self.pose_flags())
-    return dict(delta_flow_preds=g_dflow, masks=g_m, delta_rotation_preds=g_drot, delta_translation_preds=g_dtrans)
+    def tail_backward(self, outs, grads, ref_rotation: Tensor, ref_translation: Tensor, depth: Tensor,
+                      internel_k: Tensor, extra_flow_lr=None):
+        """Vector-Jacobian product of the parameter-free tail of every iteration (scflow_decoder.py:222-249: the x8
+        up-sampling of ``flow_lr + delta_flow`` and of the mask, ``get_pose_from_delta_pose``, the pose-induced flow and,
+        with ``detach_flow=False``, its 1/8 down-sampling into the next iteration).
 
-
-SCFlowDecoder.tail_backward = _scflow_tail_backward
-
-_HEAD_PARAMS = tuple(f'{m}.{p}' for m in ('flow_pred.layers.0.conv', 'flow_pred.predict_layer', 'mask_pred.layers.0.conv',
-                                          'mask_pred.predict_layer', 'delta_flow_encoder.0.conv', 'delta_flow_encoder.1.conv',
-                                          'mask_encoder.0.conv', 'mask_encoder.1.conv') for p in ('weight', 'bias'))
-
-
-def _scflow_heads_backward(self, saved: dict, g_hvs: Sequence[Tensor], g_dms: Sequence[Tensor],
-                           g_delta_flows: Sequence[Tensor], g_masks: Sequence[Tensor], param_grads: Optional[dict] = None):
-    """Backward of the two XHeads and the delta-flow / mask encoders (scflow_decoder.py:210-217: seven stride-1
-    convolutions with bias) for the T iterations of a pass at once, M = T N stacked samples, one launch per stage.
-
-    ``saved``: what a forward under ``keep_head_inputs`` left in ``pose_head_inputs`` (``hv`` (T, N, 128, h, w), ``dm``
-    (T, N, 96, h, w), ``d_flow`` (T, N, 2, h, w), the post-sigmoid ``mask`` (T, N, 1, h, w)).  ``g_hvs``, ``g_dms``: the
-    cotangents at ``hv`` and ``dm`` that ``MultiClassPoseHead.conv_backward`` returns; ``g_delta_flows``, ``g_masks``: those
-    at ``d_flow`` and at the post-sigmoid mask that ``tail_backward`` returns.  -> (``g_hidden_states``: the cotangents at
-    ``hv`` through iteration t's own heads, encoders and pose head; ``g_delta_flow_totals``: the complete cotangents at
-    ``d_flow``; ``g_mask_logits``: those at the mask head's pre-sigmoid output; T tensors each; ``param_grads``: the
-    gradients of the 16 parameters summed over all T N samples, keyed as in ``named_parameters()``).  A dict passed in
-    is accumulated into (entries it lacks are created; some but not all of these entries: an error).
-
-    The hidden activations -- ``heads`` (512 channels), ``d1`` (128), ``m1`` (64): wgrad operands and activation masks --
-    are recomputed into stacked buffers by the forward's OWN launches, one iteration at a time at the forward's batch,
-    so dispatch and bits are the forward's.  Chain per stacked sample: act_grad on ``g_dm``; wgrad + dgrad of the
-    encoders' last layers; wgrad of their first layers and dgrad with the tail's cotangents added (the mask's with the
-    sigmoid factor); wgrad of the predict layers and their dgrads into the two halves of one (M, 512, h, w) tensor
-    with the ReLU mask of ``heads``; wgrad and dgrad of the packed hidden layer with ``g_hv`` added."""
-    what = 'heads_backward'
-    T = len(g_hvs)
-    if T == 0 or T > ops.TAIL_MAX_T or any(len(s_) != T for s_ in (g_dms, g_delta_flows, g_masks)):
-        raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent of each kind per iteration')
-    try:
-        hv, dm, d_flow, mask = (saved[k] for k in ('hv', 'dm', 'd_flow', 'mask'))
-    except (KeyError, TypeError):
-        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_head_inputs (hv, dm, d_flow, mask)') from None
-    if hv.dim() != 5 or hv.shape[0] != T or not hv.is_contiguous():
-        raise _lib_error(f'{what}: hv must be a contiguous ({T}, N, C, h, w) tensor, got {tuple(hv.shape)}')
-    n, hc, h, w = hv.shape[1:]
-    fp, mp, de, me = self.flow_pred, self.mask_pred, self.delta_flow_encoder, self.mask_encoder
-    ch = fp.layers[0].conv.out_channels                     # 256: the flow head's rows of the packed hidden layer
-    c_h = ch + mp.layers[0].conv.out_channels
-    c_d1, c_df, c_m1, c_mf = (b.conv.out_channels for b in (de[0], de[1], me[0], me[1]))
-    for name, t_, c in (('dm', dm, c_df + c_mf), ('d_flow', d_flow, 2), ('mask', mask, 1)):
-        if tuple(t_.shape) != (T, n, c, h, w) or not t_.is_contiguous():
-            raise _lib_error(f'{what}: {name} must be a contiguous {(T, n, c, h, w)} tensor, got {tuple(t_.shape)}')
-    for name, seq, c in (('g_hvs', g_hvs, hc), ('g_dms', g_dms, c_df + c_mf), ('g_delta_flows', g_delta_flows, 2),
-                         ('g_masks', g_masks, 1)):
-        if any(tuple(g.shape) != (n, c, h, w) for g in seq):
-            raise _lib_error(f'{what}: {name} are {(n, c, h, w)} tensors')
-    enc_act = de[0].act
-    if any(b.act != enc_act for b in (de[1], me[0], me[1])) or enc_act not in (ACT_NONE, ACT_RELU):
-        raise NotImplementedError('heads_backward: encoders with ReLU or no activation')
-    grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the heads\' and encoders\' gradients', _HEAD_PARAMS,
-                                  param_grads)
-    dst = dict(zip(_HEAD_PARAMS, dst))
-    m = T * n
-    f32 = dict(dtype=torch.float32, device=hv.device)
-    E = lambda *shape: torch.empty(shape, **f32)       # noqa: E731
-    # ---- the forward's own launches, an iteration at a time: heads, d1, m1 in the forward's bits
-    heads, d1, m1 = E(T, n, c_h, h, w), E(T, n, c_d1, h, w), E(T, n, c_m1, h, w)
-    for t in range(T):
-        ops.conv2d(self.packed, hv[t], out=heads[t], act=ACT_RELU)
-        de[0](d_flow[t], out=d1[t])
-        me[0](mask[t], out=m1[t])
-    stack = lambda seq, c: (seq[0].contiguous() if T == 1 else torch.stack(list(seq))).view(m, c, h, w)   # noqa: E731
-    g_hv, g_dm, g_df, g_mk = stack(g_hvs, hc), stack(g_dms, c_df + c_mf), stack(g_delta_flows, 2), stack(g_masks, 1)
-    hv_, dm_, df_, mk_ = hv.view(m, hc, h, w), dm.view(m, c_df + c_mf, h, w), d_flow.view(m, 2, h, w), mask.view(m, 1, h, w)
-    heads_, d1_, m1_ = heads.view(m, c_h, h, w), d1.view(m, c_d1, h, w), m1.view(m, c_m1, h, w)
-    layers = ((c_df, c_d1, de[1].conv), (c_mf, c_m1, me[1].conv), (c_d1, 2, de[0].conv), (c_m1, 1, me[0].conv),
-              (2, ch, fp.predict_layer), (1, c_h - ch, mp.predict_layer), (c_h, hc, None))
-    ks = lambda conv: (3, 3) if conv is None else tuple(conv.kernel_size)      # noqa: E731
-    ws = E(max(ops.conv_s1_wgrad_workspace(m, co, ci, h, w, *ks(cv)) for co, ci, cv in layers))
-    a_or_none = lambda a: a if enc_act != ACT_NONE else None                    # noqa: E731
-
-    def wgrad(g, x, name, conv):
-        return ops.conv_s1_wgrad(g, x, tuple(conv.kernel_size), dw=dst[f'{name}.weight'], db=dst[f'{name}.bias'],
-                                 accumulate=acc, workspace=ws)
-
-    out = {}
-    # 1. encoders, last layers
-    u = ops.act_grad(g_dm, a_or_none(dm_), enc_act)
-    u_df, u_mf = u[:, :c_df], u[:, c_df:]
-    out['delta_flow_encoder.1.conv'] = wgrad(u_df, d1_, 'delta_flow_encoder.1.conv', de[1].conv)
-    g_d1 = ops.conv_s1_dgrad(u_df, de[1].conv.weight, a=a_or_none(d1_), act=enc_act)
-    out['mask_encoder.1.conv'] = wgrad(u_mf, m1_, 'mask_encoder.1.conv', me[1].conv)
-    g_m1 = ops.conv_s1_dgrad(u_mf, me[1].conv.weight, a=a_or_none(m1_), act=enc_act)
-    # 2. encoders, first layers: the tail's cotangents join here
-    out['delta_flow_encoder.0.conv'] = wgrad(g_d1, df_, 'delta_flow_encoder.0.conv', de[0].conv)
-    g_df_total = ops.conv_s1_dgrad(g_d1, de[0].conv.weight, add=g_df)
-    out['mask_encoder.0.conv'] = wgrad(g_m1, mk_, 'mask_encoder.0.conv', me[0].conv)
-    g_logit = ops.conv_s1_dgrad(g_m1, me[0].conv.weight, add=g_mk, a=mk_, act=ACT_SIGMOID)
-    del g_d1, g_m1, u
-    # 3. predict layers: their dgrads write the two halves of one tensor, ReLU mask of heads in the epilogue
-    out['flow_pred.predict_layer'] = wgrad(g_df_total, heads_[:, :ch], 'flow_pred.predict_layer', fp.predict_layer)
-    out['mask_pred.predict_layer'] = wgrad(g_logit, heads_[:, ch:], 'mask_pred.predict_layer', mp.predict_layer)
-    g_heads = E(m, c_h, h, w)
-    ops.conv_s1_dgrad(g_df_total, fp.predict_layer.weight, a=heads_[:, :ch], act=ACT_RELU, out=g_heads[:, :ch])
-    ops.conv_s1_dgrad(g_logit, mp.predict_layer.weight, a=heads_[:, ch:], act=ACT_RELU, out=g_heads[:, ch:])
-    # 4. the packed hidden layer: rows :ch are the flow head's, the rest the mask head's
-    a_, b_ = fp.layers[0].conv, mp.layers[0].conv
-    w_hidden = torch.cat([a_.weight, b_.weight], 0)
-    names_h = ('flow_pred.layers.0.conv', 'mask_pred.layers.0.conv')
-    dw_h = torch.cat([dst[f'{k}.weight'] for k in names_h], 0) if acc else None      # the kernel adds the previous value LAST
-    db_h = torch.cat([dst[f'{k}.bias'] for k in names_h], 0) if acc else None
-    dw_h, db_h = ops.conv_s1_wgrad(g_heads, hv_, (3, 3), dw=dw_h, db=db_h, accumulate=acc, workspace=ws)
-    for name, rows in zip(names_h, (slice(0, ch), slice(ch, c_h))):
-        if acc:
-            out[name] = (dst[f'{name}.weight'].copy_(dw_h[rows]), dst[f'{name}.bias'].copy_(db_h[rows]))
+        ``outs``: the 7-tuple ``forward`` returned.  ``grads``: cotangents under the keys of ``loss_and_grads()``
+        (``sequence_flow_from_pose``, ``sequence_flow_from_pred``, ``seq_rotations``, ``seq_translations``,
+        ``sequence_masks``), each a list over the iterations, each optional.  ``extra_flow_lr``: optional list of cotangents
+        of ``flow_lr_i`` (N,2,h,w) from a later lookup / motion-encoder backward.  Returns the gradients at the head outputs:
+        ``dict(delta_flow_preds, masks, delta_rotation_preds, delta_translation_preds)``, a list per key (``masks`` at the
+        post-sigmoid map; the sigmoid's derivative belongs to the head backward).  ``detach_flow`` / ``detach_pose`` /
+        ``detach_depth_for_xy`` / ``depth_transform`` are the decoder's.  Launches: one for all up-sampling adjoints, one for
+        the pose scan; one more when a pose-induced flow has a cotangent, one more under ``detach_flow=False``."""
+        rots, transs, d_rots, d_transs = outs[2], outs[3], outs[5], outs[6]
+        T = len(rots)
+        n, H, W = depth.shape
+        scale = 2 ** (self.num_levels - 1)
+        h, w = H // scale, W // scale
+        seq = lambda key: None if grads.get(key) is None else list(grads[key])       # noqa: E731
+        g_fpose, g_fpred, g_mask = seq('sequence_flow_from_pose'), seq('sequence_flow_from_pred'), seq('sequence_masks')
+        for name, s_ in (('sequence_flow_from_pose', g_fpose), ('sequence_flow_from_pred', g_fpred), ('sequence_masks', g_mask),
+                         ('extra_flow_lr', extra_flow_lr)):
+            if s_ is not None and len(s_) != T:
+                raise ValueError(f'tail_backward: {name} has {len(s_)} entries for {T} iterations')
+        dev = depth.device
+        zeros = lambda *shape: torch.zeros((T,) + shape, dtype=torch.float32, device=dev).unbind(0)   # noqa: E731
+        if g_mask is not None:
+            g_mask = [m.view(n, 1, H, W) for m in g_mask]
+        # ---- up-sampling adjoints: g_delta_flow_i = scale U^T g_flow_pred_i, g_mask_i = U^T g_up_mask_i, one launch
+        if g_fpred is not None and g_mask is not None:
+            g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale), second=(g_mask, 1.0))
+        elif g_fpred is not None:
+            g_dflow, g_m = ops.resize_bilinear_grad(g_fpred, (h, w), mul=float(scale)), list(zeros(n, 1, h, w))
+        elif g_mask is not None:
+            g_dflow, g_m = list(zeros(n, 2, h, w)), ops.resize_bilinear_grad(g_mask, (h, w))
         else:
-            out[name] = (dw_h[rows].contiguous(), db_h[rows].contiguous())
-    g_hidden = ops.conv_s1_dgrad(g_heads, w_hidden, add=g_hv, w_scratch=E(w_hidden.numel()))
-    for name, (dw_, db_) in out.items():
-        grads[f'{name}.weight'], grads[f'{name}.bias'] = dw_, db_
-    g_hidden, g_df_total, g_logit = g_hidden.view(T, n, hc, h, w), g_df_total.view(T, n, 2, h, w), g_logit.view(T, n, 1, h, w)
-    return ([g_hidden[t] for t in range(T)], [g_df_total[t] for t in range(T)], [g_logit[t] for t in range(T)], grads)
+            g_dflow, g_m = list(zeros(n, 2, h, w)), list(zeros(n, 1, h, w))
+        # ---- detach_flow=False: flow_lr_i = D(flow_from_pose_{i-1}) / scale, so g_flow_from_pose_{i-1} += D^T (g_flow_lr_i)
+        # / scale
+        if not self.detach_flow and T > 1 and (g_fpred is not None or extra_flow_lr is not None):
+            src = g_dflow[1:]
+            add = None if extra_flow_lr is None else list(extra_flow_lr[1:])
+            if g_fpred is None:                       # only the caller's cotangents of flow_lr
+                src, add = [e if e is not None else z for e, z in zip(add, g_dflow[1:])], None
+            if g_fpose is None:
+                g_fpose = ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add) + [None]
+            else:                                     # the caller's cotangents are not written: accumulate into copies
+                acc = [g.clone() for g in g_fpose[:-1]]
+                ops.resize_bilinear_grad(src, (H, W), mul=1.0 / scale, add=add, out=acc, accumulate=True)
+                g_fpose = acc + [g_fpose[-1]]
+        # ---- re-projection sums of every iteration, one launch
+        sums = None
+        if g_fpose is not None:
+            sums = ops.reproject_flow_grad(g_fpose, depth, internel_k, ref_rotation.contiguous(), ref_translation.contiguous(),
+                                           rots, transs)
+        # ---- combine + reverse scan over the pose updates, one launch
+        g_drot, g_dtrans = ops.pose_update_grad(d_rots, d_transs, ref_rotation.contiguous(), ref_translation.contiguous(), rots,
+                                                transs, g_rots=seq('seq_rotations'), g_transs=seq('seq_translations'),
+                                                reproject_sums=sums, image_hw=(H, W), detach_pose=self.detach_pose,
+                                                detach_depth_for_xy=self.detach_depth_for_xy, label_mode=self.pose_flags())
+        return dict(delta_flow_preds=g_dflow, masks=g_m, delta_rotation_preds=g_drot, delta_translation_preds=g_dtrans)
 
+    def heads_backward(self, saved: dict, g_hvs: Sequence[Tensor], g_dms: Sequence[Tensor],
+                       g_delta_flows: Sequence[Tensor], g_masks: Sequence[Tensor], param_grads: Optional[dict] = None):
+        """Backward of the two XHeads and the delta-flow / mask encoders (scflow_decoder.py:210-217: seven stride-1
+        convolutions with bias) for the T iterations of a pass at once, M = T N stacked samples, one launch per stage.
 
-SCFlowDecoder.heads_backward = _scflow_heads_backward
+        ``saved``: what a forward at keep level ``'decoder_heads'`` or above left in ``kept`` (``hv`` (T, N, 128, h, w), ``dm``
+        (T, N, 96, h, w), ``d_flow`` (T, N, 2, h, w), the post-sigmoid ``mask`` (T, N, 1, h, w)).  ``g_hvs``, ``g_dms``: the
+        cotangents at ``hv`` and ``dm`` that ``MultiClassPoseHead.conv_backward`` returns; ``g_delta_flows``, ``g_masks``: those
+        at ``d_flow`` and at the post-sigmoid mask that ``tail_backward`` returns.  -> (``g_hidden_states``: the cotangents at
+        ``hv`` through iteration t's own heads, encoders and pose head; ``g_delta_flow_totals``: the complete cotangents at
+        ``d_flow``; ``g_mask_logits``: those at the mask head's pre-sigmoid output; T tensors each; ``param_grads``: the
+        gradients of the 16 parameters summed over all T N samples, keyed as in ``named_parameters()``).  A dict passed in
+        is accumulated into (entries it lacks are created; some but not all of these entries: an error).
 
+        The hidden activations -- ``heads`` (512 channels), ``d1`` (128), ``m1`` (64): wgrad operands and activation masks --
+        are recomputed into stacked buffers by the forward's OWN launches, one iteration at a time at the forward's batch,
+        so dispatch and bits are the forward's.  Chain per stacked sample: act_grad on ``g_dm``; wgrad + dgrad of the
+        encoders' last layers; wgrad of their first layers and dgrad with the tail's cotangents added (the mask's with the
+        sigmoid factor); wgrad of the predict layers and their dgrads into the two halves of one (M, 512, h, w) tensor
+        with the ReLU mask of ``heads``; wgrad and dgrad of the packed hidden layer with ``g_hv`` added."""
+        what = 'heads_backward'
+        T = len(g_hvs)
+        if T == 0 or T > ops.TAIL_MAX_T or any(len(s_) != T for s_ in (g_dms, g_delta_flows, g_masks)):
+            raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent of each kind per iteration')
+        hv, dm, d_flow, mask = _kept(what, saved, ('hv', 'dm', 'd_flow', 'mask'), 'decoder_heads')
+        if hv.dim() != 5 or hv.shape[0] != T or not hv.is_contiguous():
+            raise _lib_error(f'{what}: hv must be a contiguous ({T}, N, C, h, w) tensor, got {tuple(hv.shape)}')
+        n, hc, h, w = hv.shape[1:]
+        fp, mp, de, me = self.flow_pred, self.mask_pred, self.delta_flow_encoder, self.mask_encoder
+        ch = fp.layers[0].conv.out_channels                     # 256: the flow head's rows of the packed hidden layer
+        c_h = ch + mp.layers[0].conv.out_channels
+        c_d1, c_df, c_m1, c_mf = (b.conv.out_channels for b in (de[0], de[1], me[0], me[1]))
+        for name, t_, c in (('dm', dm, c_df + c_mf), ('d_flow', d_flow, 2), ('mask', mask, 1)):
+            if tuple(t_.shape) != (T, n, c, h, w) or not t_.is_contiguous():
+                raise _lib_error(f'{what}: {name} must be a contiguous {(T, n, c, h, w)} tensor, got {tuple(t_.shape)}')
+        for name, seq, c in (('g_hvs', g_hvs, hc), ('g_dms', g_dms, c_df + c_mf), ('g_delta_flows', g_delta_flows, 2),
+                             ('g_masks', g_masks, 1)):
+            if any(tuple(g.shape) != (n, c, h, w) for g in seq):
+                raise _lib_error(f'{what}: {name} are {(n, c, h, w)} tensors')
+        enc_act = de[0].act
+        if any(b.act != enc_act for b in (de[1], me[0], me[1])) or enc_act not in (ACT_NONE, ACT_RELU):
+            raise NotImplementedError('heads_backward: encoders with ReLU or no activation')
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the heads\' and encoders\' gradients', _HEAD_PARAMS,
+                                      param_grads)
+        dst = dict(zip(_HEAD_PARAMS, dst))
+        m = T * n
+        f32 = dict(dtype=torch.float32, device=hv.device)
+        E = lambda *shape: torch.empty(shape, **f32)       # noqa: E731
+        # ---- the forward's own launches, an iteration at a time: heads, d1, m1 in the forward's bits
+        heads, d1, m1 = E(T, n, c_h, h, w), E(T, n, c_d1, h, w), E(T, n, c_m1, h, w)
+        for t in range(T):
+            ops.conv2d(self.packed, hv[t], out=heads[t], act=ACT_RELU)
+            de[0](d_flow[t], out=d1[t])
+            me[0](mask[t], out=m1[t])
+        g_hv, g_dm, g_df, g_mk = (_stacked(seq, m, c, h, w) for seq, c in ((g_hvs, hc), (g_dms, c_df + c_mf), (g_delta_flows, 2),
+                                                                          (g_masks, 1)))
+        hv_, dm_, df_, mk_ = hv.view(m, hc, h, w), dm.view(m, c_df + c_mf, h, w), d_flow.view(m, 2, h, w), mask.view(m, 1, h, w)
+        heads_, d1_, m1_ = heads.view(m, c_h, h, w), d1.view(m, c_d1, h, w), m1.view(m, c_m1, h, w)
+        layers = ((c_df, c_d1, de[1].conv), (c_mf, c_m1, me[1].conv), (c_d1, 2, de[0].conv), (c_m1, 1, me[0].conv),
+                  (2, ch, fp.predict_layer), (1, c_h - ch, mp.predict_layer), (c_h, hc, None))
+        ks = lambda conv: (3, 3) if conv is None else tuple(conv.kernel_size)      # noqa: E731
+        ws = E(max(ops.conv_s1_wgrad_workspace(m, co, ci, h, w, *ks(cv)) for co, ci, cv in layers))
+        a_or_none = lambda a: a if enc_act != ACT_NONE else None                    # noqa: E731
+        wgrad = partial(_layer_wgrad, grads, dst, acc, ws)
+        # 1. encoders, last layers
+        u = ops.act_grad(g_dm, a_or_none(dm_), enc_act)
+        u_df, u_mf = u[:, :c_df], u[:, c_df:]
+        wgrad('delta_flow_encoder.1.conv', u_df, d1_, de[1].conv)
+        g_d1 = ops.conv_s1_dgrad(u_df, de[1].conv.weight, a=a_or_none(d1_), act=enc_act)
+        wgrad('mask_encoder.1.conv', u_mf, m1_, me[1].conv)
+        g_m1 = ops.conv_s1_dgrad(u_mf, me[1].conv.weight, a=a_or_none(m1_), act=enc_act)
+        # 2. encoders, first layers: the tail's cotangents join here
+        wgrad('delta_flow_encoder.0.conv', g_d1, df_, de[0].conv)
+        g_df_total = ops.conv_s1_dgrad(g_d1, de[0].conv.weight, add=g_df)
+        wgrad('mask_encoder.0.conv', g_m1, mk_, me[0].conv)
+        g_logit = ops.conv_s1_dgrad(g_m1, me[0].conv.weight, add=g_mk, a=mk_, act=ACT_SIGMOID)
+        del g_d1, g_m1, u
+        # 3. predict layers: their dgrads write the two halves of one tensor, ReLU mask of heads in the epilogue
+        wgrad('flow_pred.predict_layer', g_df_total, heads_[:, :ch], fp.predict_layer)
+        wgrad('mask_pred.predict_layer', g_logit, heads_[:, ch:], mp.predict_layer)
+        g_heads = E(m, c_h, h, w)
+        ops.conv_s1_dgrad(g_df_total, fp.predict_layer.weight, a=heads_[:, :ch], act=ACT_RELU, out=g_heads[:, :ch])
+        ops.conv_s1_dgrad(g_logit, mp.predict_layer.weight, a=heads_[:, ch:], act=ACT_RELU, out=g_heads[:, ch:])
+        # 4. the packed hidden layer: rows :ch are the flow head's, the rest the mask head's
+        a_, b_ = fp.layers[0].conv, mp.layers[0].conv
+        w_hidden = torch.cat([a_.weight, b_.weight], 0)
+        names_h = ('flow_pred.layers.0.conv', 'mask_pred.layers.0.conv')
+        dw_h = torch.cat([dst[f'{k}.weight'] for k in names_h], 0) if acc else None      # the kernel adds the previous value LAST
+        db_h = torch.cat([dst[f'{k}.bias'] for k in names_h], 0) if acc else None
+        dw_h, db_h = ops.conv_s1_wgrad(g_heads, hv_, (3, 3), dw=dw_h, db=db_h, accumulate=acc, workspace=ws)
+        for name, rows in zip(names_h, (slice(0, ch), slice(ch, c_h))):
+            kw, kb = f'{name}.weight', f'{name}.bias'
+            if acc:
+                grads[kw], grads[kb] = dst[kw].copy_(dw_h[rows]), dst[kb].copy_(db_h[rows])
+            else:
+                grads[kw], grads[kb] = dw_h[rows].contiguous(), db_h[rows].contiguous()
+        g_hidden = ops.conv_s1_dgrad(g_heads, w_hidden, add=g_hv, w_scratch=E(w_hidden.numel()))
+        g_hidden, g_df_total, g_logit = g_hidden.view(T, n, hc, h, w), g_df_total.view(T, n, 2, h, w), g_logit.view(T, n, 1, h, w)
+        return ([g_hidden[t] for t in range(T)], [g_df_total[t] for t in range(T)], [g_logit[t] for t in range(T)], grads)
 
-def _scflow_gru_backward(self, saved: dict, g_hidden_states: Sequence[Tensor], param_grads: Optional[dict] = None):
-    """``ConvGRU.backward`` of ``self.gru`` on what a forward under ``keep_gru_inputs`` left in ``pose_head_inputs``, with
-    the decoder's channel split checked (``c``: ``cxt_channels``, ``x``: the motion encoder's 126 + 2) -> (``g_h0``,
-    ``g_context``, ``g_motion_features``, ``param_grads``), the parameter names relative to ``self.gru``."""
-    what = 'gru_backward'
-    try:
-        c, x = saved['c'], saved['x']
-    except (KeyError, TypeError):
-        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_gru_inputs (h0, c, x, hv)') from None
-    want = (self.cxt_channels, self.gru.x_channels - self.cxt_channels)
-    if c.dim() != 4 or x.dim() != 5 or (c.shape[1], x.shape[2]) != want:
-        raise _lib_error(f'{what}: c and x must hold {want[0]} and {want[1]} channels, got {tuple(c.shape)} and {tuple(x.shape)}')
-    return self.gru.backward(saved, g_hidden_states, param_grads)
+    def gru_backward(self, saved: dict, g_hidden_states: Sequence[Tensor], param_grads: Optional[dict] = None):
+        """``ConvGRU.backward`` of ``self.gru`` on what a forward at keep level ``'gru'`` or above left in ``kept``, with
+        the decoder's channel split checked (``c``: ``cxt_channels``, ``x``: the motion encoder's 126 + 2) -> (``g_h0``,
+        ``g_context``, ``g_motion_features``, ``param_grads``), the parameter names relative to ``self.gru``."""
+        what = 'gru_backward'
+        c, x = _kept(what, saved, ('c', 'x'), 'gru')
+        want = (self.cxt_channels, self.gru.x_channels - self.cxt_channels)
+        if c.dim() != 4 or x.dim() != 5 or (c.shape[1], x.shape[2]) != want:
+            raise _lib_error(f'{what}: c and x must hold {want[0]} and {want[1]} channels, got {tuple(c.shape)} and '
+                             f'{tuple(x.shape)}')
+        return self.gru.backward(saved, g_hidden_states, param_grads)
 
+    def motion_backward(self, saved: dict, g_motion_features: Sequence[Tensor], param_grads: Optional[dict] = None,
+                        intermediates: Optional[dict] = None):
+        """Backward of the motion encoder and of the correlation lookup with respect to the pyramid (scflow_decoder.py:196-206)
+        for the T iterations of a pass at once.
 
-SCFlowDecoder.gru_backward = _scflow_gru_backward
+        ``saved``: what a forward at keep level ``'motion'`` left in ``kept``: ``x`` (T, N, 128, h, w), ``flow_lr``
+        (T, N, 2, h, w), the ``pyramid`` list with its layout mask ``tiled`` and, under ``mask_corr``, ``mask`` (T, N, 1, h, w).
+        ``g_motion_features``: the T cotangents at ``x_t`` that ``gru_backward`` returns.  -> (``g_vol`` (N h w, h, w): d loss / d
+        level 0 of the correlation pyramid, summed over the iterations, the pooling adjoints of the other levels folded in;
+        ``g_flow_inputs``: T cotangents at the encoder's flow input (``flow_lr``, times the previous mask under ``mask_flow``) --
+        where a backward through the flow recurrence (``detach_flow=False``) would start; ``param_grads``: the ten
+        ``encoder.*`` gradients summed over all T N samples, keyed as in ``named_parameters()``; a dict passed in is accumulated
+        into, a partial one is an error).
 
-
-def _scflow_motion_backward(self, saved: dict, g_motion_features: Sequence[Tensor], param_grads: Optional[dict] = None,
-                            intermediates: Optional[dict] = None):
-    """Backward of the motion encoder and of the correlation lookup with respect to the pyramid (scflow_decoder.py:196-206)
-    for the T iterations of a pass at once.
-
-    ``saved``: what a forward under ``keep_motion_inputs`` left in ``pose_head_inputs``: ``x`` (T, N, 128, h, w), ``flow_lr``
-    (T, N, 2, h, w), the ``pyramid`` list with its layout mask ``tiled`` and, under ``mask_corr``, ``mask`` (T, N, 1, h, w).
-    ``g_motion_features``: the T cotangents at ``x_t`` that ``gru_backward`` returns.  -> (``g_vol`` (N h w, h, w): d loss / d
-    level 0 of the correlation pyramid, summed over the iterations, the pooling adjoints of the other levels folded in;
-    ``g_flow_inputs``: T cotangents at the encoder's flow input (``flow_lr``, times the previous mask under ``mask_flow``) --
-    where a backward through the flow recurrence (``detach_flow=False``) would start; ``param_grads``: the ten
-    ``encoder.*`` gradients summed over all T N samples, keyed as in ``named_parameters()``; a dict passed in is accumulated
-    into, a partial one is an error).
-
-    ``corr_t`` is recomputed by the forward's own lookup launch on the kept pyramid (and ``mul_mask`` under ``mask_corr``),
-    then ``MotionEncoder.backward``, then ``ops.corr_lookup_grad`` on the stacked ``g_corr`` (with the previous iteration's
-    mask -- ones before the first -- as its per-query factor under ``mask_corr``: the product's adjoint under
-    ``detach_mask``).  The lookup's derivative with respect to its coordinates is NOT taken: under ``detach_flow`` nothing
-    reads it."""
-    what = 'motion_backward'
-    T = len(g_motion_features)
-    if T == 0 or T > ops.TAIL_MAX_T:
-        raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at x per iteration')
-    try:
-        x, flow_lr, pyramid, tiled = (saved[k] for k in ('x', 'flow_lr', 'pyramid', 'tiled'))
-        mask = saved['mask'] if self.mask_corr else None
-    except (KeyError, TypeError):
-        raise _lib_error(f'{what}: saved is SCFlowDecoder.pose_head_inputs under keep_motion_inputs (x, flow_lr, pyramid, '
-                         'tiled, mask)') from None
-    if x.dim() != 5 or x.shape[0] != T or not x.is_contiguous():
-        raise _lib_error(f'{what}: x must be a contiguous ({T}, N, 128, h, w) tensor, got {tuple(x.shape)}')
-    n, _, h, w = x.shape[1:]
-    if tuple(flow_lr.shape) != (T, n, 2, h, w) or not flow_lr.is_contiguous():
-        raise _lib_error(f'{what}: flow_lr must be a contiguous {(T, n, 2, h, w)} tensor, got {tuple(flow_lr.shape)}')
-    if len(pyramid) != self.num_levels:
-        raise _lib_error(f'{what}: the pyramid has {len(pyramid)} levels, the decoder {self.num_levels}')
-    kch = self.num_levels * (2 * self.radius + 1) ** 2
-    corr = torch.empty((T, n, kch, h, w), dtype=torch.float32, device=x.device)
-    mask_prev = None
-    if self.mask_corr:
-        if tuple(mask.shape) != (T, n, 1, h, w) or not mask.is_contiguous():
-            raise _lib_error(f'{what}: mask must be a contiguous {(T, n, 1, h, w)} tensor, got {tuple(mask.shape)}')
-        mask_prev = torch.cat([torch.ones_like(mask[:1]), mask[:-1]], 0)
-    for t in range(T):
-        ops.corr_lookup(pyramid, flow_lr[t], self.radius, out=corr[t], tiled_levels=tiled)
+        ``corr_t`` is recomputed by the forward's own lookup launch on the kept pyramid (and ``mul_mask`` under ``mask_corr``),
+        then ``MotionEncoder.backward``, then ``ops.corr_lookup_grad`` on the stacked ``g_corr`` (with the previous iteration's
+        mask -- ones before the first -- as its per-query factor under ``mask_corr``: the product's adjoint under
+        ``detach_mask``).  The lookup's derivative with respect to its coordinates is NOT taken: under ``detach_flow`` nothing
+        reads it."""
+        what = 'motion_backward'
+        T = len(g_motion_features)
+        if T == 0 or T > ops.TAIL_MAX_T:
+            raise _lib_error(f'{what}: 1 .. {ops.TAIL_MAX_T} iterations with one cotangent at x per iteration')
+        x, flow_lr, pyramid, tiled = _kept(what, saved, ('x', 'flow_lr', 'pyramid', 'tiled'), 'motion')
+        mask = _kept(what, saved, ('mask',), 'motion')[0] if self.mask_corr else None
+        if x.dim() != 5 or x.shape[0] != T or not x.is_contiguous():
+            raise _lib_error(f'{what}: x must be a contiguous ({T}, N, 128, h, w) tensor, got {tuple(x.shape)}')
+        n, _, h, w = x.shape[1:]
+        if tuple(flow_lr.shape) != (T, n, 2, h, w) or not flow_lr.is_contiguous():
+            raise _lib_error(f'{what}: flow_lr must be a contiguous {(T, n, 2, h, w)} tensor, got {tuple(flow_lr.shape)}')
+        if len(pyramid) != self.num_levels:
+            raise _lib_error(f'{what}: the pyramid has {len(pyramid)} levels, the decoder {self.num_levels}')
+        kch = self.num_levels * (2 * self.radius + 1) ** 2
+        corr = torch.empty((T, n, kch, h, w), dtype=torch.float32, device=x.device)
+        mask_prev = None
         if self.mask_corr:
-            ops.mul_mask(corr[t], mask_prev[t], out=corr[t])
-    g_corr, g_flow_inputs, grads = self.encoder.backward(dict(corr=corr, x=x), g_motion_features, param_grads, intermediates,
-                                                         prefix='encoder.')
-    g_vol = ops.corr_lookup_grad(g_corr, flow_lr, mask_prev, self.radius, self.num_levels)
-    if intermediates is not None:
-        intermediates.update(corr=corr, mask_prev=mask_prev)
-    return g_vol, g_flow_inputs, grads
+            if tuple(mask.shape) != (T, n, 1, h, w) or not mask.is_contiguous():
+                raise _lib_error(f'{what}: mask must be a contiguous {(T, n, 1, h, w)} tensor, got {tuple(mask.shape)}')
+            mask_prev = torch.cat([torch.ones_like(mask[:1]), mask[:-1]], 0)
+        for t in range(T):
+            ops.corr_lookup(pyramid, flow_lr[t], self.radius, out=corr[t], tiled_levels=tiled)
+            if self.mask_corr:
+                ops.mul_mask(corr[t], mask_prev[t], out=corr[t])
+        g_corr, g_flow_inputs, grads = self.encoder.backward(dict(corr=corr, x=x), g_motion_features, param_grads, intermediates,
+                                                             prefix='encoder.')
+        g_vol = ops.corr_lookup_grad(g_corr, flow_lr, mask_prev, self.radius, self.num_levels)
+        if intermediates is not None:
+            intermediates.update(corr=corr, mask_prev=mask_prev)
+        return g_vol, g_flow_inputs, grads
 
 
-SCFlowDecoder.motion_backward = _scflow_motion_backward
-
-
-def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
+def _scflow_forward_c(self, level, pyramid, tiled, hx, ctx, rot0, trans0, depth, internel_k, label, init_flow,
                       invalid_flow_num, overlap):
     """the refinement loop through ``scf_scflow_iteration``: every scratch buffer and convolution
     descriptor of an iteration is set up ONCE per pass; an iteration is then a handful of pointer
@@ -1604,18 +1638,13 @@ def _scflow_forward_c(self, pyramid, tiled, hx, ctx, rot0, trans0, depth, intern
         it.flow_out, it.flow_pred, it.mask_up = flow.data_ptr(), fpreds[i].data_ptr(), masks[i].data_ptr()
         it.R_out, it.t_out, it.d_rot, it.d_trans = rot.data_ptr(), trans.data_ptr(), drots[i].data_ptr(), dtranss[i].data_ptr()
         ops.scflow_iteration(it)
-        self._keep_pose_inputs(i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask, xm=xm, flow_lr=flow_lr)
+        self._keep_iteration(level, i, hv, dm, raw_ys, clone=True, d_flow=d_flow, mask=mask, xm=xm, flow_lr=flow_lr)
         for lst, v in zip(outs, (flow, fpreds[i], rot, trans, masks[i], drots[i], dtranss[i])):
             lst.append(v)
     if any(overlap):          # the scratch is freed on return: the side stream's last reads are joined already
         pass
     del keep
     return outs
-
-
-def _lib_error(msg):
-    from ._lib import ScflowHipError
-    return ScflowHipError(msg)
 
 
 SCFlowDecoder._forward_c = _scflow_forward_c

@@ -8,9 +8,9 @@ keys.  PnP re-mapping is outside the hot path, and
 ``forward_single_pass`` consumes an already formatted ``data`` dict (what
 ``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).  The loss
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
-``loss()`` returns the forward VALUES the reference trains against and ``loss_and_grads()`` adds their gradients at
-the network's outputs -- the network has no backward and there is no ``train_step``; ``forward(return_loss=True)``
-keeps raising.  The config's ``renderer`` dict is ignored too;
+``loss()`` returns the forward VALUES the reference trains against, ``loss_and_grads()`` adds their gradients at
+the network's outputs and the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) -- the
+encoders have no backward and there is no ``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
@@ -22,7 +22,7 @@ from typing import Dict, Optional, Tuple, Union
 import torch
 
 from . import ops
-from .modules import HipModule, encoder_pair_supported, raft_encoder_pair
+from .modules import _GRAD_DEPTHS, KEEP_LEVELS, HipModule, encoder_pair_supported, raft_encoder_pair
 from .ops import ACT_RELU, ACT_TANH, small_work
 from .registry import REFINERS, build_decoder, build_encoder
 
@@ -227,10 +227,6 @@ class _RenderingRefiner:
         return OrderedDict((k, float(x)) for (k, _), x in zip(named, host))
 
 
-# how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do
-_GRAD_DEPTHS = ('none', 'outputs', 'head', 'pose_tail', 'pose_head', 'decoder_heads', 'gru')
-
-
 @REFINERS.register_module()
 class SCFlowRefiner(_RenderingRefiner, HipModule):
     def __init__(self, seperate_encoder: bool, cxt_channels: int, h_channels: int,
@@ -373,135 +369,86 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         way to call this without an attached renderer; it needs ``gt_masks`` when ``filter_invalid_flow`` is set."""
         return self._loss(data_batch, data, 'none')
 
+    # loss_and_*_grads(): one method per rung of _GRAD_DEPTHS (modules.py, where what has no backward yet is stated once).
+    # Every one returns (loss, None, log_vars, seq_rotations, seq_translations, grads); the values are the bits of loss(),
+    # log_vars still costs one transfer, and from 'head' on every entry the rung before returns keeps its key and its bits.
     def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss()`` plus the training signal at the network's outputs -> (loss, None, log_vars, seq_rotations,
-        seq_translations, grads): ``grads`` maps ``sequence_flow_from_pred``, ``sequence_masks`` and either
-        ``seq_rotations`` / ``seq_translations`` or, when the pose loss is a ``RAFTLoss``, ``sequence_flow_from_pose`` to the
-        list of d loss / d prediction per iteration (``loss = loss_pose + loss_flow + loss_mask``), from the
-        value-and-gradient launches: the values are the bits ``loss()`` returns and ``log_vars`` still costs one
-        transfer.  The network itself has no backward yet."""
+        """``loss()`` plus the training signal at the network's outputs: ``grads`` maps ``sequence_flow_from_pred``,
+        ``sequence_masks`` and either ``seq_rotations`` / ``seq_translations`` or, when the pose loss is a ``RAFTLoss``,
+        ``sequence_flow_from_pose`` to the list of d loss / d prediction per iteration (``loss = loss_pose + loss_flow +
+        loss_mask``), from the value-and-gradient launches."""
         return self._loss(data_batch, data, 'outputs')
 
     def loss_and_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_grads()`` carried through the parameter-free tail of every iteration -> (loss, None, log_vars,
-        seq_rotations, seq_translations, grads): ``grads`` maps ``delta_flow_preds``, ``masks`` (the post-sigmoid map),
-        ``delta_rotation_preds`` and ``delta_translation_preds`` to the list of d loss / d head output per iteration
-        (``SCFlowDecoder.tail_backward`` on the gradients ``loss_and_grads()`` returns).  The values are the bits of
-        ``loss()`` and ``log_vars`` still costs one transfer.  The heads, the GRU and the encoders have no backward yet."""
+        """``loss_and_grads()`` carried through the parameter-free tail of every iteration (``SCFlowDecoder.tail_backward``):
+        ``grads`` maps ``delta_flow_preds``, ``masks`` (the post-sigmoid map), ``delta_rotation_preds`` and
+        ``delta_translation_preds`` to the list of d loss / d head output per iteration.  These REPLACE the keys of
+        ``loss_and_grads()``; every later rung adds to them."""
         return self._loss(data_batch, data, 'head')
 
     def loss_and_pose_tail_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_head_grads()`` carried through the fully connected tail of the pose head -> the same tuple, ``grads``
-        with two more keys: ``pose_tail_inputs``, the list of d loss / d (raw output of the pose head's last convolution)
-        per iteration, and ``params``, the gradients of that tail's parameters (``decoder.pose_pred.conv_layers.2.gn``,
-        ``.fc_layers``, ``.rotation_pred``, ``.translation_pred``; keys as in ``named_parameters()``) summed over the
-        iterations (``MultiClassPoseHead.tail_backward``).  The values are the bits of ``loss()``, the head-output
-        gradients those of ``loss_and_head_grads()``.  ``delta_flow_preds`` / ``masks`` are NOT yet complete gradients: they
-        still lack the contribution that reaches them through the pose head's convolutions and the delta-flow / mask
-        encoders, whose backward (like the XHeads', the GRU's, the lookup's and the encoders') does not exist yet."""
+        """Adds the fully connected tail of the pose head (``MultiClassPoseHead.tail_backward``): ``pose_tail_inputs``, the
+        list of d loss / d (raw output of the pose head's last convolution) per iteration, and ``params``, the gradients of
+        that tail's parameters (``decoder.pose_pred.conv_layers.2.gn``, ``.fc_layers``, ``.rotation_pred``,
+        ``.translation_pred``; keys as in ``named_parameters()``) summed over the iterations.  The top-level
+        ``delta_flow_preds`` / ``masks`` are the tail's partial cotangents at every rung: the complete ones are in
+        ``decoder_heads``."""
         return self._loss(data_batch, data, 'pose_tail')
 
     def loss_and_pose_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_pose_tail_grads()`` carried through the pose head's three convolutions and GroupNorms 0 and 1 -> the
-        same tuple, ``grads`` with one more key: ``pose_head_inputs`` = (``g_hvs``, ``g_dms``), the lists of d loss / d
-        (GRU hidden state ``hv`` (N, 128, h, w)) and d loss / d (delta-flow and mask features ``dm`` (N, 96, h, w)) per
-        iteration; ``params`` now holds the gradient of EVERY parameter of ``decoder.pose_pred``, summed over the iterations
-        (``MultiClassPoseHead.conv_backward`` after ``tail_backward``).  The values are the bits of ``loss()``, every entry
-        ``loss_and_pose_tail_grads()`` returns has its bits.  ``delta_flow_preds`` / ``masks`` are still NOT complete
-        gradients: ``g_dms`` has to be carried through the delta-flow and mask encoders to reach them, and ``g_hvs`` through
-        the XHeads, the GRU, the lookup and the encoders; none of those has a backward yet."""
+        """Adds the pose head's three convolutions and GroupNorms 0 and 1 (``MultiClassPoseHead.conv_backward``):
+        ``pose_head_inputs`` = (``g_hvs``, ``g_dms``), the lists of d loss / d (GRU hidden state ``hv`` (N, 128, h, w)) and
+        d loss / d (delta-flow and mask features ``dm`` (N, 96, h, w)) per iteration; ``params`` now holds the gradient of
+        EVERY parameter of ``decoder.pose_pred``."""
         return self._loss(data_batch, data, 'pose_head')
 
     def loss_and_decoder_head_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_pose_head_grads()`` carried through the two XHeads and the delta-flow / mask encoders
-        (``SCFlowDecoder.heads_backward``) -> the same tuple, ``grads`` with one more key: ``decoder_heads`` =
+        """Adds the two XHeads and the delta-flow / mask encoders (``SCFlowDecoder.heads_backward``): ``decoder_heads`` =
         ``dict(hidden_states, delta_flow_preds, mask_logits)``, a list per key over the iterations.  ``hidden_states[t]`` is
         d loss / d ``hv_t`` (N, 128, h, w) through iteration t's OWN heads, encoders and pose head: the cotangent the GRU
         backward adds the next iteration's to.  ``delta_flow_preds[t]`` is the complete d loss / d ``d_flow_t`` (the
-        tail's plus the delta-flow encoder's), ``mask_logits[t]`` the complete d loss / d (pre-sigmoid mask) of iteration t --
-        except that under ``mask_flow`` / ``mask_corr`` without ``detach_mask`` the path from ``mask_t`` into iteration
-        t + 1's motion encoder is still missing.  ``params`` is extended by the 16 weights and biases of
-        ``decoder.flow_pred``, ``decoder.mask_pred``, ``decoder.delta_flow_encoder`` and ``decoder.mask_encoder``, summed over
-        the iterations: every parameter downstream of the GRU state now has a gradient.  The values are the bits of
-        ``loss()``; every entry ``loss_and_pose_head_grads()`` returns keeps its bits and its key (the top-level
-        ``delta_flow_preds`` / ``masks`` stay the tail's partial cotangents).  ``loss_and_gru_grads()`` carries
-        ``hidden_states`` through the GRU; the lookup, the motion encoder and the image encoders have no backward yet."""
+        tail's plus the delta-flow encoder's), ``mask_logits[t]`` the complete d loss / d (pre-sigmoid mask) of iteration t,
+        both up to the path into iteration t + 1 that no rung carries.  ``params`` is extended by the 16 weights and biases
+        of ``decoder.flow_pred``, ``decoder.mask_pred``, ``decoder.delta_flow_encoder`` and ``decoder.mask_encoder``: every
+        parameter downstream of the GRU state now has a gradient."""
         return self._loss(data_batch, data, 'decoder_heads')
 
     def loss_and_gru_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_decoder_head_grads()`` carried through the GRU by a reverse scan over the iterations
-        (``SCFlowDecoder.gru_backward``) -> the same tuple, ``grads`` with one more key: ``gru`` =
+        """Adds the GRU, a reverse scan over the iterations (``SCFlowDecoder.gru_backward``): ``gru`` =
         ``dict(initial_hidden, context, motion_features)``: d loss / d ``h0`` (N, 128, h, w), the hidden state the context
         encoder hands the decoder; d loss / d ``c`` (N, 128, h, w), its context features, summed over iterations and
         passes; and the list over the iterations of d loss / d ``x_t`` (N, 128, h, w), the motion encoder's 126 channels
         and the 2 flow channels behind them.  ``params`` is extended by the ``decoder.gru.*`` gradients (12 for
-        ``'SeqConv'``, 6 for ``'Conv'``), summed over the iterations.  The values are the bits of ``loss()``; every entry
-        ``loss_and_decoder_head_grads()`` returns keeps its bits and its key.  ``loss_and_motion_grads()`` carries
-        ``motion_features`` through the motion encoder and the lookup; still missing: the backward of the correlation
-        build and the image encoders -- ``initial_hidden`` and ``context`` are where the context encoder's will start --
-        and, under ``detach_flow=False`` and under ``mask_flow`` / ``mask_corr`` without
-        ``detach_mask``, the path from ``motion_features[t]`` back into iteration t - 1 (its flow and its mask), which
-        belongs to the motion-encoder backward: ``decoder_heads`` and the head gradients do not contain it."""
+        ``'SeqConv'``, 6 for ``'Conv'``)."""
         return self._loss(data_batch, data, 'gru')
 
     def loss_and_motion_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
-        """``loss_and_gru_grads()`` carried through the motion encoder and through the correlation lookup to the pyramid
-        (``SCFlowDecoder.motion_backward``) -> the same tuple, ``grads`` with one more key: ``motion`` =
-        ``dict(correlation, flow_inputs)``: d loss / d (level 0 of the correlation pyramid) (N h w, h, w), summed over the
-        iterations with the pooling adjoints of the coarser levels folded in -- where the correlation-build backward and
-        the image encoders will start -- and the list over the iterations of d loss / d (the encoder's flow input)
-        (N, 2, h, w).  ``params`` is extended by the ten ``decoder.encoder.*`` gradients, summed over the iterations: every
-        parameter of the decoder now has a gradient.  The values are the bits of ``loss()``; every entry
-        ``loss_and_gru_grads()`` returns keeps its bits and its key.  The depth ladder of ``_loss`` ends at ``'gru'``; this
-        stage runs beside it, on what a forward under ``keep_motion_inputs`` keeps.
+        """Adds the motion encoder and the correlation lookup with respect to the pyramid
+        (``SCFlowDecoder.motion_backward``): ``motion`` = ``dict(correlation, flow_inputs)``: d loss / d (level 0 of the
+        correlation pyramid) (N h w, h, w), summed over the iterations with the pooling adjoints of the coarser levels
+        folded in, and the list over the iterations of d loss / d (the encoder's flow input) (N, 2, h, w).  ``params`` is
+        extended by the ten ``decoder.encoder.*`` gradients: every parameter of the decoder now has a gradient.
 
         Only where nothing flows from ``x_t`` back into iteration t - 1: ``detach_flow=True``, and ``detach_mask=True``
         whenever ``mask_flow`` or ``mask_corr`` is set (the shipped configuration).  Otherwise the cotangent re-enters the
         previous iteration through ``flow_lr`` (which needs the lookup's derivative with respect to its coordinates) or
-        through the mask, a reverse scan over whole iterations: NotImplementedError."""
-        dec = self.decoder
-        if not dec.detach_flow:
-            raise NotImplementedError('loss_and_motion_grads: detach_flow=False needs the path from flow_lr of iteration t into '
-                                      'iteration t - 1 (the lookup\'s derivative with respect to its coordinates and a reverse '
-                                      'scan over whole iterations), which has no backward yet')
-        if (dec.mask_flow or dec.mask_corr) and not dec.detach_mask:
-            raise NotImplementedError('loss_and_motion_grads: mask_flow / mask_corr without detach_mask needs the path from the '
-                                      'mask of iteration t - 1 into iteration t\'s motion encoder (a reverse scan over whole '
-                                      'iterations), which has no backward yet')
-        kept = dec.keep_motion_inputs
-        dec.keep_motion_inputs = True
-        try:
-            out = self._loss(data_batch, data, 'gru')
-        finally:
-            dec.keep_motion_inputs = kept
-        grads = out[5]
-        g_vol, g_flow_inputs, params = dec.motion_backward(dec.pose_head_inputs, grads['gru']['motion_features'])
-        grads['motion'] = dict(correlation=g_vol, flow_inputs=g_flow_inputs)
-        grads['params'].update(('decoder.' + key, val) for key, val in params.items())
-        return out
+        through the mask, a reverse scan over whole iterations: NotImplementedError (``SCFlowDecoder.check_backward``)."""
+        return self._loss(data_batch, data, 'motion')
 
     def _loss(self, data_batch, data, depth):
         from . import losses as L
         at = _GRAD_DEPTHS.index
         level = at(depth)
         with_grads = level >= at('outputs')
+        dec = self.decoder
+        dec.check_backward(depth)
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
-        dec = self.decoder
-        kept, kept_head, kept_heads = dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs
-        kept_gru = dec.keep_gru_inputs
-        dec.keep_gru_inputs = kept_gru or level >= at('gru')
-        dec.keep_pose_tail_input = kept or level >= at('pose_tail')
-        dec.keep_pose_head_input = kept_head or level >= at('pose_head')
-        dec.keep_head_inputs = kept_heads or level >= at('decoder_heads')
-        try:
+        with dec.keeping(depth if depth in KEEP_LEVELS else 'none'):
             outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
                                  data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
-        finally:
-            dec.keep_pose_tail_input, dec.keep_pose_head_input, dec.keep_head_inputs = kept, kept_head, kept_heads
-            dec.keep_gru_inputs = kept_gru
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
@@ -536,26 +483,10 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
                 grads['seq_translations'] = pose_out[2][1]
         if level >= at('head'):
-            grads = self.decoder.tail_backward(outs, grads, data['ref_rotations'], data['ref_translations'],
-                                               data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
-        if level >= at('pose_tail'):
-            head = dec.pose_pred
-            g_ys, params = head.tail_backward(dec.pose_tail_inputs, labels, grads['delta_rotation_preds'],
-                                              grads['delta_translation_preds'])
-            grads['pose_tail_inputs'] = g_ys
-            if level >= at('pose_head'):
-                g_hvs, g_dms, params = head.conv_backward(dec.pose_head_inputs, g_ys, params)
-                grads['pose_head_inputs'] = (g_hvs, g_dms)
-            grads['params'] = {'decoder.pose_pred.' + key: val for key, val in params.items()}
-            if level >= at('decoder_heads'):
-                g_h, g_df, g_ml, head_params = dec.heads_backward(dec.pose_head_inputs, g_hvs, g_dms,
-                                                                  grads['delta_flow_preds'], grads['masks'])
-                grads['decoder_heads'] = dict(hidden_states=g_h, delta_flow_preds=g_df, mask_logits=g_ml)
-                grads['params'].update(('decoder.' + key, val) for key, val in head_params.items())
-                if level >= at('gru'):
-                    g_h0, g_c, g_x, gru_params = dec.gru_backward(dec.pose_head_inputs, g_h)
-                    grads['gru'] = dict(initial_hidden=g_h0, context=g_c, motion_features=g_x)
-                    grads['params'].update(('decoder.gru.' + key, val) for key, val in gru_params.items())
+            grads = dec.backward(depth, outs, grads, labels, data['ref_rotations'], data['ref_translations'],
+                                 data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
+        if 'params' in grads:
+            grads['params'] = {'decoder.' + key: val for key, val in grads['params'].items()}
         return out + (grads,)
 
     def forward(self, data, data_batch=None, return_loss=False):

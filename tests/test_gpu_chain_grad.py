@@ -93,12 +93,12 @@ def build(variant, iters, decoder=None, shapes_file='state_dict_keys.json', fc1_
 
 def relu_decisions(m):
     """the ReLU decisions of the GPU's forward, layer by layer and iteration by iteration, from what the forward kept
-    (`pose_head_inputs` under keep_motion_inputs) and the FORWARD's own modules run again on it; nothing of the backward
+    (`decoder.kept` at keep level 'motion') and the FORWARD's own modules run again on it; nothing of the backward
     is read -> {(oracle layer prefix, t): bool}.  The float64 chain reads them only at units whose float64
     pre-activation lies within fp32 rounding of zero (`chain_ref64`).  The pose head's GroupNorm + ReLU and fully
     connected ReLUs are not handed over."""
     dec = m.decoder
-    enc, kept = dec.encoder, dec.pose_head_inputs
+    enc, kept = dec.encoder, dec.kept
     ch, cdf = dec.flow_pred.layers[0].conv.out_channels, dec.delta_flow_encoder[1].conv.out_channels
     out = {}
     for t in range(dec.iters):
@@ -134,7 +134,7 @@ def run(m, case, variant, flags, feats=None):
             out = m.loss_and_motion_grads(None, data=data)
         finally:
             del m.extract_feat
-    kept = m.decoder.pose_head_inputs
+    kept = m.decoder.kept
     assert same_bits(kept['h0'], feats[2]) and same_bits(kept['c'], feats[3]), 'the decoder did not start from these inputs'
     hdata = dict(CH.chain_data(case), gt_flow=m._supervision(data, True).cpu())
     res = CH.chain_ref64([f.cpu() for f in feats], CH.decoder_sd64(m.state_dict()), hdata, CH.chain_cfgs(case, variant),

@@ -1,5 +1,5 @@
 """GPU: conv_grad.hip (scf_conv_dgrad, scf_conv_wgrad, scf_conv_wgrad_workspace), MultiClassPoseHead.conv_backward,
-SCFlowDecoder.keep_pose_head_input and SCFlowRefiner.loss_and_pose_head_grads against the float64 restatements and the
+SCFlowDecoder.keep = 'pose_head' and SCFlowRefiner.loss_and_pose_head_grads against the float64 restatements and the
 derived bounds of tests/test_conv_grad_host.py.  Every comparison is `error <= bound` over ALL elements (ratio <= 1) or bit
 equality; there is no absolute tolerance.  The measured ratios are recorded in DESIGN.md section 4.8."""
 import json
@@ -322,7 +322,7 @@ def _conv_check(head, saved, g_y2, b_gy2, g_hvs, g_dms, grads):
 
 
 def _saved_of(head, xs):
-    """what a decoder under keep_pose_head_input keeps, built from the head's own launches -> (saved, tail inputs, a0s, a1s)"""
+    """what a decoder at keep level 'pose_head' keeps, built from the head's own launches -> (saved, tail inputs, a0s, a1s)"""
     ys = [head._conv_outputs(x[:, :128].contiguous(), x[:, 128:].contiguous()) for x in xs]
     five = lambda y: y if y.dim() == 5 else y[None]                 # noqa: E731
     saved = dict(hv=torch.stack([x[:, :128] for x in xs]).contiguous(), dm=torch.stack([x[:, 128:] for x in xs]).contiguous())
@@ -416,16 +416,16 @@ def test_loss_and_pose_head_grads(scflow_model):
             assert all(same_bits(a, b) for a, b in zip(grads[key], seq)), key
     dec = m.decoder
     head = dec.pose_pred
-    assert dec.keep_pose_head_input is False and dec.keep_pose_tail_input is False
-    assert len(dec.pose_tail_inputs) == dec.iters == HL.REFINER_ITERS
+    assert dec.keep == 'none'
+    assert len(dec.kept['tail_inputs']) == dec.iters == HL.REFINER_ITERS
     prefix = 'decoder.pose_pred.'
     assert set(grads['params']) == {prefix + k for k in dict(head.named_parameters())}
     params = {k[len(prefix):]: v for k, v in grads['params'].items()}
     g_hvs, g_dms = grads['pose_head_inputs']
     assert len(g_hvs) == len(g_dms) == dec.iters
-    g_y2, b_gy2 = _tail_refs(head, dec.pose_tail_inputs, data['labels'], grads['delta_rotation_preds'],
+    g_y2, b_gy2 = _tail_refs(head, dec.kept['tail_inputs'], data['labels'], grads['delta_rotation_preds'],
                              grads['delta_translation_preds'], head.label_mode)
-    worst = _conv_check(head, dec.pose_head_inputs, g_y2, b_gy2, g_hvs, g_dms, params)
+    worst = _conv_check(head, dec.kept, g_y2, b_gy2, g_hvs, g_dms, params)
     for key, v in worst.items():
         measured(f'loss_and_pose_head_grads {key}, error / composed bound', v)
         assert v <= 1.0, key
@@ -444,17 +444,19 @@ def test_keeping_the_head_input_changes_no_bit(scflow_model):
     try:
         for c_iteration in (True, False):
             dec.c_iteration = c_iteration
-            dec.pose_tail_inputs, dec.pose_head_inputs = [], {}
+            dec.kept = {}
             off = get()
-            assert dec.pose_tail_inputs == [] and dec.pose_head_inputs == {}
-            dec.keep_pose_head_input = True
+            assert dec.kept == {}
+            dec.keep = 'pose_head'
             on = get()
-            dec.keep_pose_head_input = False
-            kept[c_iteration] = ({k: v.clone() for k, v in dec.pose_head_inputs.items()}, [t.clone() for t in dec.pose_tail_inputs])
+            dec.keep = 'none'
+            assert sorted(dec.kept) == ['dm', 'hv', 'tail_inputs', 'y0', 'y1', 'y2']
+            kept[c_iteration] = ({k: v.clone() for k, v in dec.kept.items() if k != 'tail_inputs'},
+                                 [t.clone() for t in dec.kept['tail_inputs']])
             for a, b in zip(off, on):
                 assert all(same_bits(x, y) for x, y in zip(a, b)), f'c_iteration {c_iteration}'
     finally:
-        dec.keep_pose_head_input, dec.c_iteration = False, old
+        dec.keep, dec.c_iteration = 'none', old
     (sc, tc), (sp, tp) = kept[True], kept[False]
     assert sorted(sc) == sorted(sp) == ['dm', 'hv', 'y0', 'y1', 'y2'] and len(tc) == len(tp) == dec.iters
     assert all(same_bits(sc[k], sp[k]) for k in sc), 'the two loop forms keep different tensors'

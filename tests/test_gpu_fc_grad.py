@@ -1,5 +1,5 @@
 """GPU: fc_grad.hip (scf_fc_operand, scf_pose_select_grad, scf_fc_dgrad, scf_fc_wgrad, scf_group_norm_flat_grad),
-MultiClassPoseHead.tail_backward, SCFlowDecoder.keep_pose_tail_input and SCFlowRefiner.loss_and_pose_tail_grads against the
+MultiClassPoseHead.tail_backward, SCFlowDecoder.keep = 'pose_tail' and SCFlowRefiner.loss_and_pose_tail_grads against the
 float64 restatements and the derived bounds of tests/test_fc_grad_host.py.  Every comparison is `error <= bound` over ALL
 elements (ratio <= 1) or bit equality; there is no absolute tolerance.  The measured ratios are recorded in DESIGN.md
 section 4.7."""
@@ -465,11 +465,11 @@ def test_loss_and_pose_tail_grads(scflow_model):
     for key, seq in base[5].items():
         assert all(same_bits(a, b) for a, b in zip(grads[key], seq)), key
     dec = m.decoder
-    assert dec.keep_pose_tail_input is False and len(dec.pose_tail_inputs) == dec.iters == HL.REFINER_ITERS
+    assert dec.keep == 'none' and len(dec.kept['tail_inputs']) == dec.iters == HL.REFINER_ITERS
     prefix = 'decoder.pose_pred.'
     assert all(k.startswith(prefix) and k in dict(m.named_parameters()) for k in grads['params'])
     params = {k[len(prefix):]: v for k, v in grads['params'].items()}
-    worst = _tail_check(dec.pose_pred, dec.pose_tail_inputs, data['labels'], grads['delta_rotation_preds'],
+    worst = _tail_check(dec.pose_pred, dec.kept['tail_inputs'], data['labels'], grads['delta_rotation_preds'],
                         grads['delta_translation_preds'], grads['pose_tail_inputs'], params, dec.pose_pred.label_mode)
     for key, v in worst.items():
         measured(f'loss_and_pose_tail_grads {key}, error / composed bound', v)
@@ -488,14 +488,15 @@ def test_keeping_the_tail_input_changes_no_bit(scflow_model, c_iteration):
     old = dec.c_iteration
     dec.c_iteration = c_iteration
     try:
-        dec.pose_tail_inputs = []
+        dec.kept = {}
         off = get()
-        assert dec.pose_tail_inputs == []
-        dec.keep_pose_tail_input = True
+        assert dec.kept == {}
+        dec.keep = 'pose_tail'
         on = get()
-        kept = list(dec.pose_tail_inputs)
+        assert sorted(dec.kept) == ['tail_inputs']
+        kept = list(dec.kept['tail_inputs'])
     finally:
-        dec.keep_pose_tail_input, dec.c_iteration = False, old
+        dec.keep, dec.c_iteration = 'none', old
     assert len(kept) == dec.iters
     for a, b in zip(off, on):
         assert all(same_bits(x, y) for x, y in zip(a, b))

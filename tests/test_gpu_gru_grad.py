@@ -1,5 +1,5 @@
 """GPU: gru_grad.hip (scf_gru_gate_grad_q, scf_gru_gate_grad_r, scf_gru_carry, scf_gru_gate_state), ConvGRU.backward /
-recompute_gates, SCFlowDecoder.keep_gru_inputs / gru_backward and SCFlowRefiner.loss_and_gru_grads against the float64
+recompute_gates, SCFlowDecoder.keep = 'gru' / gru_backward and SCFlowRefiner.loss_and_gru_grads against the float64
 restatement and the derived bounds of tests/test_gru_grad_host.py.  Every comparison is `error <= bound` over ALL
 elements (ratio <= 1) or bit equality; there is no absolute tolerance.  The measured ratios are recorded in DESIGN.md
 section 4.11."""
@@ -459,11 +459,11 @@ def test_loss_and_gru_grads(scflow_model):
         return same_bits(a, b)
     for key, v in base[5].items():
         assert same({k: grads[key][k] for k in v} if key == 'params' else grads[key], v), key
-    assert dec.keep_gru_inputs is False and dec.keep_head_inputs is False and dec.keep_pose_head_input is False
+    assert dec.keep == 'none'
     g = grads['gru']
     assert sorted(g) == ['context', 'initial_hidden', 'motion_features'] and len(g['motion_features']) == dec.iters
-    saved = dec.pose_head_inputs
-    assert sorted(saved) == ['c', 'd_flow', 'dm', 'h0', 'hv', 'mask', 'x', 'y0', 'y1', 'y2']
+    saved = dec.kept
+    assert sorted(saved) == ['c', 'd_flow', 'dm', 'h0', 'hv', 'mask', 'tail_inputs', 'x', 'y0', 'y1', 'y2']
     gates = dec.gru.recompute_gates(saved)
     got = (g['initial_hidden'], g['context'], g['motion_features'], {k: grads['params']['decoder.gru.' + k] for k in GH.param_names('SeqConv')})
     for key, v in _check(dec.gru, 'SeqConv', saved, gates, grads['decoder_heads']['hidden_states'], got).items():
@@ -485,28 +485,30 @@ def test_keeping_the_gru_inputs_changes_no_bit(scflow_model):
     get = lambda: m.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'], data['ref_translations'],   # noqa: E731
                              data['rendered_depths'], data['internel_k'], data['labels'])
     old = dec.c_iteration
-    kept = {}
+    kept, tails = {}, {}
     try:
         for c_iteration in (True, False):
             dec.c_iteration = c_iteration
-            dec.pose_tail_inputs, dec.pose_head_inputs = [], {}
+            dec.kept = {}
             off = get()
-            assert dec.pose_tail_inputs == [] and dec.pose_head_inputs == {}
-            dec.keep_gru_inputs = True
+            assert dec.kept == {}
+            dec.keep = 'gru'
             on = get()
-            dec.keep_gru_inputs = False
-            assert dec.keep_head_inputs is False and dec.keep_pose_head_input is False
-            kept[c_iteration] = {k: v.clone() for k, v in dec.pose_head_inputs.items()}
+            dec.keep = 'none'
+            assert sorted(dec.kept) == ['c', 'd_flow', 'dm', 'h0', 'hv', 'mask', 'tail_inputs', 'x', 'y0', 'y1', 'y2']
+            kept[c_iteration] = {k: v.clone() for k, v in dec.kept.items() if k != 'tail_inputs'}
+            tails[c_iteration] = [t.clone() for t in dec.kept['tail_inputs']]
             for a, b in zip(off, on):
                 assert all(same_bits(x, y) for x, y in zip(a, b)), f'c_iteration {c_iteration}'
     finally:
-        dec.keep_gru_inputs, dec.c_iteration = False, old
+        dec.keep, dec.c_iteration = 'none', old
     sc, sp = kept[True], kept[False]
     assert sorted(sc) == sorted(sp) == ['c', 'd_flow', 'dm', 'h0', 'hv', 'mask', 'x', 'y0', 'y1', 'y2']
     n, (h, w) = sc['hv'].shape[1], sc['hv'].shape[3:]
     assert sc['h0'].shape == (n, 128, h, w) and sc['c'].shape == (n, 128, h, w) and sc['x'].shape == (dec.iters, n, 128, h, w)
     assert all(v.is_contiguous() for v in sc.values())
     assert all(same_bits(sc[k], sp[k]) for k in sc), 'the two loop forms keep different tensors'
+    assert len(tails[True]) == len(tails[False]) == dec.iters and all(same_bits(a, b) for a, b in zip(tails[True], tails[False]))
     assert not same_bits(sc['x'][0], sc['x'][1]) and not same_bits(sc['h0'], sc['hv'][0])
     # the kept tensors are the forward's own: the GRU run again from them gives the kept states
     again = _forward(dec.gru, sc['h0'], sc['c'], sc['x'])

@@ -1,5 +1,5 @@
 """GPU: conv_s1_grad.hip (scf_conv_s1_dgrad, scf_conv_s1_wgrad, scf_conv_s1_wgrad_workspace, scf_act_grad),
-SCFlowDecoder.heads_backward / keep_head_inputs and SCFlowRefiner.loss_and_decoder_head_grads against the float64
+SCFlowDecoder.heads_backward / keep = 'decoder_heads' and SCFlowRefiner.loss_and_decoder_head_grads against the float64
 restatements and the derived bounds of tests/test_head_grad_host.py.  Every comparison is `error <= bound` over ALL
 elements (ratio <= 1) or bit equality; there is no absolute tolerance.  The measured ratios are recorded in DESIGN.md
 section 4.10."""
@@ -297,7 +297,7 @@ def _decoder(act_cfg=dict(type='ReLU'), seed=5):
 
 
 def _saved_of(dec, hvs):
-    """what a decoder under keep_head_inputs keeps, built from the forward's own launches -> (saved, activations)"""
+    """what a decoder at keep level 'decoder_heads' keeps, built from the forward's own launches -> (saved, activations)"""
     keep = {k: [] for k in ('hv', 'heads', 'd_flow', 'mask', 'd1', 'm1', 'dm')}
     for hv in hvs:
         n, _, h, w = hv.shape
@@ -412,13 +412,13 @@ def test_loss_and_decoder_head_grads(scflow_model):
         else:
             assert all(same_bits(a, b) for a, b in zip(grads[key], seq)), key
     dec = m.decoder
-    assert dec.keep_head_inputs is False and dec.keep_pose_head_input is False and dec.keep_pose_tail_input is False
+    assert dec.keep == 'none'
     head_names = {'decoder.pose_pred.' + k for k in dict(dec.pose_pred.named_parameters())}
     assert set(grads['params']) == head_names | {'decoder.' + k for k in HH.HEAD_NAMES}
     dh = grads['decoder_heads']
     assert sorted(dh) == ['delta_flow_preds', 'hidden_states', 'mask_logits'] and all(len(v) == dec.iters for v in dh.values())
-    saved = dec.pose_head_inputs
-    assert sorted(saved) == ['d_flow', 'dm', 'hv', 'mask', 'y0', 'y1', 'y2']
+    saved = dec.kept
+    assert sorted(saved) == ['d_flow', 'dm', 'hv', 'mask', 'tail_inputs', 'y0', 'y1', 'y2']
     _, acts = _saved_of(dec, list(saved['hv']))
     assert all(same_bits(acts[k], saved[k]) for k in ('dm', 'd_flow', 'mask')), 'the kept tensors are the forward\'s own'
     g_hvs, g_dms = grads['pose_head_inputs']
@@ -441,18 +441,19 @@ def test_keeping_the_head_inputs_changes_no_bit(scflow_model):
     try:
         for c_iteration in (True, False):
             dec.c_iteration = c_iteration
-            dec.pose_tail_inputs, dec.pose_head_inputs = [], {}
+            dec.kept = {}
             off = get()
-            assert dec.pose_tail_inputs == [] and dec.pose_head_inputs == {}
-            dec.keep_head_inputs = True
+            assert dec.kept == {}
+            dec.keep = 'decoder_heads'
             on = get()
-            dec.keep_head_inputs = False
-            assert dec.keep_pose_head_input is False
-            kept[c_iteration] = ({k: v.clone() for k, v in dec.pose_head_inputs.items()}, [t.clone() for t in dec.pose_tail_inputs])
+            dec.keep = 'none'
+            assert sorted(dec.kept) == ['d_flow', 'dm', 'hv', 'mask', 'tail_inputs', 'y0', 'y1', 'y2']
+            kept[c_iteration] = ({k: v.clone() for k, v in dec.kept.items() if k != 'tail_inputs'},
+                                 [t.clone() for t in dec.kept['tail_inputs']])
             for a, b in zip(off, on):
                 assert all(same_bits(x, y) for x, y in zip(a, b)), f'c_iteration {c_iteration}'
     finally:
-        dec.keep_head_inputs, dec.c_iteration = False, old
+        dec.keep, dec.c_iteration = 'none', old
     (sc, tc), (sp, tp) = kept[True], kept[False]
     assert sorted(sc) == sorted(sp) == ['d_flow', 'dm', 'hv', 'mask', 'y0', 'y1', 'y2'] and len(tc) == len(tp) == dec.iters
     n, (h, w) = sc['hv'].shape[1], sc['hv'].shape[3:]

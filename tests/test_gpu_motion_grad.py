@@ -1,4 +1,4 @@
-"""GPU: corr_lookup_grad.hip (scf_corr_lookup_grad), MotionEncoder.backward, SCFlowDecoder.keep_motion_inputs /
+"""GPU: corr_lookup_grad.hip (scf_corr_lookup_grad), MotionEncoder.backward, SCFlowDecoder.keep = 'motion' /
 motion_backward and SCFlowRefiner.loss_and_motion_grads against the float64 restatements and the derived bounds of
 tests/test_motion_grad_host.py.  Every comparison is `error <= bound` over ALL elements (ratio <= 1) or bit equality; the
 one relative tolerance is the fixture's measured float64-vs-fp32 margin.  The measured ratios are recorded in DESIGN.md
@@ -275,7 +275,7 @@ def test_kernels_against_the_reference_fixture():
 
 
 # ================================================================================================= the refiner's entry
-KEPT = ['c', 'd_flow', 'dm', 'flow_lr', 'h0', 'hv', 'mask', 'pyramid', 'tiled', 'x', 'y0', 'y1', 'y2']
+KEPT = ['c', 'd_flow', 'dm', 'flow_lr', 'h0', 'hv', 'mask', 'pyramid', 'tail_inputs', 'tiled', 'x', 'y0', 'y1', 'y2']
 
 
 def _check_volume(dec, saved, im, g_vol):
@@ -307,9 +307,8 @@ def test_loss_and_motion_grads(scflow_model):  # noqa: F811
         return same_bits(a, b)
     for key, v in base[5].items():
         assert same({k: grads[key][k] for k in v} if key == 'params' else grads[key], v), key
-    assert dec.keep_motion_inputs is False and dec.keep_gru_inputs is False and dec.keep_head_inputs is False
-    assert dec.keep_pose_head_input is False and dec.keep_pose_tail_input is False
-    saved = dec.pose_head_inputs
+    assert dec.keep == 'none'
+    saved = dec.kept
     assert sorted(saved) == KEPT
     mo = grads['motion']
     T, n, _, h, w = saved['flow_lr'].shape
@@ -378,25 +377,25 @@ def test_keeping_the_motion_inputs_changes_no_bit(scflow_model):  # noqa: F811
     try:
         for c_iteration in (True, False):
             dec.c_iteration = c_iteration
-            dec.pose_tail_inputs, dec.pose_head_inputs = [], {}
+            dec.kept = {}
             off = _get_pose(m, data)
-            assert dec.pose_tail_inputs == [] and dec.pose_head_inputs == {}
-            dec.keep_motion_inputs = True
+            assert dec.kept == {}
+            dec.keep = 'motion'
             on = _get_pose(m, data)
-            dec.keep_motion_inputs = False
-            assert dec.keep_gru_inputs is False and dec.keep_head_inputs is False and dec.keep_pose_head_input is False
-            kept[c_iteration] = dict(dec.pose_head_inputs)
+            dec.keep = 'none'
+            kept[c_iteration] = dict(dec.kept)
             kept[c_iteration]['flow_lr'] = kept[c_iteration]['flow_lr'].clone()
             for a, b in zip(off, on):
                 assert all(same_bits(x, y) for x, y in zip(a, b)), f'c_iteration {c_iteration}'
     finally:
-        dec.keep_motion_inputs, dec.c_iteration = False, old
+        dec.keep, dec.c_iteration = 'none', old
     sc, sp = kept[True], kept[False]
     assert sorted(sc) == sorted(sp) == KEPT
     T, n, _, h, w = sc['x'].shape
     assert sc['flow_lr'].shape == (T, n, 2, h, w) and sc['flow_lr'].is_contiguous() and sc['tiled'] == sp['tiled']
     assert len(sc['pyramid']) == dec.num_levels and all(same_bits(a, b) for a, b in zip(sc['pyramid'], sp['pyramid']))
-    assert all(same_bits(sc[k], sp[k]) for k in sc if k not in ('pyramid', 'tiled')), 'the two loop forms keep different tensors'
+    assert all(same_bits(sc[k], sp[k]) for k in sc if k not in ('pyramid', 'tiled', 'tail_inputs')), 'the two loop forms keep different tensors'
+    assert len(sc['tail_inputs']) == len(sp['tail_inputs']) == T and all(same_bits(a, b) for a, b in zip(sc['tail_inputs'], sp['tail_inputs']))
     assert not same_bits(sc['flow_lr'][0], sc['flow_lr'][1])
     # the kept tensors are the forward's own: lookup + encoder run again from them give the kept x
     for t in range(T):
@@ -411,9 +410,9 @@ def test_motion_backward_under_mask_corr(scflow_model):  # noqa: F811
     data = HL.refiner_data(case, DEV)
     dec = m.decoder
     try:
-        dec.mask_corr, dec.keep_motion_inputs = True, True
+        dec.mask_corr, dec.keep = True, 'motion'
         _get_pose(m, data)
-        saved = dict(dec.pose_head_inputs)
+        saved = dict(dec.kept)
         T, n, _, h, w = saved['x'].shape
         gen = MH.gen(77)
         g_x = [D(torch.randn((n, 128, h, w), generator=gen)) for _ in range(T)]
@@ -430,5 +429,5 @@ def test_motion_backward_under_mask_corr(scflow_model):  # noqa: F811
         with pytest.raises(ScflowHipError):
             dec.motion_backward({k: v for k, v in saved.items() if k != 'mask'}, g_x)
     finally:
-        dec.mask_corr, dec.keep_motion_inputs = False, False
-        dec.pose_tail_inputs, dec.pose_head_inputs = [], {}
+        dec.mask_corr, dec.keep = False, 'none'
+        dec.kept = {}

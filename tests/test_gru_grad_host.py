@@ -300,7 +300,7 @@ def test_symbols_are_declared_exported_and_bound():
         assert hasattr(lib, name) and name in _lib.SIGNATURES, name
     assert all(hasattr(ops, n) for n in ('gru_gate_grad_q', 'gru_gate_grad_r', 'gru_carry', 'gru_gate_state'))
     assert hasattr(ConvGRU, 'backward') and hasattr(SCFlowDecoder, 'gru_backward') and hasattr(SCFlowRefiner, 'loss_and_gru_grads')
-    assert _GRAD_DEPTHS[-1] == 'gru' and _GRAD_DEPTHS[-2] == 'decoder_heads'
+    assert _GRAD_DEPTHS[-3:] == ('decoder_heads', 'gru', 'motion')
     for net in NETS:
         assert list(ConvGRU(8, 8, net).param_names()) == param_names(net)
         assert set(param_names(net)) == {k for k, _ in ConvGRU(8, 8, net).named_parameters()}

@@ -216,7 +216,7 @@ def test_symbols_are_declared_exported_and_bound():
     assert callable(ops.corr_lookup_grad) and callable(MotionEncoder.backward) and callable(MotionEncoder.branches)
     assert callable(SCFlowDecoder.motion_backward) and callable(SCFlowRefiner.loss_and_motion_grads)
     dec = scflow_amd.build_refiner(scflow_amd.scflow_model_cfg(iters=2)).decoder
-    assert dec.keep_motion_inputs is False and dec.detach_mask is True
+    assert dec.keep == 'none' and dec.detach_mask is True
     # lk_centre has ONE definition, shared by the forward and the adjoint
     csrc = os.path.join(ROOT, 'scflow_amd', 'csrc')
     for name in ('corr_lookup.hip', 'corr_lookup_grad.hip'):

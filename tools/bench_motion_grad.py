@@ -3,7 +3,7 @@
 ``scf_corr_lookup_grad``) at batch 32, 8 iterations, 32 x 32 maps, radius 4, 4 levels, random weights, features, flows and
 cotangents.  Device events bracket a window of calls; every shape is warmed up first; the columns alternate inside one run.
     python tools/bench_motion_grad.py [N]   -> one JSON line
-``hip_us`` is ``motion_backward`` from what a forward under ``keep_motion_inputs`` keeps: the T lookups and the
+``hip_us`` is ``motion_backward`` from what a forward at keep level ``'motion'`` keeps: the T lookups and the
 recomputation of ``c1``, ``f1``, ``cf`` by the forward's own launches (``recompute_us`` times both alone), the ten
 convolution-gradient launches over the T N stacked samples, and the lookup adjoint.  ``launch_us`` times each kind of
 launch alone, at the shape the stage gives it.  ``lookup_grad_floor_us`` is the adjoint's compulsory traffic (``g_corr``
