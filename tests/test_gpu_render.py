@@ -15,7 +15,8 @@ import scflow_amd
 from scflow_amd import ops
 from scflow_amd.mesh import MeshRenderer, MeshStore, icosphere, make_mesh
 
-from test_render_host import SHIPPED, colored_icosphere, cube, intrinsics, look_at_pose, render_reference, sample_zmin
+from test_render_host import (SHIPPED, check_ambiguous_cap, colored_icosphere, cube, intrinsics, look_at_pose,
+                              render_reference, sample_zmin)
 
 DEV = 'cuda:0'
 pytestmark = pytest.mark.gpu
@@ -42,6 +43,7 @@ def _render(store, labels, poses, Ks, H, W, **kw):
 def _check(out, i, mesh, pose, K, H, W, lights=dict(default_lights=True, seperate_lights=True), batch_zmin=None,
            what=''):
     ref = render_reference(mesh, pose[0], pose[1], K, H, W, batch_zmin=batch_zmin, **lights)
+    check_ambiguous_cap(ref, what)                 # what the comparison leaves out is at most 1 % of the image
     ok = ~ref['ambiguous']
     face = out['pix_to_face'][i].numpy()
     z = out['zbuf'][i].numpy().astype(np.float64)

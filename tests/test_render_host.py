@@ -1,7 +1,9 @@
 """CPU: the mesh renderer's host side -- PLY reader, labels from file names, MeshRenderer's option checks, the
 pixel sampling formula, the C entry points' argument checks -- and ``render_reference``, a float64 brute-force
 restatement of the semantics render.hip states, checked here on closed-form cases and used by
-test_gpu_render.py as the yardstick."""
+test_gpu_render.py and test_gpu_render_edges.py as the yardstick.  The scene lists of the latter (ragged sizes,
+fx != fy, sub-pixel faces, full chunks, skipped faces, constructed ties) live here, next to the restatement, with the
+cap on the pixels a comparison may leave out; the CPU tests at the end check both without a GPU."""
 import ctypes as C
 import os
 import struct
@@ -91,7 +93,8 @@ def render_reference(mesh, R, t, K, H, W, default_lights=True, seperate_lights=T
         sz[better] = bz[better]
         bz[better] = zz[better]
         bf[better] = f
-        bb[better] = (pb / q[..., None])[better]
+        with np.errstate(divide='ignore', invalid='ignore'):
+            bb[better] = (pb / q[..., None])[better]
     covered = best_f >= 0
     with np.errstate(invalid="ignore"):
         amb |= covered & (np.abs(second - best_z) <= depth_tol * best_z)
@@ -144,6 +147,271 @@ def cube(size):
     f = [(a, b, c) for a, b, c, d in quads] + [(a, c, d) for a, b, c, d in quads]
     col = (v / size + 0.5).clip(0, 1)
     return make_mesh(v, f, colors=col)
+
+
+def intrinsics2(fx, fy, cx, cy):
+    return np.array([[fx, 0, cx], [0, fy, cy], [0, 0, 1]], dtype=np.float32)
+
+
+def soup(n, seed):
+    """n random triangles of 40-120 mm in a 200 mm box: heavy occlusion, random winding and colours."""
+    g = np.random.default_rng(seed)
+    centers = g.uniform(-100, 100, size=(n, 1, 3))
+    verts = (centers + g.uniform(-60, 60, size=(n, 3, 3))).reshape(-1, 3)
+    return make_mesh(verts, np.arange(3 * n).reshape(n, 3), colors=g.uniform(0, 1, size=(3 * n, 3)))
+
+
+# ------------------------------------------------------------------- the ambiguous set and its cap (DESIGN.md 4.14)
+AMBIGUOUS_CAP = 0.01
+LIGHTS = [dict(default_lights=True, seperate_lights=True), dict(default_lights=True, seperate_lights=False),
+          dict(default_lights=False, seperate_lights=True), dict(default_lights=False, seperate_lights=False)]
+
+
+def check_ambiguous_cap(ref, what=''):
+    """the cap on what a comparison may leave out: at most 1 % of an image's pixels are `ambiguous`."""
+    share = float(ref['ambiguous'].sum()) / ref['ambiguous'].size
+    assert share <= AMBIGUOUS_CAP, f'{what}: {share:.3%} of the pixels ambiguous (cap 1 %)'
+    return share
+
+
+# ----------------------------------------------------------------- scenes at the renderer's edges (DESIGN.md 4.14)
+class Scene:
+    """one sample: mesh, pose (R, t), K, image size; `all_lights` = cheap enough to restate under the four light
+    settings; `min_cover` = the share of covered pixels the restatement must at least report (a scene that renders
+    nothing tests nothing)."""
+
+    def __init__(self, name, mesh, pose, K, H, W, all_lights=True, min_cover=0.02):
+        self.name, self.mesh, self.pose, self.K, self.H, self.W = name, mesh, pose, K, H, W
+        self.all_lights, self.min_cover = all_lights, min_cover
+        self._ref = {}
+
+    def reference(self, default_lights=True, seperate_lights=True, batch_zmin=None, background=(.5, .5, .5)):
+        """render_reference of the scene, computed once per setting and shared (never modify it)."""
+        key = (default_lights, seperate_lights, batch_zmin, tuple(background))
+        if key not in self._ref:
+            self._ref[key] = render_reference(self.mesh, self.pose[0], self.pose[1], self.K, self.H, self.W,
+                                              default_lights, seperate_lights, background, batch_zmin)
+        return self._ref[key]
+
+    def zmin(self):
+        return sample_zmin(self.mesh, *self.pose)
+
+    def __repr__(self):
+        return self.name
+
+
+EDGE_POSE = look_at_pose(0.3, -0.4, 0.2, 600.0, 10.0, -5.0)
+
+# H > W, W > H, neither a multiple of the 16 x 16 tile, one tile and a part of one, min(H, W) = 1 (pixel_range's
+# step = 0: every pixel of the long axis samples the same point, at (1, 5) u = 2.0 for all five columns)
+RAGGED_SIZES = [(50, 37), (17, 90), (33, 33), (15, 15), (31, 64), (1, 1), (1, 5), (5, 1), (2, 3)]
+
+
+def _scenes(build):
+    cache = []
+
+    def get():
+        if not cache:
+            cache.extend(build())
+        return cache
+    return get
+
+
+@_scenes
+def ragged_scenes():
+    """an icosphere under fy = 1.3 fx and an off-centre principal point at every size with min(H, W) >= 15; below
+    that a cube under fx = fy = 3, which covers the few sampling points there are."""
+    out = []
+    ico, cb = colored_icosphere(3, 70.0), cube(120.0)
+    for H, W in RAGGED_SIZES:
+        s = min(H, W)
+        if s >= 15:
+            K = intrinsics2(3.0 * s, 3.9 * s, (W - 1) / 2 + 2.3, (H - 1) / 2 - 1.7)
+            out.append(Scene(f'ragged {H}x{W}', ico, EDGE_POSE, K, H, W, min_cover=0.05))
+        else:
+            K = intrinsics2(3.0, 3.0, (W - 1) / 2, (H - 1) / 2)
+            out.append(Scene(f'ragged {H}x{W}', cb, EDGE_POSE, K, H, W, min_cover=1 / 6))
+    return out
+
+
+@_scenes
+def anisotropic_scenes():
+    """fx != fy by 1.5 x or more and a principal point several pixels off centre, H > W and W > H."""
+    return [Scene('aniso cube 50x37', cube(120.0), EDGE_POSE, intrinsics2(90, 150, 20.3, 30.1), 50, 37, min_cover=0.3),
+            Scene('aniso cube 37x50', cube(120.0), EDGE_POSE, intrinsics2(150, 90, 30.1, 14.3), 37, 50, min_cover=0.3),
+            Scene('aniso icosphere 31x64', colored_icosphere(3, 70.0), look_at_pose(-0.7, 1.1, 2.5, 450.0, -20.0, 15.0),
+                  intrinsics2(160, 80, 37.4, 12.2), 31, 64, min_cover=0.2)]
+
+
+@_scenes
+def subpixel_scenes():
+    """20 480 faces on a disc of 8 px radius: about 93 faces per covered pixel, nearly every face's box is the
+    +-1 widening of pixel_range and nothing else."""
+    return [Scene('subpixel icosphere(5) 48x40', colored_icosphere(5, 60.0), look_at_pose(0.3, -0.4, 0.2, 900.0, 3.0, -2.0),
+                  intrinsics2(120, 120, 20.1, 23.2), 48, 40, all_lights=False, min_cover=0.08)]
+
+
+@_scenes
+def close_scenes():
+    """faces many tiles large: a cube that fills the frame from outside, and a soup straddling the image plane
+    (faces partly and wholly behind the camera) at a ragged size."""
+    return [Scene('close cube 37x50', cube(120.0), look_at_pose(0.05, -0.03, 0.02, 110.0, 2.0, -1.0),
+                  intrinsics2(60, 60, 24.8, 17.7), 37, 50, min_cover=1.0),
+            Scene('close soup 37x50', soup(200, 11), look_at_pose(0.1, 0.2, 0.0, 40.0),
+                  intrinsics2(60, 45, 25.3, 17.1), 37, 50, min_cover=0.3)]
+
+
+def stacked_triangles(n, reverse):
+    """n triangles far larger than the view, 10 mm apart in depth from z = 0 (object frame), one colour each; face
+    k is the k-th nearest, or with `reverse` the k-th farthest (the nearest is then face n - 1)."""
+    g = np.random.default_rng(5)
+    tri = np.array([[-9000, -6000, 0], [9000, -6000, 0], [0, 12000, 0]], np.float64)
+    order = np.arange(n)[::-1] if reverse else np.arange(n)
+    verts = np.concatenate([tri + [0, 0, 10.0 * d] for d in order])
+    colors = np.repeat(g.uniform(0.1, 1, size=(n, 3)), 3, axis=0)
+    return make_mesh(verts, np.arange(3 * n).reshape(n, 3), colors=colors)
+
+
+@_scenes
+def full_chunk_scenes():
+    """300 faces that each cover the whole image: every one of the first chunk's 256 faces hits every tile (the
+    compacted list is full), and with the list reversed the winner, face 299, sits in the second chunk."""
+    pose = look_at_pose(0.02, -0.03, 0.01, 500.0, 4.0, -3.0)
+    K = intrinsics2(40, 52, 17.2, 15.1)
+    return [Scene('full chunk, winner 299', stacked_triangles(300, True), pose, K, 33, 33, min_cover=1.0),
+            Scene('full chunk, winner 0', stacked_triangles(300, False), pose, K, 33, 33, min_cover=1.0)]
+
+
+@_scenes
+def light_batch_scenes():
+    """one batch of three: zmin - 400 is negative for the first (the light sits at the origin) and positive for
+    the others, and the batch-wide znear of the non-separate, non-default setting comes from the first alone."""
+    ico = colored_icosphere(2, 70.0)
+    K = intrinsics2(70, 95, 33.9, 13.8)
+    return [Scene(f'light batch tz={tz}', ico, look_at_pose(0.3, -0.4, 0.2, tz, 10.0, -5.0), K, 31, 64, min_cover=0.01)
+            for tz in (300.0, 600.0, 900.0)]
+
+
+SCENE_LISTS = dict(RAGGED=ragged_scenes, ANISOTROPIC=anisotropic_scenes, SUBPIXEL=subpixel_scenes, CLOSE=close_scenes,
+                   FULL_CHUNK=full_chunk_scenes, LIGHT_BATCH=light_batch_scenes)
+
+
+# ------------------------------------------------------------------------------------------- skipped faces
+SKIP_FACES = (0, 68, 128, 148, 255, 257, 308, 319)  # the first, the last, around the chunk boundary of 256, and five
+                                                    # that skip_scene's pose sees (68, 128, 148, 257, 308)
+
+
+def skipped_face_meshes():
+    """(degenerate, out_of_range, clean): an icosphere(2) in which the faces SKIP_FACES are, alternately, (a, a, c)
+    and three collinear vertices; its twin in which the same faces carry the vertex indices -1 and nv; and the
+    mesh with those faces removed, with the map from its face indices to the twins'.  The collinear vertices are
+    appended (inside the sphere), and all three meshes share vertices, normals and colours, so the kept faces shade
+    alike.  make_mesh refuses indices outside the mesh: the twin is built as a Mesh directly."""
+    from scflow_amd.mesh import Mesh
+    base = colored_icosphere(2, 60.0)
+    extra = np.array([[-20, -10, 5], [0, 0, 5], [20, 10, 5]], np.float32)        # collinear, exactly
+    verts = np.concatenate([base.verts, extra])
+    normals = np.concatenate([base.normals, np.tile(np.float32([0, 0, 1]), (3, 1))])
+    colors = np.concatenate([base.colors, np.full((3, 3), 0.9, np.float32)])
+    nv, nb = len(verts), len(base.verts)
+    deg, oob = base.faces.copy(), base.faces.copy()
+    for j, f in enumerate(SKIP_FACES):
+        a, _, c = base.faces[f]
+        deg[f] = (a, a, c) if j % 2 == 0 else (nb, nb + 1, nb + 2)
+        oob[f] = (a, -1, c) if j % 2 == 0 else (nv, a, c)
+    keep = np.setdiff1d(np.arange(len(base.faces)), SKIP_FACES)
+    mk = lambda faces: Mesh(verts, np.ascontiguousarray(faces, dtype=np.int32), normals, colors)   # noqa: E731
+    return mk(deg), mk(oob), mk(base.faces[keep]), keep
+
+
+def skip_scene():
+    deg, oob, clean, keep = skipped_face_meshes()
+    K = intrinsics2(150, 190, 20.9, 27.3)
+    return Scene('skipped faces 50x37', deg, EDGE_POSE, K, 50, 37, min_cover=0.2), oob, clean, keep
+
+
+CLIP_FACES = 50
+
+
+def clip_scenes():
+    """(the soup's first CLIP_FACES faces as a scene, the whole soup, a cube of fewer faces than the clip as a
+    scene): a store of the whole soup and the cube whose max_faces is lowered to CLIP_FACES renders the first as
+    the restatement of the soup's first CLIP_FACES faces and leaves the second alone.  The clipped mesh keeps every
+    vertex, so zmin, and with it the light, is the whole soup's."""
+    from scflow_amd.mesh import Mesh
+    full = soup(120, 9)
+    first = Mesh(full.verts, np.ascontiguousarray(full.faces[:CLIP_FACES]), full.normals, full.colors)
+    pose, K = look_at_pose(-0.7, 1.1, 2.5, 450.0, -20.0, 15.0), intrinsics2(70, 95, 17.9, 26.2)
+    return (Scene('clip soup[:50] 50x37', first, pose, K, 50, 37, min_cover=0.2), full,
+            Scene('clip cube 50x37', cube(120.0), EDGE_POSE, K, 50, 37, min_cover=0.1))
+
+
+# ------------------------------------------------------------------------------------------- tie scenes
+TIE_SIZE, TIE_LINE, TIE_Z, TIE_F = 64, 20, 500.0, 125.0
+
+
+def tie_coord(i):
+    """sampling point i of a 64-pixel axis, (126 i + 63) / 128: exact in fp32."""
+    return (126 * i + 63) / 128
+
+
+def shared_edge_scene(axis, first):
+    """two fronto-parallel quads at z = 500 (R = I, t = (0, 0, 500)) sharing the edge X = 0 (axis 0; Y = 0 for axis
+    1), projected onto column (row) TIE_LINE of a 64 x 64 image.  `first` = 0 lists the quad on the negative side
+    first, 1 the other.  Faces are listed as [inner triangle, edge-owning triangle] per quad, so the faces that own
+    the shared edge are 1 and 3 and the expected winner on the line is face 1, of the quad listed first.
+
+    Every number is a small dyadic rational: f / z = 1/4, the corners sit at multiples of 4 mm, the principal point
+    and the sampling points are multiples of 1/128 px.  The fp32 records are therefore exact, the edge functions on
+    the shared edge are exactly 0 for both owners, and both owners' depths 1 / ((w0 a + w1 a + w2 a) / s), a =
+    fl32(1/500), are the same bits: each product has at most 26 + 24 bits, their sum is (w0 + w1 + w2) a, which is
+    representable, and the quotient by s is a.  The tie is exact and the face index alone decides it.
+    -> (mesh, K, pixels (rows, cols) of the line inside the quads, winner face, the first quad alone as a mesh)."""
+    line = tie_coord(TIE_LINE)
+    other = 31.3125
+    K = intrinsics2(TIE_F, TIE_F, line, other) if axis == 0 else intrinsics2(TIE_F, TIE_F, other, line)
+    ext, half = 64.0, 40.0                       # the quads reach 16 px from the edge and +-10 px along it
+
+    def quad(sign, color):
+        # corners: e0, e1 on the shared edge, o0, o1 away from it
+        e0, e1, o0, o1 = [0, -half], [0, half], [sign * ext, -half], [sign * ext, half]
+        c = np.array([o0, e0, e1, o1], np.float64)
+        if axis == 1:
+            c = c[:, ::-1]
+        v = np.concatenate([c, np.zeros((4, 1))], 1)
+        return v, np.array([(0, 2, 3), (0, 1, 2)]), np.tile(np.asarray(color, np.float64), (4, 1))   # inner, owner
+    quads = [quad(-1, (0.9, 0.2, 0.1)), quad(+1, (0.1, 0.3, 0.8))]
+    if first == 1:
+        quads = quads[::-1]
+    verts = np.concatenate([q[0] for q in quads])
+    faces = np.concatenate([quads[0][1], quads[1][1] + 4])
+    colors = np.concatenate([q[2] for q in quads])
+    nrm = np.tile(np.float32([0, 0, -1]), (8, 1))
+    mesh = make_mesh(verts, faces, normals=nrm, colors=colors)
+    alone = make_mesh(verts[:4], faces[:2], normals=nrm[:4], colors=colors[:4])
+    idx = np.arange(TIE_SIZE)
+    c = pixel_coord(idx, TIE_SIZE, TIE_SIZE)
+    inside = idx[(c > other - half * TIE_F / TIE_Z) & (c < other + half * TIE_F / TIE_Z)]
+    fixed = np.full_like(inside, TIE_LINE)
+    pixels = (inside, fixed) if axis == 0 else (fixed, inside)
+    return mesh, K, pixels, 1, alone
+
+
+TIE_POSE = (np.eye(3, dtype=np.float32), np.array([0, 0, TIE_Z], np.float32))
+
+
+def duplicate_face_scene(first):
+    """two faces on identical vertex positions (duplicated vertices, different colours), `first` choosing which
+    colour face 0 carries: identical fp32 records, identical depth bits, so every covered pixel is face 0.
+    -> (mesh, the mesh of face 0 alone, pose, K, H, W)."""
+    tri = np.array([[-70, -50, 10], [80, -30, -25], [-10, 75, 30]], np.float64)
+    cols = [np.array([[.9, .1, .1], [.8, .3, .1], [.7, .1, .3]]), np.array([[.1, .2, .9], [.1, .4, .8], [.3, .1, .7]])]
+    if first == 1:
+        cols = cols[::-1]
+    nrm = np.tile(_unit(np.cross(tri[1] - tri[0], tri[2] - tri[0])), (6, 1))
+    mesh = make_mesh(np.concatenate([tri, tri]), [(0, 1, 2), (3, 4, 5)], normals=nrm, colors=np.concatenate(cols))
+    alone = make_mesh(tri, [(0, 1, 2)], normals=nrm[:3], colors=cols[0])
+    return mesh, alone, EDGE_POSE, intrinsics2(110, 150, 19.7, 26.4), 50, 37
 
 
 # ------------------------------------------------------------------------------------------- PLY
@@ -373,3 +641,139 @@ def test_reference_depth_order_and_behind_camera():
     np.testing.assert_allclose(out['zbuf'][cov], 300, rtol=1e-12)
     behind = make_mesh(big - [0, 0, 100], [(0, 1, 2)])       # every vertex at z <= 0: skipped
     assert (render_reference(behind, np.eye(3), np.zeros(3), K, H, W)['face'] == -1).all()
+
+
+# ------------------------------------------------------------------------- the edge scenes, restatement only
+def _existing_gpu_scenes():
+    """every compared scene of test_gpu_render.py, restated here so that its ambiguous share is measured
+    without a GPU: (name, mesh, pose, K, H, W)."""
+    import math
+    poses = [look_at_pose(0.3, -0.4, 0.2, 600.0, 10.0, -5.0), look_at_pose(-0.7, 1.1, 2.5, 450.0, -20.0, 15.0),
+             look_at_pose(2.0, 0.1, -0.9, 800.0, 0.0, 0.0)]
+    out = []
+    meshes = {0: cube(120.0), 1: colored_icosphere(3, 70.0)}
+    for i in range(6):
+        out.append((f'cube/icosphere {i}', meshes[i % 2], poses[i // 2], intrinsics(300.0, 128, 128), 128, 128))
+    for i in range(2):
+        out.append((f'soup {i}', soup(300, 3), poses[i], intrinsics(120.0, 64, 64), 64, 64))
+    out.append(('64x96', colored_icosphere(3, 80.0), look_at_pose(0.2, 0.5, 0.1, 500.0, 40.0, -10.0),
+                intrinsics(150.0, 64, 96), 64, 96))
+    meshes = {0: cube(100.0), 1: colored_icosphere(2, 60.0), 3: soup(60, 5)}
+    labels = [3, 0, 1, 1, 0, 3, 0, 1]
+    g = np.random.default_rng(8)
+    ps = [look_at_pose(*g.uniform(-math.pi, math.pi, 3), g.uniform(350, 700), *g.uniform(-30, 30, 2)) for _ in labels]
+    Ks = [intrinsics(g.uniform(90, 140), 64, 64) for _ in labels]
+    for i, l in enumerate(labels):
+        out.append((f'mixed {i}', meshes[l], ps[i], Ks[i], 64, 64))
+    out.append(('behind', soup(200, 11), look_at_pose(0.1, 0.2, 0.0, 40.0), intrinsics(60.0, 64, 64), 64, 64))
+    return out
+
+
+def test_existing_gpu_scenes_stay_under_the_ambiguous_cap():
+    """_check of test_gpu_render.py asserts the cap on the GPU machine; this is the same condition from the
+    restatement alone."""
+    for name, mesh, pose, K, H, W in _existing_gpu_scenes():
+        ref = render_reference(mesh, pose[0], pose[1], K, H, W)
+        print(f'[measured] {name}: ambiguous {check_ambiguous_cap(ref, name):.3%}, covered {(ref["face"] >= 0).mean():.1%}')
+
+
+@pytest.mark.parametrize('which', ['RAGGED', 'ANISOTROPIC', 'SUBPIXEL', 'CLOSE', 'FULL_CHUNK', 'LIGHT_BATCH'])
+def test_edge_scenes_stay_under_the_ambiguous_cap(which):
+    """every scene of the new lists through render_reference only: at most 1 % of its pixels are ambiguous, and it
+    covers what its list is there for."""
+    for s in SCENE_LISTS[which]():
+        ref = s.reference()
+        share, cover = check_ambiguous_cap(ref, s.name), (ref['face'] >= 0).mean()
+        print(f'[measured] {s.name}: ambiguous {share:.3%}, covered {cover:.1%}')
+        assert cover >= s.min_cover, f'{s.name}: {cover:.1%} covered'
+        assert ref['zbuf'].shape == (s.H, s.W)
+
+
+def test_edge_scene_lists_reach_their_branches():
+    assert {(s.H, s.W) for s in ragged_scenes()} == set(RAGGED_SIZES)
+    assert any(s.H > s.W and s.H % 16 and s.W % 16 for s in ragged_scenes())
+    assert any(s.W > s.H and s.H % 16 and s.W % 16 for s in ragged_scenes())
+    assert sum(min(s.H, s.W) == 1 for s in ragged_scenes()) == 3
+    # (1, 5): one sampling point for the five columns, and the restatement renders them alike
+    assert (pixel_coord(np.arange(5), 5, 1) == 2.0).all()
+    ref = next(s for s in ragged_scenes() if (s.H, s.W) == (1, 5)).reference()
+    assert (ref['face'] == ref['face'][0, 0]).all() and ref['face'][0, 0] >= 0 and (ref['zbuf'] == ref['zbuf'][0, 0]).all()
+    for s in anisotropic_scenes():
+        fx, fy = float(s.K[0, 0]), float(s.K[1, 1])
+        assert max(fx / fy, fy / fx) >= 1.3
+        assert abs(s.K[0, 2] - (s.W - 1) / 2) >= 1.5 and abs(s.K[1, 2] - (s.H - 1) / 2) >= 1.5
+    assert any(s.H > s.W for s in anisotropic_scenes()) and any(s.W > s.H for s in anisotropic_scenes())
+    # sub-pixel: far more faces than covered pixels
+    s = subpixel_scenes()[0]
+    assert len(s.mesh.faces) / max((s.reference()['face'] >= 0).sum(), 1) > 50
+    # full chunk: one winner, in the second chunk of 256 for the reversed list and face 0 for the other
+    a, b = full_chunk_scenes()
+    assert len(a.mesh.faces) >= 300 and (a.reference()['face'] == 299).all() and (b.reference()['face'] == 0).all()
+    # the light batch: zmin - 400 on both sides of 0, the batch minimum from the first sample
+    z = [s.zmin() for s in light_batch_scenes()]
+    assert z[0] < 400 < z[1] < z[2] and np.floor(z[0] / 100) != np.floor(z[1] / 100)
+    # the soup has faces wholly and partly behind the camera
+    s = close_scenes()[1]
+    zf = (s.mesh.verts.astype(np.float64) @ s.pose[0].T.astype(np.float64) + s.pose[1])[:, 2].reshape(-1, 3)
+    assert (zf <= 0).all(1).any() and ((zf <= 0).any(1) & (zf > 0).any(1)).any()
+
+
+def test_skipped_face_meshes_restate_as_the_mesh_without_them():
+    s, oob, clean, keep = skip_scene()
+    ref = s.reference()
+    check_ambiguous_cap(ref, s.name)
+    assert (ref['face'] >= 0).mean() >= s.min_cover and not np.isin(ref['face'], SKIP_FACES).any()
+    nv = len(oob.verts)
+    bad = ((oob.faces < 0) | (oob.faces >= nv)).any(1)
+    assert sorted(np.nonzero(bad)[0]) == sorted(SKIP_FACES) and oob.faces.min() == -1 and oob.faces.max() == nv
+    np.testing.assert_array_equal(np.delete(oob.faces, SKIP_FACES, 0), np.delete(s.mesh.faces, SKIP_FACES, 0))
+    want = render_reference(clean, s.pose[0], s.pose[1], s.K, s.H, s.W)
+    ok = ~ref['ambiguous']
+    np.testing.assert_array_equal(ref['face'][ok], np.where(want['face'] >= 0, keep[want['face']], -1)[ok])
+    np.testing.assert_array_equal(ref['zbuf'][ok], want['zbuf'][ok])
+    np.testing.assert_array_equal(ref['rgb'][ok], want['rgb'][ok])
+    # some skipped face would have been seen: without its neighbours' cover the test would prove nothing
+    vis = render_reference(colored_icosphere(2, 60.0), s.pose[0], s.pose[1], s.K, s.H, s.W)['face']
+    assert np.isin(vis, SKIP_FACES).any()
+
+
+def test_clip_scenes_differ_from_the_whole_mesh():
+    first, full, cb = clip_scenes()
+    ref = first.reference()
+    check_ambiguous_cap(ref, first.name)
+    check_ambiguous_cap(cb.reference(), cb.name)
+    assert (ref['face'] >= 0).mean() >= first.min_cover and len(cb.mesh.faces) < CLIP_FACES < len(full.faces)
+    whole = render_reference(full, *first.pose, first.K, first.H, first.W)
+    assert (whole['face'] >= CLIP_FACES).mean() > 0.1       # a renderer that ignores the clip shows other faces
+    assert first.zmin() == sample_zmin(full, *first.pose)
+
+
+@pytest.mark.parametrize('axis', [0, 1])
+@pytest.mark.parametrize('first', [0, 1])
+def test_shared_edge_scene_is_exact_and_ambiguous_in_the_restatement(axis, first):
+    mesh, K, (rows, cols), winner, alone = shared_edge_scene(axis, first)
+    assert len(rows) == 20 and winner == 1
+    assert np.float32(tie_coord(TIE_LINE)) == tie_coord(TIE_LINE) == pixel_coord(TIE_LINE, TIE_SIZE, TIE_SIZE)
+    ref = render_reference(mesh, *TIE_POSE, K, TIE_SIZE, TIE_SIZE)
+    assert ref['ambiguous'][rows, cols].all() and (ref['face'][rows, cols] >= 0).all()
+    check_ambiguous_cap(ref, 'shared edge')                 # the line is 20 of 4096 pixels: the rest is compared
+    np.testing.assert_array_equal(ref['zbuf'][rows, cols], TIE_Z)
+    one = render_reference(alone, *TIE_POSE, K, TIE_SIZE, TIE_SIZE)
+    assert (one['face'][rows, cols] == 1).all()             # the quad alone: its edge-owning triangle covers the line
+    side = one['face'] >= 0
+    assert 250 < side.sum() < 400 and side[rows, cols].all()
+    # the two orders put different colours on the line
+    other = render_reference(shared_edge_scene(axis, 1 - first)[4], *TIE_POSE, K, TIE_SIZE, TIE_SIZE)
+    assert np.abs(one['rgb'][rows, cols] - other['rgb'][rows, cols]).max() > 0.1
+
+
+@pytest.mark.parametrize('first', [0, 1])
+def test_duplicate_face_scene(first):
+    mesh, alone, pose, K, H, W = duplicate_face_scene(first)
+    np.testing.assert_array_equal(mesh.verts[:3], mesh.verts[3:])
+    assert np.abs(mesh.colors[:3] - mesh.colors[3:]).max(1).min() > 0.3
+    ref = render_reference(alone, *pose, K, H, W)
+    check_ambiguous_cap(ref, 'duplicate face')
+    assert (ref['face'] >= 0).mean() > 0.1
+    both = render_reference(mesh, *pose, K, H, W)
+    assert (both['ambiguous'] == ((both['face'] >= 0) | ref['ambiguous'])).all()     # every covered pixel is a depth tie
