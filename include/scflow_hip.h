@@ -1021,6 +1021,73 @@ int scf_conv_s1_wgrad(const float* g, int64_t g_stride, const float* x, int64_t 
                       int KH, int KW, scf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Backward of the context encoder's remaining layers (raft_encoder.py:286-314, resnet.py:14-94 with eval-mode BatchNorm;
+ * encoder_grad.hip): the weight gradient of the thin-input 7x7 / stride-2 stem, the input and weight gradient of a
+ * down-sampling block's 1x1 / stride-2 shortcut, a per-channel sum (the bias gradient scf_conv_wgrad lacks), and the
+ * BatchNorm fold with its gradient.  fp32; no atomics, allocation, synchronisation or read-back; every sum has one order
+ * fixed by the shapes (encoder_grad.hip), so results are bit-identical from run to run.  Half-size maps: Ho = (Hin - 1) / 2
+ * + 1, Wo = (Win - 1) / 2 + 1, any Hin, Win >= 1.  A null required pointer, a non-positive size, maps that do not belong
+ * together, an unknown act, act != NONE without a, a sample stride below C H W, a workspace that is too small: SCF_EINVAL;
+ * a geometry that is not built: SCF_EUNSUPPORTED; both with nothing launched or written.  Sample strides are in elements.
+ * w / dW are raw parameters in the torch layout.  Added without a version bump; the presence of scf_conv_stem_wgrad marks
+ * the feature.
+ * --------------------------------------------------------------------------------- */
+
+/* dW[co][ci][ky][kx] = sum_{m, oy, ox} g[m, co, oy, ox] x[m, ci, 2 oy - 3 + ky, 2 ox - 3 + kx]  (zero outside the map),
+ * db[co] = sum g (db NULL: none), of F.conv2d(x, w, b, stride=2, padding=3) with a 7x7 kernel and Cin <= 4 (another
+ * kernel, stride or padding, the encoder's stride-1 stem of scale 1/4 included, or a wider input: SCF_EUNSUPPORTED).
+ * g (M, Cout, Ho, Wo), x (M, Cin, Hin, Win).  A GEMM of Cout x 49 Cin on v_mfma_f32_32x32x2_f32 whose patch operand is
+ * built from input rows staged in LDS.  Chunks (m, oy, segment of 16 output pixels) row-major are cut into S splits of
+ * consecutive chunks; a split is ONE fma chain from +0 per element, chunks then pixels ascending (zeros in the padding
+ * and past Wo), db one chain of plain adds in the same order; the second launch takes partial 0, adds partials 1 .. S - 1
+ * in ascending order and, with accumulate != 0, the previous value of dW / db last.
+ * workspace: scf_conv_stem_wgrad_workspace(...) floats of device memory (-1: invalid sizes). */
+int64_t scf_conv_stem_wgrad_workspace(int M, int Cout, int Cin, int Ho, int Wo);
+int scf_conv_stem_wgrad(const float* g, int64_t g_stride, const float* x, int64_t x_stride, float* dW, float* db,
+                        int accumulate, float* workspace, int64_t workspace_floats, int M, int Cout, int Cin, int Ho,
+                        int Wo, int Hin, int Win, int KH, int KW, int stride, int pad, scf_stream_t stream);
+
+/* The join at the input of a down-sampling block, whose 1x1 / stride-2 shortcut F.conv2d(x, w, stride=2) reads the even
+ * pixels:  gx[m, ci, iy, ix] = act'(a) (add + [iy and ix even] sum_co g[m, co, iy / 2, ix / 2] w[co, ci])
+ * g (M, Cout, Ho, Wo); w (Cout, Cin); add (the 3x3 / stride-2 layer's input gradient; NULL: none), a, gx (M, Cin, Hin,
+ * Win).  Per even pixel ONE fma chain from +0 over co ascending (padded with zeros to a multiple of 32), then + add, then
+ * the factor as scf_act_grad; every other pixel gets act'(a) add.  A sample's result depends on that sample alone. */
+int scf_conv_ds_dgrad(const float* g, int64_t g_stride, const float* w, const float* add, int64_t add_stride,
+                      const float* a, int64_t a_stride, int act, float* gx, int64_t gx_stride, int M, int Cout, int Cin,
+                      int Ho, int Wo, int Hin, int Win, scf_stream_t stream);
+
+/* dW[co][ci] = sum_{m, oy, ox} g[m, co, oy, ox] x[m, ci, 2 oy, 2 ox], db[co] = sum g (db NULL: none).  Splits of
+ * consecutive chunks (m, oy, segment of 16 output pixels), ONE fma chain from +0 per element inside a split, and the
+ * combine launch, all as scf_conv_stem_wgrad.  workspace: scf_conv_ds_wgrad_workspace(...) floats. */
+int64_t scf_conv_ds_wgrad_workspace(int M, int Cout, int Cin, int Ho, int Wo);
+int scf_conv_ds_wgrad(const float* g, int64_t g_stride, const float* x, int64_t x_stride, float* dW, float* db,
+                      int accumulate, float* workspace, int64_t workspace_floats, int M, int Cout, int Cin, int Ho, int Wo,
+                      int Hin, int Win, scf_stream_t stream);
+
+/* out[c] = sum_{m, i} g[m, c, i], g (M, C, n) with a sample stride: the bias gradient of a layer whose weight gradient
+ * has none.  q = (m, i) row-major is cut into S splits of `per` elements (a multiple of 256); in a split thread t adds
+ * q0 + t, q0 + t + 256, ... in one chain from +0, then the 256 values pairwise, v[t] += v[t + k] for k = 128, ..., 1;
+ * the second launch adds the splits in ascending order, then with accumulate != 0 the previous value of out last.
+ * workspace: scf_channel_sum_workspace(M, C, n) floats. */
+int64_t scf_channel_sum_workspace(int M, int C, int64_t n);
+int scf_channel_sum(const float* g, int64_t g_stride, float* out, int accumulate, float* workspace,
+                    int64_t workspace_floats, int M, int C, int64_t n, scf_stream_t stream);
+
+/* Eval-mode BatchNorm folded into the convolution in front: y = W' * x + b' with sd = sqrt(var + eps), s = gamma / sd
+ * (one rounding each), W'[c] = s[c] W[c], b' = fma(s, b - mean, beta).  W, Wf (Cout, K) rows of K = Cin KH KW floats. */
+int scf_bn_fold(const float* W, const float* b, const float* gamma, const float* beta, const float* mean, const float* var,
+                float eps, float* Wf, float* bf, int Cout, int64_t K, scf_stream_t stream);
+
+/* From the folded layer's gradients (dWf, dbf): dW = s dWf, db = s dbf, dbeta = dbf,
+ * dgamma[c] = fma(b - mean, dbf, <W_c, dWf_c>) / sd.  <W_c, dWf_c> (= sum g (W * x)): lane l of the channel's wave runs one
+ * fma chain from +0 over k = l, l + 64, ... (k the torch order of a row), then v[l] += v[l + j] for j = 32, 16, ..., 1.
+ * accumulate != 0: the previous value of each of the four is added last.  The running statistics get no gradient.
+ * A channel reads and writes its own rows only.  dW must not alias dWf. */
+int scf_bn_unfold(const float* W, const float* b, const float* gamma, const float* mean, const float* var, float eps,
+                  const float* dWf, const float* dbf, float* dW, float* db, float* dgamma, float* dbeta, int accumulate,
+                  int Cout, int64_t K, scf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Gate arithmetic of the ConvGRU backward (raft_decoder.py:168-253; gru_grad.hip), between the convolution gradients
  * above.  One pass of the forward: z = sigmoid(conv_z([h|x])), r = sigmoid(conv_r([h|x])), q = tanh(conv_q([r h|x])),
  * h' = (1 - z) h + z q.  With g = d loss / d h':  u_q = g z (1 - q^2), u_z = g (q - h) z (1 - z), [g_rh | g_x] =

@@ -307,6 +307,19 @@ SIGNATURES = {
     'scf_conv_s1_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     'scf_conv_s1_wgrad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int,
                                     C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_conv_stem_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_conv_stem_wgrad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int,
+                                      C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_conv_ds_dgrad': (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, _fp, C.c_int64, C.c_int, _fp, C.c_int64, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_conv_ds_wgrad_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
+    'scf_conv_ds_wgrad': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int,
+                                    C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_channel_sum_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int64]),
+    'scf_channel_sum': (C.c_int, [_fp, C.c_int64, _fp, C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
+    'scf_bn_fold': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp, C.c_int, C.c_int64, _fp]),
+    'scf_bn_unfold': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int,
+                                C.c_int64, _fp]),
     'scf_gru_gate_grad_q': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,
                                       C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
     'scf_gru_gate_grad_r': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,

@@ -47,9 +47,11 @@ def _lib_error(msg):
 KEEP_LEVELS = ('none', 'pose_tail', 'pose_head', 'decoder_heads', 'gru', 'motion')
 _KEEP = {name: i for i, name in enumerate(KEEP_LEVELS)}
 # how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do; from 'head' on the chain is
-# SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  No backward yet: the
-# correlation build and the image and context encoders (they start from grads['motion']['correlation'],
-# grads['gru']['initial_hidden'] and grads['gru']['context']), and the path from iteration t into iteration t - 1 under
+# SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  Behind the last depth the
+# context encoder has RAFTEncoder.backward (from grads['gru']['initial_hidden'] and grads['gru']['context'];
+# SCFlowRefiner.loss_and_context_grads), its own switch and no depth of this ladder.  No backward yet: the correlation build
+# and the feature encoders behind it (they start from grads['motion']['correlation']), and the path from iteration t into
+# iteration t - 1 under
 # detach_flow=False or under mask_flow / mask_corr without detach_mask (SCFlowDecoder.check_backward refuses it at 'motion')
 _GRAD_DEPTHS = ('none', 'outputs', 'head') + KEEP_LEVELS[1:]
 
@@ -227,9 +229,10 @@ class _BasicBlock(HipModule):
                                              bn=self._bn(self.downsample[1]), eps=eps)
         return p
 
-    def forward(self, x: Tensor) -> Tensor:
+    def forward(self, x: Tensor, kept: Optional[list] = None) -> Tensor:
         """resnet.py:67-94.  BN (eval) is folded into the conv epilogue; IN needs the
-        whole plane, so it is its own kernel (residual add + ReLU fused there)."""
+        whole plane, so it is its own kernel (residual add + ReLU fused there).
+        ``kept``: a list that receives (the post-ReLU conv1 output, the block's output), the forward's own tensors."""
         p = self.packed
         # a block with a shortcut convolution hands both layers that read x to ops.conv2d_pair: on full grids the blocks of a
         # 3x3 / s2 conv1 compute the 1x1 / s2 shortcut from the patch they stage anyway (conv_dma.hip, shared-input form)
@@ -238,15 +241,19 @@ class _BasicBlock(HipModule):
                 y, idt = ops.conv2d_pair((p['c1'], x, dict(act=ACT_RELU)), (p['ds'], x))
             else:
                 y, idt = ops.conv2d(p['c1'], x, act=ACT_RELU), x
-            return ops.conv2d(p['c2'], y, res=idt, act=ACT_RELU)
-        if 'ds' in p:
-            y, idt = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
+            out = ops.conv2d(p['c2'], y, res=idt, act=ACT_RELU)
         else:
-            y, idt = ops.conv2d(p['c1'], x), x
-        ops.instance_norm(y, relu=True, out=y)
-        y2 = ops.conv2d(p['c2'], y)
-        # (the shortcut's own normalisation rides in the block's final pass)
-        return ops.instance_norm(y2, res=idt, relu=True, out=y2, res_norm='ds' in p)
+            if 'ds' in p:
+                y, idt = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
+            else:
+                y, idt = ops.conv2d(p['c1'], x), x
+            ops.instance_norm(y, relu=True, out=y)
+            y2 = ops.conv2d(p['c2'], y)
+            # (the shortcut's own normalisation rides in the block's final pass)
+            out = ops.instance_norm(y2, res=idt, relu=True, out=y2, res_norm='ds' in p)
+        if kept is not None:
+            kept.append((y, out))
+        return out
 
 
 @ENCODERS.register_module()
@@ -285,6 +292,22 @@ class RAFTEncoder(HipModule):
             self.res_layers.append(f'res_layer{i}')
             inplanes = planes
         self.conv2 = nn.Conv2d(128, out_channels, 1)
+        # under keeping() a forward leaves in ``kept`` what backward() reads: x (the input image), stem (the stem's output), per
+        # block i = 0 .. 5 t{i} (the post-ReLU conv1 output) and y{i} (the block's output), and out (the head's
+        # post-activation output).  The forward's own tensors; out is a copy when the caller owns its destination.  Its own
+        # switch, not a level of SCFlowDecoder.keep; a forward outside keeping() empties it
+        self.keep = False
+        self.kept = {}
+
+    @contextlib.contextmanager
+    def keeping(self):
+        """forwards inside the body leave their activations in ``kept`` (a setting of the caller's stays)"""
+        prev = self.keep
+        self.keep = True
+        try:
+            yield self
+        finally:
+            self.keep = prev
 
     def _pack(self):
         n1 = getattr(self, self.tag + '1')
@@ -298,16 +321,149 @@ class RAFTEncoder(HipModule):
         """raft_encoder.py:286-314.  ``out`` / ``head_*`` let the caller have the 1x1 head
         write (with a split tanh/relu epilogue) straight into a slice of a larger buffer."""
         p = self.packed
+        blocks = [] if self.keep else None
+        image = x
         if self.kind == 'BN':
             x = ops.conv2d(p['stem'], x, act=ACT_RELU)
         else:
             x = ops.conv2d(p['stem'], x)
             ops.instance_norm(x, relu=True, out=x)
+        stem = x
         for name in self.res_layers:
             for blk in getattr(self, name):
-                x = blk(x)
-        return ops.conv2d(p['head'], x, out=out, act=head_act, act2=head_act2,
-                          act_split=head_split)
+                x = blk(x, blocks)
+        y = ops.conv2d(p['head'], x, out=out, act=head_act, act2=head_act2,
+                       act_split=head_split)
+        self.kept = {} if blocks is None else self._kept_dict(image, stem, blocks, y, out is not None)
+        return y
+
+    @staticmethod
+    def _kept_dict(image: Tensor, stem: Tensor, blocks, y: Tensor, clone_out: bool) -> dict:
+        kept = dict(x=image, stem=stem, out=y.clone() if clone_out else y)
+        for i, (t, o) in enumerate(blocks):
+            kept[f't{i}'], kept[f'y{i}'] = t, o
+        return kept
+
+    def backward(self, saved: dict, g_out: Union[Tensor, Sequence[Tensor]], out: Optional[Tensor] = None,
+                 head_act: int = ACT_NONE, head_act2: int = ACT_NONE, head_split: int = 0,
+                 param_grads: Optional[dict] = None, intermediates: Optional[dict] = None, prefix: str = ''):
+        """Backward of the BatchNorm (eval statistics) encoder with respect to its parameters: the reference's context
+        encoder under ``freeze_bn=True``.  The input image gets no gradient.
+
+        ``saved``: ``kept`` of a forward under ``keeping()`` (x, stem, t0 .. t5, y0 .. y5, out).  ``g_out``: the cotangent
+        at the head's post-activation output (N, out_channels, h, w), or its channel slices in order (with the refiner's
+        split head: d loss / d h0, d loss / d context).  ``out``: the head's post-activation output where ``saved`` does
+        not hold it (``SCFlowDecoder.kept`` has h0 and c from keep level 'gru' on); ``head_*`` as the forward was called.
+        -> the gradients of the parameters summed over the samples, keyed as ``named_parameters()`` behind ``prefix`` (62
+        entries).  A ``param_grads`` passed in is accumulated into (entries it lacks are created; some but not all: an
+        error).
+
+        Chain: act_grad on the head's output; wgrad + dgrad (ReLU mask of y5 in the epilogue) of the 1x1 head; then per
+        block in reverse, with G the cotangent at the block's pre-ReLU sum: conv2's wgrad (G, t) and dgrad with the mask
+        of t -> G_t; a stride-1 conv1: wgrad (G_t, x) and ``conv_s1_dgrad(G_t, W1', add=G, a=x, act=RELU)``; a stride-2
+        conv1: ``conv_wgrad`` + ``channel_sum`` (the bias), ``conv_dgrad``, the shortcut's ``conv_ds_wgrad`` (G, x) and the
+        join ``conv_ds_dgrad`` that adds both input gradients under the mask of x; last the stem's ``conv_stem_wgrad``.
+        Every BatchNorm layer's dgrad reads the folded weight (``bn_fold``), and its (dW', db') go through ``bn_unfold``.
+
+        ``intermediates``: a dict that receives every launch's operands and results (None: nothing is kept)."""
+        what = 'RAFTEncoder.backward'
+        if self.kind != 'BN':
+            raise NotImplementedError(f'{what}: the InstanceNorm feature encoder has no backward yet; it waits for the '
+                                      'correlation-build backward, which gives the cotangents at its outputs')
+        if self.stem_stride != 2:
+            raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
+        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
+        nb = len(blocks)
+        keys = ['x', 'stem'] + [f'{k}{i}' for i in range(nb) for k in 'ty'] + ([] if out is not None else ['out'])
+        try:
+            got = {k: saved[k] for k in keys}
+        except (KeyError, TypeError):
+            raise _lib_error(f"{what}: saved holds {', '.join(keys)}: RAFTEncoder.kept after a forward under "
+                             'keeping()') from None
+        if out is None:
+            out = got['out']
+        image, y_last = got['x'], got[f'y{nb - 1}']
+        n, co = y_last.shape[0], self.out_channels
+        shape = (n, co) + tuple(y_last.shape[2:])
+        if tuple(out.shape) != shape:
+            raise _lib_error(f'{what}: out must be {shape}, got {tuple(out.shape)}')
+        split = int(head_split)
+        if not 0 <= split < co:
+            raise _lib_error(f'{what}: head_split {split} outside [0, {co})')
+        parts = [(0, co, head_act)] if split == 0 else [(0, split, head_act), (split, co, head_act2)]
+        gs = [g_out] if isinstance(g_out, torch.Tensor) else list(g_out)
+        if len(gs) == 1:
+            if tuple(gs[0].shape) != shape:
+                raise _lib_error(f'{what}: g_out must be {shape}, got {tuple(gs[0].shape)}')
+            gs = [gs[0][:, a:b] for a, b, _ in parts]
+        elif len(gs) != len(parts) or any(tuple(g.shape) != (n, b - a) + shape[2:] for g, (a, b, _) in zip(gs, parts)):
+            raise _lib_error(f'{what}: g_out is one {shape} tensor or its {len(parts)} channel slices '
+                             f'{[(n, b - a) + shape[2:] for a, b, _ in parts]}, got {[tuple(g.shape) for g in gs]}')
+        names = [prefix + k for k, _ in self.named_parameters()]
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
+        dst = dict(zip(names, dst))
+        rec = {} if intermediates is None else intermediates
+
+        def folded(key, conv, bn):
+            wf, bf = ops.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+            rec[key] = dict(wf=wf, bf=bf)
+            return wf
+
+        def unfold(key, ckey, bkey, conv, bn, dwf, dbf):
+            ks = [f'{prefix}{ckey}.weight', f'{prefix}{ckey}.bias', f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
+            res = ops.bn_unfold(conv.weight, conv.bias, bn.weight, bn.running_mean, bn.running_var, bn.eps, dwf, dbf,
+                                out=[dst[k] for k in ks], accumulate=acc)
+            grads.update(zip(ks, res))
+            rec[key].update(dwf=dwf, dbf=dbf)
+
+        # ---- head: 1x1, no norm
+        u = torch.empty(shape, dtype=torch.float32, device=out.device)
+        for g, (a, b, act) in zip(gs, parts):
+            ops.act_grad(g, None if act == ACT_NONE else out[:, a:b], act, out=u[:, a:b])
+        kw, kb = f'{prefix}conv2.weight', f'{prefix}conv2.bias'
+        grads[kw], grads[kb] = ops.conv_s1_wgrad(u, y_last, (1, 1), dw=dst[kw], db=dst[kb], accumulate=acc)
+        G = ops.conv_s1_dgrad(u, self.conv2.weight, a=y_last, act=ACT_RELU)
+        rec['head'] = dict(g=u, x=y_last, gx=G)
+        # ---- blocks, last to first
+        i = nb
+        for name in reversed(self.res_layers):
+            layer = getattr(self, name)
+            for j in reversed(range(len(layer))):
+                i -= 1
+                blk, key = layer[j], f'{name}.{j}'
+                x_in, t = (got[f'y{i - 1}'] if i else got['stem']), got[f't{i}']
+                bn1, bn2 = getattr(blk, blk.tag + '1'), getattr(blk, blk.tag + '2')
+                w2 = folded(f'{key}.conv2', blk.conv2, bn2)
+                dwf, dbf = ops.conv_s1_wgrad(G, t, (3, 3))
+                g_t = ops.conv_s1_dgrad(G, w2, a=t, act=ACT_RELU)
+                unfold(f'{key}.conv2', f'{key}.conv2', f'{key}.{blk.tag}2', blk.conv2, bn2, dwf, dbf)
+                rec[f'{key}.conv2'].update(g=G, x=t, gx=g_t)
+                w1 = folded(f'{key}.conv1', blk.conv1, bn1)
+                if blk.downsample is None:
+                    dwf, dbf = ops.conv_s1_wgrad(g_t, x_in, (3, 3))
+                    g_prev = ops.conv_s1_dgrad(g_t, w1, add=G, a=x_in, act=ACT_RELU)
+                    unfold(f'{key}.conv1', f'{key}.conv1', f'{key}.{blk.tag}1', blk.conv1, bn1, dwf, dbf)
+                    rec[f'{key}.conv1'].update(g=g_t, x=x_in, add=G, gx=g_prev)
+                else:
+                    in_hw = tuple(x_in.shape[2:])
+                    dwf, dbf = ops.conv_wgrad(g_t, x_in), ops.channel_sum(g_t)
+                    gx1 = ops.conv_dgrad(g_t, w1, in_hw)
+                    unfold(f'{key}.conv1', f'{key}.conv1', f'{key}.{blk.tag}1', blk.conv1, bn1, dwf, dbf)
+                    rec[f'{key}.conv1'].update(g=g_t, x=x_in, gx=gx1)
+                    ds, dsn = blk.downsample
+                    wd = folded(f'{key}.downsample', ds, dsn)
+                    dwf, dbf = ops.conv_ds_wgrad(G, x_in)
+                    g_prev = ops.conv_ds_dgrad(G, wd, in_hw, add=gx1, a=x_in, act=ACT_RELU)
+                    unfold(f'{key}.downsample', f'{key}.downsample.0', f'{key}.downsample.1', ds, dsn, dwf, dbf)
+                    rec[f'{key}.downsample'].update(g=G, x=x_in, add=gx1, gx=g_prev)
+                G = g_prev
+        # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
+        n1 = getattr(self, self.tag + '1')
+        rec['conv1'] = {}
+        dwf, dbf = ops.conv_stem_wgrad(G, image)
+        unfold('conv1', 'conv1', self.tag + '1', self.conv1, n1, dwf, dbf)
+        rec['conv1'].update(g=G, x=image)
+        return grads
 
 
 def encoder_pair_supported(fe: 'RAFTEncoder', ce: 'RAFTEncoder') -> bool:
@@ -326,6 +482,7 @@ def raft_encoder_pair(fe: 'RAFTEncoder', xf: Tensor, ce: 'RAFTEncoder', xc: Tens
     if not encoder_pair_supported(fe, ce):
         raise ValueError('raft_encoder_pair: (InstanceNorm feature encoder, BatchNorm context encoder) of one layer geometry')
     pf, pc = fe.packed, ce.packed
+    fe.kept, ce.kept = {}, {}                  # this walk keeps nothing (SCFlowRefiner.extract_feat: not taken while keeping)
     yf, yc = ops.conv2d_pair((pf['stem'], xf), (pc['stem'], xc, dict(act=ACT_RELU)))
     ops.instance_norm(yf, relu=True, out=yf)
     for name in fe.res_layers:

@@ -2401,6 +2401,197 @@ def conv_s1_wgrad(g: Tensor, x: Tensor, kernel_size, dw: Optional[Tensor] = None
     return dw, db
 
 
+# ------------------------------------------------- backward of the context encoder's remaining layers (encoder_grad.hip)
+def _half_map(what: str, g: Tensor, x_shape) -> None:
+    m, _, ho, wo = g.shape
+    xm, _, hin, win = x_shape
+    if xm != m or m * hin * win == 0 or ho != (hin - 1) // 2 + 1 or wo != (win - 1) // 2 + 1:
+        raise _lib.ScflowHipError(f'{what}: a {tuple(x_shape)} input does not give the map of g {tuple(g.shape)}')
+
+
+def _grad_workspace(what: str, workspace: Optional[Tensor], need: int, like: Tensor) -> Tensor:
+    if need < 0:
+        raise _lib.ScflowHipError(f'{what}: invalid sizes')
+    if workspace is None:
+        workspace = torch.empty((need,), dtype=torch.float32, device=like.device)
+    _dev(workspace, f'{what}: workspace')
+    if not workspace.is_contiguous() or workspace.numel() < need:
+        raise _lib.ScflowHipError(f'{what}: workspace must be contiguous with at least {need} floats, got {workspace.numel()}')
+    return workspace
+
+
+def conv_stem_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
+    """floats of workspace ``conv_stem_wgrad`` needs (``scf_conv_stem_wgrad_workspace``)."""
+    n = int(_lib.load().scf_conv_stem_wgrad_workspace(m, cout, cin, ho, wo))
+    if n < 0:
+        raise _lib.ScflowHipError(f'conv_stem_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
+    return n
+
+
+def conv_stem_wgrad(g: Tensor, x: Tensor, dw: Optional[Tensor] = None, db: Optional[Tensor] = None, bias: bool = True,
+                    accumulate: bool = False, workspace: Optional[Tensor] = None, kernel_size: int = 7, stride: int = 2,
+                    padding: int = 3):
+    """Weight and bias gradient of the encoder stem ``F.conv2d(x, weight, bias, stride=2, padding=3)`` with a 7x7 kernel and
+    at most 4 input channels (``scf_conv_stem_wgrad``): ``g`` (M, Cout, Ho, Wo), ``x`` (M, Cin, Hin, Win), both contiguous up
+    to a channel slice -> (dw (Cout, Cin, 7, 7), db (Cout,) or None with ``bias=False``); ``accumulate``: added to them."""
+    what = 'conv_stem_wgrad'
+    pg, gs = _s1_map(g, what, 'g')
+    px, xs = _s1_map(x, what, 'x')
+    if (kernel_size, stride, padding) != (7, 2, 3):
+        raise _lib.ScflowHipError(f'{what}: 7x7 / stride 2 / padding 3 only, got {kernel_size} / {stride} / {padding}')
+    _half_map(what, g, tuple(x.shape))
+    m, cout, ho, wo = g.shape
+    cin, hin, win = x.shape[1:]
+    if not 1 <= cin <= 4 or cout < 1:
+        raise _lib.ScflowHipError(f'{what}: 1 .. 4 input channels, got {cin}')
+    dw = _fc_grad_out(dw, (cout, cin, 7, 7), g, what, 'dw', accumulate)
+    if bias or db is not None:
+        db = _fc_grad_out(db, (cout,), g, what, 'db', accumulate)
+    workspace = _grad_workspace(what, workspace, conv_stem_wgrad_workspace(m, cout, cin, ho, wo), g)
+    _lib.check(_lib.load().scf_conv_stem_wgrad(pg, gs, px, xs, dw.data_ptr(), None if db is None else db.data_ptr(),
+                                               int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m, cout, cin,
+                                               ho, wo, hin, win, 7, 7, 2, 3, _stream()), 'scf_conv_stem_wgrad')
+    return dw, db
+
+
+def conv_ds_dgrad(g: Tensor, weight: Tensor, in_hw: Tuple[int, int], add: Optional[Tensor] = None,
+                  a: Optional[Tensor] = None, act: int = ACT_NONE, out: Optional[Tensor] = None) -> Tensor:
+    """The join at the input of a down-sampling block (``scf_conv_ds_dgrad``): ``act'(a) * (add + dgrad)`` with ``dgrad`` the
+    input gradient of the 1x1 / stride-2 shortcut ``F.conv2d(x, weight, stride=2)``, non-zero at the even pixels only.
+    ``g`` (M, Cout, Ho, Wo); ``weight`` (Cout, Cin, 1, 1) or (Cout, Cin); ``add`` (the 3x3 / stride-2 layer's input
+    gradient), ``a``, ``out`` (M, Cin, Hin, Win) with (Hin, Win) = ``in_hw``; all maps contiguous up to a channel slice."""
+    what = 'conv_ds_dgrad'
+    _dev(weight, f'{what}: weight')
+    if not weight.is_contiguous() or weight.dim() not in (2, 4) or tuple(weight.shape[2:]) not in ((), (1, 1)):
+        raise _lib.ScflowHipError(f'{what}: weight must be a contiguous (Cout, Cin, 1, 1) tensor, got {tuple(weight.shape)}')
+    cout, cin = weight.shape[:2]
+    _s1_act(what, act, a)
+    pg, gs = _s1_map(g, what, 'g')
+    m, gc = g.shape[:2]
+    hin, win = in_hw
+    if gc != cout or cin < 1:
+        raise _lib.ScflowHipError(f'{what}: g must be (M, {cout}, Ho, Wo), got {tuple(g.shape)}')
+    shape = (m, cin, hin, win)
+    _half_map(what, g, shape)
+    padd, sadd = (None, 0) if add is None else _s1_map(add, what, 'add', shape)
+    pa, sa = (None, 0) if a is None else _s1_map(a, what, 'a', shape)
+    if out is None:
+        out = torch.empty(shape, dtype=torch.float32, device=g.device)
+    po, so = _s1_map(out, what, 'out', shape)
+    _lib.check(_lib.load().scf_conv_ds_dgrad(pg, gs, weight.data_ptr(), padd, sadd, pa, sa, act, po, so, m, cout, cin,
+                                             g.shape[2], g.shape[3], hin, win, _stream()), 'scf_conv_ds_dgrad')
+    return out
+
+
+def conv_ds_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
+    """floats of workspace ``conv_ds_wgrad`` needs (``scf_conv_ds_wgrad_workspace``)."""
+    n = int(_lib.load().scf_conv_ds_wgrad_workspace(m, cout, cin, ho, wo))
+    if n < 0:
+        raise _lib.ScflowHipError(f'conv_ds_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
+    return n
+
+
+def conv_ds_wgrad(g: Tensor, x: Tensor, dw: Optional[Tensor] = None, db: Optional[Tensor] = None, bias: bool = True,
+                  accumulate: bool = False, workspace: Optional[Tensor] = None):
+    """Weight and bias gradient of the 1x1 / stride-2 shortcut ``F.conv2d(x, weight, bias, stride=2)``
+    (``scf_conv_ds_wgrad``): ``g`` (M, Cout, Ho, Wo), ``x`` (M, Cin, Hin, Win), both contiguous up to a channel slice ->
+    (dw (Cout, Cin, 1, 1), db (Cout,) or None with ``bias=False``); ``accumulate``: added to them."""
+    what = 'conv_ds_wgrad'
+    pg, gs = _s1_map(g, what, 'g')
+    px, xs = _s1_map(x, what, 'x')
+    _half_map(what, g, tuple(x.shape))
+    m, cout, ho, wo = g.shape
+    cin, hin, win = x.shape[1:]
+    if cin < 1 or cout < 1:
+        raise _lib.ScflowHipError(f'{what}: empty channels {tuple(g.shape)}, {tuple(x.shape)}')
+    dw = _fc_grad_out(dw, (cout, cin, 1, 1), g, what, 'dw', accumulate)
+    if bias or db is not None:
+        db = _fc_grad_out(db, (cout,), g, what, 'db', accumulate)
+    workspace = _grad_workspace(what, workspace, conv_ds_wgrad_workspace(m, cout, cin, ho, wo), g)
+    _lib.check(_lib.load().scf_conv_ds_wgrad(pg, gs, px, xs, dw.data_ptr(), None if db is None else db.data_ptr(),
+                                             int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m, cout, cin,
+                                             ho, wo, hin, win, _stream()), 'scf_conv_ds_wgrad')
+    return dw, db
+
+
+def channel_sum_workspace(m: int, c: int, n: int) -> int:
+    """floats of workspace ``channel_sum`` needs (``scf_channel_sum_workspace``)."""
+    k = int(_lib.load().scf_channel_sum_workspace(m, c, n))
+    if k < 0:
+        raise _lib.ScflowHipError(f'channel_sum_workspace: invalid sizes {(m, c, n)}')
+    return k
+
+
+def channel_sum(g: Tensor, out: Optional[Tensor] = None, accumulate: bool = False,
+                workspace: Optional[Tensor] = None) -> Tensor:
+    """``g.sum((0, 2, 3))`` in one fixed order (``scf_channel_sum``): the bias gradient of a layer whose weight gradient has
+    none.  ``g`` (M, C, H, W), contiguous up to a channel slice -> (C,); ``accumulate``: added to ``out``."""
+    what = 'channel_sum'
+    pg, gs = _s1_map(g, what, 'g')
+    m, c, h, w = g.shape
+    if m * c * h * w == 0:
+        raise _lib.ScflowHipError(f'{what}: empty tensor {tuple(g.shape)}')
+    out = _fc_grad_out(out, (c,), g, what, 'out', accumulate)
+    workspace = _grad_workspace(what, workspace, channel_sum_workspace(m, c, h * w), g)
+    _lib.check(_lib.load().scf_channel_sum(pg, gs, out.data_ptr(), int(bool(accumulate)), workspace.data_ptr(),
+                                           workspace.numel(), m, c, h * w, _stream()), 'scf_channel_sum')
+    return out
+
+
+def _bn_vectors(what: str, cout: int, **named) -> list:
+    ptrs = []
+    for name, t in named.items():
+        ptrs.append(_dense(t, f'{what}: {name}'))
+        if tuple(t.shape) != (cout,):
+            raise _lib.ScflowHipError(f'{what}: {name} must be ({cout},), got {tuple(t.shape)}')
+    return ptrs
+
+
+def _bn_weight(what: str, weight: Tensor, name: str = 'weight', shape=None) -> Tuple[int, int]:
+    _dev(weight, f'{what}: {name}')
+    if weight.dim() < 2 or not weight.is_contiguous() or weight.numel() == 0 or (
+            shape is not None and tuple(weight.shape) != tuple(shape)):
+        raise _lib.ScflowHipError(f'{what}: {name} must be a contiguous (Cout, ...) tensor'
+                                  f'{"" if shape is None else " of shape " + str(tuple(shape))}, got {tuple(weight.shape)}')
+    return weight.shape[0], weight.numel() // weight.shape[0]
+
+
+def bn_fold(weight: Tensor, bias: Tensor, gamma: Tensor, beta: Tensor, mean: Tensor, var: Tensor, eps: float,
+            out: Optional[Tuple[Tensor, Tensor]] = None) -> Tuple[Tensor, Tensor]:
+    """Eval-mode BatchNorm folded into the convolution in front (``scf_bn_fold``): (W', b') of ``y = W' * x + b'`` with
+    ``s = gamma / sqrt(var + eps)``, ``W' = s W``, ``b' = beta + s (b - mean)``, in the raw torch layout."""
+    what = 'bn_fold'
+    cout, k = _bn_weight(what, weight)
+    ptrs = _bn_vectors(what, cout, bias=bias, gamma=gamma, beta=beta, mean=mean, var=var)
+    wf, bf = (None, None) if out is None else out
+    wf = _fc_grad_out(wf, tuple(weight.shape), weight, what, 'out[0]')
+    bf = _fc_grad_out(bf, (cout,), weight, what, 'out[1]')
+    _lib.check(_lib.load().scf_bn_fold(weight.data_ptr(), *ptrs, float(eps), wf.data_ptr(), bf.data_ptr(), cout, k,
+                                       _stream()), 'scf_bn_fold')
+    return wf, bf
+
+
+def bn_unfold(weight: Tensor, bias: Tensor, gamma: Tensor, mean: Tensor, var: Tensor, eps: float, dwf: Tensor, dbf: Tensor,
+              out: Optional[Sequence[Optional[Tensor]]] = None, accumulate: bool = False):
+    """The folded layer's gradients (``dwf``, ``dbf``) carried to the raw parameters (``scf_bn_unfold``) ->
+    (d conv.weight, d conv.bias, d bn.weight, d bn.bias); ``out``: the four destinations, ``accumulate``: added to them."""
+    what = 'bn_unfold'
+    cout, k = _bn_weight(what, weight)
+    _bn_weight(what, dwf, 'dwf', tuple(weight.shape))
+    pb, pg, pm, pv, pdb = _bn_vectors(what, cout, bias=bias, gamma=gamma, mean=mean, var=var, dbf=dbf)
+    outs = (None,) * 4 if out is None else tuple(out)
+    if len(outs) != 4:
+        raise _lib.ScflowHipError(f'{what}: out holds the four destinations (dw, db, dgamma, dbeta)')
+    dw = _fc_grad_out(outs[0], tuple(weight.shape), weight, what, 'out[0]', accumulate)
+    vec = [_fc_grad_out(o, (cout,), weight, what, f'out[{i + 1}]', accumulate) for i, o in enumerate(outs[1:])]
+    if dw.data_ptr() == dwf.data_ptr():
+        raise _lib.ScflowHipError(f'{what}: out[0] must not alias dwf')
+    _lib.check(_lib.load().scf_bn_unfold(weight.data_ptr(), pb, pg, pm, pv, float(eps), dwf.data_ptr(), pdb, dw.data_ptr(),
+                                         *(v.data_ptr() for v in vec), int(bool(accumulate)), cout, k, _stream()),
+               'scf_bn_unfold')
+    return (dw, *vec)
+
+
 # ------------------------------------------------- gate arithmetic of the ConvGRU backward (gru_grad.hip)
 def _gg_rows(what: str, shape, named) -> list:
     """(pointer, sample stride) of every (M, C, H, W) operand of a gate kernel; None stays (None, 0)."""

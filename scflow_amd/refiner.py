@@ -9,8 +9,9 @@ keys.  PnP re-mapping is outside the hot path, and
 ``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).  The loss
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
 ``loss()`` returns the forward VALUES the reference trains against, ``loss_and_grads()`` adds their gradients at
-the network's outputs and the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) -- the
-encoders have no backward and there is no ``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
+the network's outputs, the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) and
+``loss_and_context_grads()`` through the context encoder -- the feature encoders and the correlation build have no backward
+and there is no ``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
@@ -288,10 +289,13 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         # materialised here, on the main stream, before the fork event (a copy enqueued after it
         # would not be ordered before the side branch's first read)
         rend = render_images.contiguous()
-        ov_ctx = small_work(n, H, W, 'context')
+        # a context encoder that keeps its activations for backward() runs its own forward, on this stream: the paired walk
+        # below keeps nothing (same kernels per layer, same bits), and what it keeps is read on this stream afterwards
+        keeping = self.context.keep
+        ov_ctx = small_work(n, H, W, 'context') and not keeping
         fork = ops.fork_point() if ov_ctx else None     # the context encoder may start from here
-        if (not self.seperate_encoder and ops.branch_mode(n, H, W, 'context') == 2 and ops._CONV_EVENTS is None
-                and encoder_pair_supported(self.render_encoder, self.context)):
+        if (not self.seperate_encoder and not keeping and ops.branch_mode(n, H, W, 'context') == 2
+                and ops._CONV_EVENTS is None and encoder_pair_supported(self.render_encoder, self.context)):
             # r6: the context encoder's launches ride in the feature encoder's (modules.raft_encoder_pair; IN | BN encoders)
             both = torch.empty((2 * n, 3, H, W), dtype=torch.float32, device=dev)
             ops.copy_channels(rend, both[:n])
@@ -435,6 +439,25 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         through the mask, a reverse scan over whole iterations: NotImplementedError (``SCFlowDecoder.check_backward``)."""
         return self._loss(data_batch, data, 'motion')
 
+    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_motion_grads()`` (its keys, values and bits, and its refusals) with the context encoder behind it
+        (``RAFTEncoder.backward`` from ``gru['initial_hidden']`` and ``gru['context']``, complete only at that rung):
+        ``params`` is extended by the 62 ``context.*`` gradients, BatchNorm with running statistics as the forward
+        computes it (the reference's ``freeze_bn=True``).  Every parameter of the network except the feature encoder's
+        now has a gradient: the reference's ``freeze_encoder=True`` training case.  The context encoder keeps its
+        activations during this forward (``RAFTEncoder.keeping``) and drops them before returning."""
+        ctx = self.context
+        try:
+            with ctx.keeping():
+                out = self._loss(data_batch, data, 'motion')
+            grads = out[-1]
+            grads['params'].update(ctx.backward(
+                ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
+                head_act2=ACT_RELU, head_split=self.h_channels, prefix='context.'))
+        finally:
+            ctx.kept = {}
+        return out
+
     def _loss(self, data_batch, data, depth):
         from . import losses as L
         at = _GRAD_DEPTHS.index
@@ -498,7 +521,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
                                       'loss_and_pose_head_grads() through the pose head\'s convolutions to hv and dm, '
                                       'loss_and_decoder_head_grads() through the XHeads and the delta-flow / mask encoders to hv, '
                                       'loss_and_gru_grads() through the GRU to h0, the context and the motion features, '
-                                      'loss_and_motion_grads() through the motion encoder and the lookup to the correlation volume')
+                                      'loss_and_motion_grads() through the motion encoder and the lookup to the correlation volume, '
+                                      'loss_and_context_grads() through the context encoder to its 62 parameters')
         if self.test_cfg.get('cycles', 1) > 1:
             # base_refiner.py:250-258: every further cycle RE-RENDERS the object at the updated pose (update_data).
             # Without an attached renderer, refuse instead of silently running one cycle.
