@@ -1171,6 +1171,46 @@ int scf_mul_mask(const float* x, int64_t x_nstride, const float* mask, float* ou
 int scf_copy_strided(const float* src, int64_t src_nstride, float* dst, int64_t dst_nstride,
                      int N, int64_t count, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Optimizer step (optim.hip): gradient-norm clipping and AdamW over a LIST of tensors in at most three launches.
+ * replaces torch.nn.utils.clip_grad_norm_ + torch.optim.AdamW(amsgrad=False) as the reference's runner applies them
+ * (configs/refine_models/scflow.py: optimizer, optimizer_config.grad_clip).
+ * Added without a version bump (SCF_VERSION stays at .3): the presence of scf_adamw_step marks the feature.
+ *
+ * The tensors are cut into chunks of SCF_ADAMW_CHUNK elements, a tensor's last chunk ragged; one block of
+ * SCF_ADAMW_NORM_THREADS threads owns one chunk.  scf_adamw_chunks is a HOST function: it writes the table for tensors of
+ * sizes[0..ntensors) elements to out[0..capacity) (host memory) and returns the number of chunks; out = NULL only
+ * counts.  Empty tensors get no chunk.  The caller uploads the table once.
+ *
+ * p, g, m, v are DEVICE arrays of ntensors device pointers (parameter, gradient, first and second moment; fp32, each
+ * tensor contiguous, any 4-byte alignment).  The chunk table is trusted: it must come from scf_adamw_chunks over the
+ * sizes of exactly these tensors.
+ *
+ * scf_grad_sqnorm: partial[b] = sum of g^2 over chunk b, then *norm = sqrt(sum_b partial[b]); both sums in a fixed
+ * order without atomics (bitwise reproducible for the same pointers; the order depends on the chunking and on each
+ * gradient's address modulo 16).  fp32 accumulation.  partial: nchunks floats of scratch.  Two launches.
+ *
+ * scf_adamw_step: with c = min(max_norm / (*norm + 1e-6), 1) (c = 1 when norm is NULL; a NaN norm gives c = NaN), per
+ * element, in fp32 and in torch's operation order:
+ *   g' = c g;  p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = beta2 v + (1 - beta2) g'^2;
+ *   p -= (lr / bias_correction1) * (m / (sqrt(v) / sqrt(bias_correction2) + eps))
+ * g is not modified.  lr, the step count and both bias corrections (1 - beta^t) are the caller's, in double; the
+ * entry rounds the derived factors to fp32 once.  One launch.  Nothing here synchronises: norm is read on the device. */
+#define SCF_ADAMW_CHUNK 4096
+#define SCF_ADAMW_NORM_THREADS 256
+typedef struct scf_adamw_chunk {
+  int32_t tensor;   /* index into p / g / m / v */
+  int32_t length;   /* 1 .. SCF_ADAMW_CHUNK elements */
+  int64_t offset;   /* first element, a multiple of SCF_ADAMW_CHUNK */
+} scf_adamw_chunk;
+int64_t scf_adamw_chunks(const int64_t* sizes, int ntensors, scf_adamw_chunk* out, int64_t capacity);
+int scf_grad_sqnorm(const scf_adamw_chunk* chunks, int64_t nchunks, const float* const* g, float* partial,
+                    float* norm, scf_stream_t stream);
+int scf_adamw_step(const scf_adamw_chunk* chunks, int64_t nchunks, float* const* p, const float* const* g,
+                   float* const* m, float* const* v, const float* norm, double max_norm, double lr,
+                   double weight_decay, double beta1, double beta2, double eps, double bias_correction1,
+                   double bias_correction2, scf_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -25,3 +25,4 @@ from .weights import fill_state_dict  # noqa: F401
 from .synthetic import make_inputs  # noqa: F401
 from .mesh import Fragments, Mesh, MeshRenderer, MeshStore, make_mesh, read_ply  # noqa: F401
 from .patches import PatchPipeline, TrainPatchPipeline  # noqa: F401
+from .optim import AdamW, OneCycle, build_optimizer  # noqa: F401

@@ -134,6 +134,11 @@ class PatchAugParams(C.Structure):
                 ('fix_error_swap_quirk', C.c_int32), ('mask_pad_val', C.c_int32)]
 
 
+class AdamwChunk(C.Structure):
+    """mirror of ``scf_adamw_chunk`` (include/scflow_hip.h)."""
+    _fields_ = [('tensor', C.c_int32), ('length', C.c_int32), ('offset', C.c_int64)]
+
+
 class IterGN(C.Structure):
     """mirror of ``scf_iter_gn``."""
     _fields_ = [('gamma', _fp), ('beta', _fp), ('out', _fp),
@@ -333,6 +338,10 @@ SIGNATURES = {
     'scf_avgpool2x2': (C.c_int, [_fp, _fp, C.c_int64, C.c_int, C.c_int, _fp]),
     'scf_mul_mask': (C.c_int, [_fp, C.c_int64, _fp, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_copy_strided': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int64, _fp]),
+    'scf_adamw_chunks': (C.c_int64, [C.POINTER(C.c_int64), C.c_int, C.POINTER(AdamwChunk), C.c_int64]),
+    'scf_grad_sqnorm': (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp]),
+    'scf_adamw_step': (C.c_int, [_fp, C.c_int64, _fp, _fp, _fp, _fp, _fp, C.c_double, C.c_double, C.c_double, C.c_double,
+                                 C.c_double, C.c_double, C.c_double, C.c_double, _fp]),
 }
 
 _lib = None

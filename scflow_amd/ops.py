@@ -31,6 +31,7 @@ __all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scfl
            'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
            'unproject_depth', 'linear_pair', 'resize_bilinear', 'resize_bilinear_grad', 'reproject_flow_grad', 'pose_update_grad', 'convex_upsample', 'avgpool2x2', 'copy_channels',
            'fc_operand', 'fc_dgrad', 'fc_wgrad', 'pose_select_grad', 'group_norm_flat_grad',
+           'ADAMW_CHUNK', 'ADAMW_NORM_THREADS', 'adamw_chunk_table', 'adamw_chunk_rows', 'AdamwChunks', 'grad_sqnorm', 'adamw_step',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_TANH', 'CONV_PLAIN', 'CONV_GRU_ZR',
            'CONV_GRU_Q']
 
@@ -2663,3 +2664,92 @@ def gru_gate_state(h: Tensor, gate: Tensor, q: Optional[Tensor] = None, out: Opt
     args = _gg_rows(what, shape, (('h', h), ('gate', gate), ('q', q), ('out', out)))
     _lib.check(_lib.load().scf_gru_gate_state(*args, m, n, _stream()), 'scf_gru_gate_state')
     return out
+
+
+# ----------------------------------------------------------------------------------------------------- optimizer step
+ADAMW_CHUNK = 4096            # SCF_ADAMW_CHUNK of include/scflow_hip.h: elements per block of the multi-tensor kernels
+ADAMW_NORM_THREADS = 256      # SCF_ADAMW_NORM_THREADS: the block size the norm's summation depth is counted from
+
+
+def adamw_chunk_table(sizes: Sequence[int]) -> Tensor:
+    """``scf_adamw_chunks`` (a host function): the chunk table of tensors with ``sizes`` elements as a CPU int64 tensor
+    (nchunks, 2) with the bytes of ``scf_adamw_chunk``: word 0 = tensor index | length << 32, word 1 = offset
+    (``adamw_chunk_rows`` decodes it).  Upload it once and hand it to ``grad_sqnorm`` / ``adamw_step``."""
+    lib = _lib.load()
+    sizes = [int(s) for s in sizes]
+    if any(s < 0 for s in sizes):
+        raise ValueError(f'adamw_chunk_table: negative size in {sizes}')
+    arr = (C.c_int64 * max(len(sizes), 1))(*sizes)
+    n = lib.scf_adamw_chunks(arr, len(sizes), None, 0)
+    if n < 0:
+        _lib.check(int(n), 'scf_adamw_chunks')
+    table = torch.zeros((n, 2), dtype=torch.int64)
+    if n:
+        got = lib.scf_adamw_chunks(arr, len(sizes), C.cast(table.data_ptr(), C.POINTER(_lib.AdamwChunk)), n)
+        if got != n:
+            raise _lib.ScflowHipError(f'scf_adamw_chunks wrote {got} chunks, counted {n}')
+    return table
+
+
+def adamw_chunk_rows(table: Tensor) -> List[Tuple[int, int, int]]:
+    """[(tensor index, offset, length)] of an ``adamw_chunk_table``."""
+    return [(int(a) & 0xffffffff, int(off), int(a) >> 32) for a, off in table.cpu().tolist()]
+
+
+class AdamwChunks:
+    """the uploaded chunk table of a tensor list together with what the kernels cannot check on the device: how many
+    tensors it indexes and how many chunks it has.  The wrappers below refuse pointer tables of another length."""
+
+    def __init__(self, sizes: Sequence[int], device) -> None:
+        self.sizes = [int(s) for s in sizes]
+        host = adamw_chunk_table(self.sizes)
+        self.nchunks, self.ntensors = int(host.shape[0]), len(self.sizes)
+        self.table = host.to(device)
+
+
+def _adamw_tables(chunks: AdamwChunks, **ptrs: Tensor) -> None:
+    """the device tables of the optimizer kernels: int64, on the current device, contiguous, one pointer per tensor"""
+    if not isinstance(chunks, AdamwChunks):
+        raise _lib.ScflowHipError(f'chunks: expected an ops.AdamwChunks, got {type(chunks).__name__}')
+    for name, t in (('chunks', chunks.table),) + tuple(ptrs.items()):
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != torch.int64 or not t.is_contiguous():
+            raise _lib.ScflowHipError(f'{name}: expected a contiguous int64 tensor on the GPU')
+        if t.device.index != _cur_dev():
+            raise _lib.ScflowHipError(f'{name} lives on cuda:{t.device.index} but the current device is cuda:{_cur_dev()}')
+    for name, t in ptrs.items():
+        if t.numel() != chunks.ntensors:
+            raise _lib.ScflowHipError(f'{name}: {t.numel()} pointers for {chunks.ntensors} tensors')
+
+
+def grad_sqnorm(chunks: AdamwChunks, g_ptrs: Tensor, partial: Tensor, norm: Tensor) -> Tensor:
+    """``scf_grad_sqnorm``: the L2 norm of the gradient list behind ``g_ptrs`` (device int64 table of device pointers, the
+    tensors of ``chunks.sizes`` elements) into the 0-dim ``norm``, through ``partial`` (>= nchunks floats).  Two launches,
+    no synchronisation."""
+    _adamw_tables(chunks, g_ptrs=g_ptrs)
+    _dev(partial, 'partial')
+    _dev(norm, 'norm')
+    if partial.numel() < chunks.nchunks or not partial.is_contiguous() or norm.numel() != 1:
+        raise _lib.ScflowHipError(f'grad_sqnorm: partial needs {chunks.nchunks} contiguous floats, norm one')
+    _lib.check(_lib.load().scf_grad_sqnorm(chunks.table.data_ptr(), chunks.nchunks, g_ptrs.data_ptr(), partial.data_ptr(),
+                                           norm.data_ptr(), _stream()), 'scf_grad_sqnorm')
+    return norm
+
+
+def adamw_step(chunks: AdamwChunks, p_ptrs: Tensor, g_ptrs: Tensor, m_ptrs: Tensor, v_ptrs: Tensor, norm: Optional[Tensor],
+               max_norm: float, lr: float, weight_decay: float, beta1: float, beta2: float, eps: float, step: int) -> None:
+    """``scf_adamw_step``: clip by ``max_norm`` against the device scalar ``norm`` (None: no clipping) and apply step
+    number ``step`` (1-based) of AdamW to the tensors behind the four pointer tables.  The bias corrections are computed
+    here in float64.  One launch."""
+    _adamw_tables(chunks, p_ptrs=p_ptrs, g_ptrs=g_ptrs, m_ptrs=m_ptrs, v_ptrs=v_ptrs)
+    if norm is not None:
+        _dev(norm, 'norm')
+        if norm.numel() != 1:
+            raise _lib.ScflowHipError('adamw_step: norm is one float')
+    if step < 1:
+        raise ValueError(f'adamw_step: step counts from 1, got {step}')
+    bc1, bc2 = 1.0 - float(beta1) ** step, 1.0 - float(beta2) ** step
+    _lib.check(_lib.load().scf_adamw_step(chunks.table.data_ptr(), chunks.nchunks, p_ptrs.data_ptr(), g_ptrs.data_ptr(),
+                                          m_ptrs.data_ptr(), v_ptrs.data_ptr(), None if norm is None else norm.data_ptr(),
+                                          float(max_norm) if norm is not None else 0.0, float(lr), float(weight_decay),
+                                          float(beta1), float(beta2), float(eps), bc1, bc2, _stream()), 'scf_adamw_step')
+

@@ -10,8 +10,9 @@ keys.  PnP re-mapping is outside the hot path, and
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
 ``loss()`` returns the forward VALUES the reference trains against, ``loss_and_grads()`` adds their gradients at
 the network's outputs, the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) and
-``loss_and_context_grads()`` through the context encoder -- the feature encoders and the correlation build have no backward
-and there is no ``train_step``; ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
+``loss_and_context_grads()`` through the context encoder -- the feature encoders and the correlation build have no backward.
+``train_step()`` applies those gradients with ``scflow_amd.optim.AdamW`` (the reference's ``freeze_encoder=True,
+freeze_bn=True`` case, nothing else); ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
@@ -260,6 +261,9 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         assert self.h_channels + self.cxt_channels == self.context.out_channels
         self.filter_invalid_flow = filter_invalid_flow
         self.render_augmentations = render_augmentations
+        # what train_step() may leave untouched: it trains only with BOTH set (the feature encoders and the correlation
+        # build have no backward, BatchNorm runs on its running statistics); nothing else reads them
+        self.freeze_encoder, self.freeze_bn = bool(freeze_encoder), bool(freeze_bn)
         # built at the first loss() call (_build_loss_funcs): attribute -> (constructor key, config as given)
         self._loss_cfgs = dict(pose_loss_func=('pose_loss_cfg', pose_loss_cfg), flow_loss_func=('flow_loss_cfg', flow_loss_cfg),
                                mask_loss_func=('mask_loss_cfg', mask_loss_cfg))
@@ -439,7 +443,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         through the mask, a reverse scan over whole iterations: NotImplementedError (``SCFlowDecoder.check_backward``)."""
         return self._loss(data_batch, data, 'motion')
 
-    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None, _host_log: bool = True):
         """``loss_and_motion_grads()`` (its keys, values and bits, and its refusals) with the context encoder behind it
         (``RAFTEncoder.backward`` from ``gru['initial_hidden']`` and ``gru['context']``, complete only at that rung):
         ``params`` is extended by the 62 ``context.*`` gradients, BatchNorm with running statistics as the forward
@@ -449,7 +453,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         ctx = self.context
         try:
             with ctx.keeping():
-                out = self._loss(data_batch, data, 'motion')
+                out = self._loss(data_batch, data, 'motion', _host_log)
             grads = out[-1]
             grads['params'].update(ctx.backward(
                 ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
@@ -458,7 +462,75 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             ctx.kept = {}
         return out
 
-    def _loss(self, data_batch, data, depth):
+    # ------------------------------------------------------------------ training
+    def trainable_parameters(self):
+        """the (name, parameter) pairs ``train_step`` updates: every parameter of ``decoder.*`` and ``context.*`` in
+        ``named_parameters()`` order -- the ones ``loss_and_context_grads()`` has a gradient for.  Never the feature
+        encoders (no backward) and never a buffer (BatchNorm's running statistics stay as loaded)."""
+        return [(n, p) for n, p in self.named_parameters() if n.startswith(('decoder.', 'context.'))]
+
+    def train_step(self, data_batch: Optional[Dict], optimizer, data: Optional[Dict] = None) -> Dict:
+        """base_refiner.py:325-336 -> ``dict(loss, log_vars, log_imgs=None, num_samples)``, with ONE deviation: there is no
+        autograd graph behind ``loss``, so the optimizer step happens HERE (``loss_and_context_grads()``, then
+        ``optimizer.step(grads['params'])``) -- a runner must not add an optimizer hook on top.  ``optimizer``: a
+        ``scflow_amd.optim.AdamW`` over ``trainable_parameters()`` (``build_optimizer``).  ``log_vars`` gains ``grad_norm``
+        (when the optimizer clips) and ``lr``, still through one device-to-host transfer.  After it returns the next
+        forward runs on the new weights; a hipGraph captured before (``GraphedRefiner``) holds the old ones and must be
+        captured again.
+
+        ``train_cfg['cycles'] > 1`` follows ``train_multiple_iterations`` (base_refiner.py:220-247): loss, step,
+        ``update_data`` at the last pose of the cycle, next cycle, on the attached renderer; ``log_vars`` is the mean over
+        the cycles plus ``iter_{i}_loss`` of every cycle but the last.  The last cycle steps here too (the reference leaves
+        that one to the runner's hook), and every cycle of one call uses the same learning rate.
+
+        Trains what has a backward: NotImplementedError unless ``freeze_encoder and freeze_bn``, and everything
+        ``loss_and_motion_grads()`` refuses.  ``data``: an already formatted dict (it is not modified)."""
+        from .optim import AdamW
+        if not isinstance(optimizer, AdamW):
+            raise TypeError(f'train_step needs a scflow_amd.optim.AdamW (build_optimizer), got {type(optimizer).__name__}: there '
+                            'is no autograd graph behind the loss and no .grad for another optimizer to read')
+        missing = []
+        if not self.freeze_encoder:
+            missing.append('freeze_encoder=False needs the feature-encoder and correlation-build backward')
+        if not self.freeze_bn:
+            missing.append('freeze_bn=False needs BatchNorm on batch statistics, forward and backward')
+        if missing:
+            raise NotImplementedError('train_step trains the decoder and the context encoder only (freeze_encoder=True, '
+                                      'freeze_bn=True): ' + '; '.join(missing) + ', which are not implemented')
+        mine = self.trainable_parameters()
+        if len(mine) != len(optimizer.params) or any(a is not b for (_, a), b in zip(mine, optimizer.params)):
+            raise ValueError('train_step: the optimizer was not built over this model\'s trainable_parameters()')
+        cycles = int(self.train_cfg.get('cycles', 1))
+        if cycles > 1:
+            self._need_renderer("train_cfg['cycles'] > 1")
+        self.decoder.check_backward('motion')           # refuse before anything is rendered or stepped
+        if data is None:
+            data = self.format_data_train_sup(data_batch)
+        data = dict(data)
+        num_samples = len(data_batch['img_metas']) if isinstance(data_batch, dict) and 'img_metas' in data_batch \
+            else len(data['real_images'])
+        named = []
+        for i in range(cycles):
+            loss, _, log, seq_r, seq_t, grads = self.loss_and_context_grads(data_batch, data=data, _host_log=False)
+            norm = optimizer.step(grads['params'], end_of_iteration=i == cycles - 1)
+            if optimizer.model is not self:
+                self.invalidate_packed()
+            if norm is not None:
+                log = log + [('grad_norm', norm)]
+            named.append(log)
+            if i < cycles - 1:
+                data = self.update_data(seq_r[-1], seq_t[-1], data)
+        keys = [k for k, _ in named[0]]
+        flat = self._log_vars([(f'{i}.{k}', v) for i, log in enumerate(named) for k, v in log])
+        log_vars = OrderedDict((k, sum(flat[f'{i}.{k}'] for i in range(cycles)) / cycles) for k in keys)
+        for i in range(cycles - 1):
+            log_vars[f'iter_{i}_loss'] = flat[f'{i}.loss']
+        log_vars['lr'] = optimizer.lr
+        return dict(loss=loss, log_vars=log_vars, log_imgs=None, num_samples=num_samples)
+
+    def _loss(self, data_batch, data, depth, host_log=True):
+        """``host_log=False`` (train_step): ``log_vars`` stays the list of (key, 0-dim GPU tensor) it is made from, so that
+        the caller can add its own entries and still make ONE device-to-host transfer (``_log_vars``)."""
         from . import losses as L
         at = _GRAD_DEPTHS.index
         level = at(depth)
@@ -495,7 +567,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             named += [(f'seq_{i}_pose_loss', seq_pose[i]), (f'seq_{i}_flow_loss', seq_flow[i]),
                       (f'seq_{i}_mask_loss', seq_mask[i])]
         named += [('loss_mask', loss_mask), ('loss_flow', loss_flow), ('loss_pose', loss_pose), ('loss', loss)]
-        out = (loss, None, self._log_vars(named), seq_rotations, seq_translations)
+        out = (loss, None, self._log_vars(named) if host_log else named, seq_rotations, seq_translations)
         if not with_grads:
             return out
         grads = dict(sequence_flow_from_pred=flow_out[2], sequence_masks=mask_out[2])
