@@ -1088,6 +1088,32 @@ int scf_bn_unfold(const float* W, const float* b, const float* gamma, const floa
                   int Cout, int64_t K, scf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * Backward of scf_instance_norm / scf_instance_norm_res_norm (instance_norm_grad.hip): InstanceNorm2d(eps, affine =
+ * False, biased variance, eps inside the root) as the feature encoder applies it.  Every operand is (planes, HW) dense.
+ * Per plane, with u the raw convolution output, mean / rstd recomputed from u with the forward's partial sums in the
+ * forward's order, xhat = (u - mean) rstd (one rounding each) and g' the cotangent at IN(u):
+ *   S1 = sum g', S2 = sum g' xhat, m1 = S1 / HW, m2 = S2 / HW, du = ((g' - m1) - xhat m2) rstd    (one rounding each)
+ * scf_instance_norm_grad, y == NULL and gp == NULL ("mid", relu(IN(u))): g' = g, which the consumer's dgrad epilogue has
+ *   already masked.  y != NULL and gp != NULL ("tail", y = relu(IN(u) + r)): g' = y > 0 ? g : +0, written to gp (the
+ *   shortcut's cotangent) as well.  Exactly one of y / gp NULL: SCF_EINVAL.
+ * scf_instance_norm_res_norm_grad (y = relu(IN(u) + IN(r)), the down-sampling blocks): g' as in the tail form; du from
+ *   u's statistics and S2, dr from r's own statistics and its own S2r = sum g' rhat; one g' and S1 for both.
+ * The mask is always read from y, the forward's own bits (a NaN in y masks), never from a recomputed xhat.
+ * Order: HW % 4 == 0, every pointer 16-byte aligned and HW <= 16384: the plane stays in registers, thread t of 256
+ * owns the float4 t, t + 256, ...; a thread adds its float4 as (a + b) + (c + d) to one chain from +0, then the
+ * workgroup's tree of the forward.  Other planes: four sweeps, HW % 4 == 0 aligned up to 81920 with 1024 threads
+ * in the same float4 pattern, else thread t of 256 adds elements t, t + 256, ... in one chain.  No atomics, allocation
+ * or synchronisation; bit-identical from run to run; a plane's result depends on that plane alone.  HW == 1 gives zeros.
+ * Outputs may alias g element for element (du over g) and nothing else.
+ * A null required pointer, planes <= 0 or HW <= 0: SCF_EINVAL; planes >= 2^31: SCF_EUNSUPPORTED; nothing launched or
+ * written.  Added without a version bump; the presence of scf_instance_norm_grad marks the feature.
+ * --------------------------------------------------------------------------------- */
+int scf_instance_norm_grad(const float* g, const float* y, const float* u, float* gp, float* du, int64_t planes, int HW,
+                           float eps, scf_stream_t stream);
+int scf_instance_norm_res_norm_grad(const float* g, const float* y, const float* u, const float* r, float* du, float* dr,
+                                    int64_t planes, int HW, float eps, scf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Gate arithmetic of the ConvGRU backward (raft_decoder.py:168-253; gru_grad.hip), between the convolution gradients
  * above.  One pass of the forward: z = sigmoid(conv_z([h|x])), r = sigmoid(conv_r([h|x])), q = tanh(conv_q([r h|x])),
  * h' = (1 - z) h + z q.  With g = d loss / d h':  u_q = g z (1 - q^2), u_z = g (q - h) z (1 - z), [g_rh | g_x] =

@@ -325,6 +325,8 @@ SIGNATURES = {
     'scf_bn_fold': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp, C.c_int, C.c_int64, _fp]),
     'scf_bn_unfold': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_float, _fp, _fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int,
                                 C.c_int64, _fp]),
+    'scf_instance_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
+    'scf_instance_norm_res_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
     'scf_gru_gate_grad_q': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,
                                       C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
     'scf_gru_gate_grad_r': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,

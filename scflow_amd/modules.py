@@ -232,8 +232,12 @@ class _BasicBlock(HipModule):
     def forward(self, x: Tensor, kept: Optional[list] = None) -> Tensor:
         """resnet.py:67-94.  BN (eval) is folded into the conv epilogue; IN needs the
         whole plane, so it is its own kernel (residual add + ReLU fused there).
-        ``kept``: a list that receives (the post-ReLU conv1 output, the block's output), the forward's own tensors."""
+        ``kept``: a list that receives (the post-ReLU conv1 output, the block's output), the forward's own tensors.  An
+        InstanceNorm block then normalises out of place and appends the raw outputs of conv1, conv2 and the shortcut
+        convolution (None without one) as well: ``RAFTEncoder.in_backward`` recomputes the statistics from them."""
         p = self.packed
+        if kept is not None and self.kind != 'BN':
+            return self._forward_keeping(x, kept)
         # a block with a shortcut convolution hands both layers that read x to ops.conv2d_pair: on full grids the blocks of a
         # 3x3 / s2 conv1 compute the 1x1 / s2 shortcut from the patch they stage anyway (conv_dma.hip, shared-input form)
         if self.kind == 'BN':
@@ -253,6 +257,20 @@ class _BasicBlock(HipModule):
             out = ops.instance_norm(y2, res=idt, relu=True, out=y2, res_norm='ds' in p)
         if kept is not None:
             kept.append((y, out))
+        return out
+
+    def _forward_keeping(self, x: Tensor, kept: list) -> Tensor:
+        """the InstanceNorm block's launches with every normalisation out of place: the same kernels on the same values,
+        so the same bits.  The shortcut's raw output is normalised in a copy where the final pass uses it as scratch."""
+        p = self.packed
+        if 'ds' in p:
+            u1, r = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
+        else:
+            u1, r = ops.conv2d(p['c1'], x), None
+        t = ops.instance_norm(u1, relu=True)
+        u2 = ops.conv2d(p['c2'], t)
+        out = ops.instance_norm(u2, res=x if r is None else r.clone(), relu=True, res_norm=r is not None)
+        kept.append((t, out, u1, u2, r))
         return out
 
 
@@ -295,7 +313,9 @@ class RAFTEncoder(HipModule):
         # under keeping() a forward leaves in ``kept`` what backward() reads: x (the input image), stem (the stem's output), per
         # block i = 0 .. 5 t{i} (the post-ReLU conv1 output) and y{i} (the block's output), and out (the head's
         # post-activation output).  The forward's own tensors; out is a copy when the caller owns its destination.  Its own
-        # switch, not a level of SCFlowDecoder.keep; a forward outside keeping() empties it
+        # switch, not a level of SCFlowDecoder.keep; a forward outside keeping() empties it.  An InstanceNorm encoder
+        # normalises out of place while keeping (same bits) and adds what in_backward() reads: u_stem, u1_{i}, u2_{i} (the raw
+        # outputs of the stem and of a block's two convolutions) and r{i} (the raw output of a shortcut convolution, i = 2, 4)
         self.keep = False
         self.kept = {}
 
@@ -326,8 +346,9 @@ class RAFTEncoder(HipModule):
         if self.kind == 'BN':
             x = ops.conv2d(p['stem'], x, act=ACT_RELU)
         else:
-            x = ops.conv2d(p['stem'], x)
-            ops.instance_norm(x, relu=True, out=x)
+            x = raw = ops.conv2d(p['stem'], x)
+            # keeping: out of place (the same kernel on the same values), the raw output stays for in_backward()
+            x = ops.instance_norm(raw, relu=True, out=None if self.keep else raw)
         stem = x
         for name in self.res_layers:
             for blk in getattr(self, name):
@@ -335,13 +356,18 @@ class RAFTEncoder(HipModule):
         y = ops.conv2d(p['head'], x, out=out, act=head_act, act2=head_act2,
                        act_split=head_split)
         self.kept = {} if blocks is None else self._kept_dict(image, stem, blocks, y, out is not None)
+        if blocks is not None and self.kind == 'IN':
+            self.kept['u_stem'] = raw
         return y
 
     @staticmethod
     def _kept_dict(image: Tensor, stem: Tensor, blocks, y: Tensor, clone_out: bool) -> dict:
         kept = dict(x=image, stem=stem, out=y.clone() if clone_out else y)
-        for i, (t, o) in enumerate(blocks):
+        for i, (t, o, *raws) in enumerate(blocks):
             kept[f't{i}'], kept[f'y{i}'] = t, o
+            for k, v in zip(('u1_', 'u2_', 'r'), raws):       # an InstanceNorm block's raw convolution outputs
+                if v is not None:
+                    kept[f'{k}{i}'] = v
         return kept
 
     def backward(self, saved: dict, g_out: Union[Tensor, Sequence[Tensor]], out: Optional[Tensor] = None,
@@ -368,8 +394,9 @@ class RAFTEncoder(HipModule):
         ``intermediates``: a dict that receives every launch's operands and results (None: nothing is kept)."""
         what = 'RAFTEncoder.backward'
         if self.kind != 'BN':
-            raise NotImplementedError(f'{what}: the InstanceNorm feature encoder has no backward yet; it waits for the '
-                                      'correlation-build backward, which gives the cotangents at its outputs')
+            raise NotImplementedError(f'{what}: this is the BatchNorm chain; the InstanceNorm feature encoder\'s is '
+                                      'RAFTEncoder.in_backward, which takes a cotangent at the encoder\'s output -- the '
+                                      'training step still waits for the correlation-build backward to produce it')
         if self.stem_stride != 2:
             raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
         blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
@@ -463,6 +490,108 @@ class RAFTEncoder(HipModule):
         dwf, dbf = ops.conv_stem_wgrad(G, image)
         unfold('conv1', 'conv1', self.tag + '1', self.conv1, n1, dwf, dbf)
         rec['conv1'].update(g=G, x=image)
+        return grads
+
+    def in_backward(self, saved: dict, g_out: Tensor, param_grads: Optional[dict] = None,
+                    intermediates: Optional[dict] = None, prefix: str = ''):
+        """Backward of the InstanceNorm encoder with respect to its parameters: the reference's feature encoder
+        (``norm_cfg=dict(type='IN')``, affine=False).  The input image gets no gradient.
+
+        ``saved``: ``kept`` of a forward under ``keeping()`` (x, stem, u_stem and per block t, y, u1_, u2_, with r for the
+        two down-sampling blocks).  ``g_out``: the cotangent at the 1x1 head's output (N, out_channels, h, w); that head has
+        no activation.  -> the gradients of the 32 parameters summed over the samples, keyed as ``named_parameters()``
+        behind ``prefix``; ``param_grads`` and ``intermediates`` as in ``backward``.
+
+        Chain: ``backward``'s order and launches on the raw weights (nothing to fold or unfold), with the derivative of
+        InstanceNorm (``ops.instance_norm_grad``) between the convolution gradients.  Head: wgrad and an unmasked dgrad ->
+        G, the cotangent at the last block's output.  Per block in reverse: the tail form on (G, y, u2) -> g' = G [y > 0]
+        (the shortcut's cotangent) and du2 -- a down-sampling block: (du2, dr) from (G, y, u2, r); conv2's wgrad (du2, t)
+        and dgrad under the mask of t; the mid form -> du1; conv1's wgrad and a dgrad that adds g' and stays unmasked (the
+        block in front masks with its own y; in front of block 0 the stem's output masks in the epilogue) -- a
+        down-sampling block: ``conv_wgrad`` + ``channel_sum``, ``conv_dgrad``, the shortcut's ``conv_ds_wgrad`` (dr, x)
+        and the unmasked join ``conv_ds_dgrad``.  Last the mid form at the stem and ``conv_stem_wgrad`` at Cin = 3.
+
+        The bias of a convolution in front of an InstanceNorm has gradient 0 in exact arithmetic (du sums to 0 over a
+        plane); it is computed like any other bias gradient and comes out as rounding noise, as autograd's does.
+
+        Nothing joins this to ``train_step`` yet: the cotangent at the encoder's output comes from the correlation-build
+        backward, which the project does not have."""
+        what = 'RAFTEncoder.in_backward'
+        if self.kind != 'IN':
+            raise NotImplementedError(f'{what}: a BatchNorm encoder takes RAFTEncoder.backward (eval statistics, folded)')
+        if self.stem_stride != 2:
+            raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
+        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
+        nb = len(blocks)
+        keys = (['x', 'stem', 'u_stem'] + [f'{k}{i}' for i in range(nb) for k in ('t', 'y', 'u1_', 'u2_')]
+                + [f'r{i}' for i, blk in enumerate(blocks) if blk.downsample is not None])
+        try:
+            got = {k: saved[k] for k in keys}
+        except (KeyError, TypeError):
+            raise _lib_error(f"{what}: saved holds {', '.join(keys)}: RAFTEncoder.kept after an InstanceNorm encoder's "
+                             'forward under keeping()') from None
+        image, y_last = got['x'], got[f'y{nb - 1}']
+        shape = (y_last.shape[0], self.out_channels) + tuple(y_last.shape[2:])
+        if not isinstance(g_out, torch.Tensor) or tuple(g_out.shape) != shape:
+            raise _lib_error(f'{what}: g_out must be a {shape} tensor, got '
+                             f'{tuple(g_out.shape) if isinstance(g_out, torch.Tensor) else type(g_out).__name__}')
+        names = [prefix + k for k, _ in self.named_parameters()]
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
+        dst = dict(zip(names, dst))
+        rec = {} if intermediates is None else intermediates
+        eps = getattr(self, self.tag + '1').eps
+
+        def put(key, dw, db):
+            grads[f'{prefix}{key}.weight'], grads[f'{prefix}{key}.bias'] = dw, db
+
+        def slots(key):
+            return dict(dw=dst[f'{prefix}{key}.weight'], db=dst[f'{prefix}{key}.bias'], accumulate=acc)
+
+        # ---- head: 1x1, no norm, no activation
+        put('conv2', *ops.conv_s1_wgrad(g_out, y_last, (1, 1), **slots('conv2')))
+        G = ops.conv_s1_dgrad(g_out, self.conv2.weight)
+        rec['head'] = dict(g=g_out, x=y_last, gx=G)
+        # ---- blocks, last to first
+        i = nb
+        for name in reversed(self.res_layers):
+            layer = getattr(self, name)
+            for j in reversed(range(len(layer))):
+                i -= 1
+                blk, key = layer[j], f'{name}.{j}'
+                x_in, t, y = (got[f'y{i - 1}'] if i else got['stem']), got[f't{i}'], got[f'y{i}']
+                u1, u2 = got[f'u1_{i}'], got[f'u2_{i}']
+                if blk.downsample is None:
+                    g_sc, du2 = ops.instance_norm_grad(G, u2, y=y, eps=eps)
+                    rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
+                else:
+                    du2, dr = ops.instance_norm_grad(G, u2, y=y, r=got[f'r{i}'], eps=eps)
+                    rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=dr)
+                put(f'{key}.conv2', *ops.conv_s1_wgrad(du2, t, (3, 3), **slots(f'{key}.conv2')))
+                g_t = ops.conv_s1_dgrad(du2, blk.conv2.weight, a=t, act=ACT_RELU)
+                rec[f'{key}.conv2'] = dict(g=du2, x=t, gx=g_t)
+                du1 = ops.instance_norm_grad(g_t, u1, eps=eps)
+                rec[f'{key}.in1'] = dict(g=g_t, u=u1, du=du1)
+                if blk.downsample is None:
+                    put(f'{key}.conv1', *ops.conv_s1_wgrad(du1, x_in, (3, 3), **slots(f'{key}.conv1')))
+                    mask = dict(a=x_in, act=ACT_RELU) if i == 0 else {}
+                    g_prev = ops.conv_s1_dgrad(du1, blk.conv1.weight, add=g_sc, **mask)
+                    rec[f'{key}.conv1'] = dict(g=du1, x=x_in, add=g_sc, gx=g_prev)
+                else:
+                    in_hw = tuple(x_in.shape[2:])
+                    s = slots(f'{key}.conv1')
+                    put(f'{key}.conv1', ops.conv_wgrad(du1, x_in, dw=s['dw'], accumulate=acc),
+                        ops.channel_sum(du1, out=s['db'], accumulate=acc))
+                    gx1 = ops.conv_dgrad(du1, blk.conv1.weight, in_hw)
+                    rec[f'{key}.conv1'] = dict(g=du1, x=x_in, gx=gx1)
+                    put(f'{key}.downsample.0', *ops.conv_ds_wgrad(dr, x_in, **slots(f'{key}.downsample.0')))
+                    g_prev = ops.conv_ds_dgrad(dr, blk.downsample[0].weight, in_hw, add=gx1)
+                    rec[f'{key}.downsample'] = dict(g=dr, x=x_in, add=gx1, gx=g_prev)
+                G = g_prev
+        # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
+        du = ops.instance_norm_grad(G, got['u_stem'], eps=eps)
+        rec['in1'] = dict(g=G, u=got['u_stem'], du=du)
+        put('conv1', *ops.conv_stem_wgrad(du, image, **slots('conv1')))
+        rec['conv1'] = dict(g=du, x=image)
         return grads
 
 

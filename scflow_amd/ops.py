@@ -2593,6 +2593,52 @@ def bn_unfold(weight: Tensor, bias: Tensor, gamma: Tensor, mean: Tensor, var: Te
     return (dw, *vec)
 
 
+# ------------------------------------------------- backward of InstanceNorm (instance_norm_grad.hip)
+def instance_norm_grad(g: Tensor, u: Tensor, y: Optional[Tensor] = None, r: Optional[Tensor] = None, eps: float = 1e-5,
+                       out: Optional[Sequence[Optional[Tensor]]] = None):
+    """Backward of ``instance_norm`` with respect to its raw input(s) (``scf_instance_norm_grad``,
+    ``scf_instance_norm_res_norm_grad``).  ``u``: the raw convolution output the forward normalised; the statistics are
+    recomputed from it.  Every operand a contiguous (N, C, H, W) tensor of one shape.  Three forms:
+
+    * ``y`` None (``relu(IN(u))``): ``g`` is the cotangent at ``IN(u)``, already masked by the consumer -> ``du``;
+    * ``y`` given (``y = relu(IN(u) + res)``): ``g`` the cotangent at ``y`` -> ``(g', du)`` with ``g' = g [y > 0]``, which
+      is also the cotangent of ``res``;
+    * ``y`` and ``r`` given (``y = relu(IN(u) + IN(r))``, ``res_norm=True``): -> ``(du, dr)``.
+
+    ``out``: the destination(s) in the order returned (None entries are allocated); ``du`` may be ``g`` itself."""
+    what = 'instance_norm_grad'
+    if g.dim() != 4 or g.numel() == 0:
+        raise _lib.ScflowHipError(f'{what}: g must be a non-empty (N, C, H, W) tensor, got {tuple(g.shape)}')
+    if r is not None and y is None:
+        raise _lib.ScflowHipError(f'{what}: r (a normalised shortcut) comes with y, the block\'s output')
+    shape = tuple(g.shape)
+    named = dict(g=g, u=u, y=y, r=r)
+    nout = 1 if y is None else 2
+    outs = [None] * nout if out is None else ([out] if isinstance(out, torch.Tensor) else list(out))
+    if len(outs) != nout:
+        raise _lib.ScflowHipError(f'{what}: out holds {nout} destination(s) in this form, got {len(outs)}')
+    outs = [torch.empty(shape, dtype=torch.float32, device=g.device) if o is None else o for o in outs]
+    named.update({f'out[{i}]': o for i, o in enumerate(outs)})
+    ptr = {}
+    for k, t in named.items():
+        if t is None:
+            ptr[k] = None
+            continue
+        ptr[k] = _dense(t, f'{what}: {k}')
+        if tuple(t.shape) != shape:
+            raise _lib.ScflowHipError(f'{what}: {k} must be {shape} like g, got {tuple(t.shape)}')
+    n, c, h, w = shape
+    lib = _lib.load()
+    if r is None:
+        gp, du = (None, ptr['out[0]']) if y is None else (ptr['out[0]'], ptr['out[1]'])
+        _lib.check(lib.scf_instance_norm_grad(ptr['g'], ptr['y'], ptr['u'], gp, du, n * c, h * w, float(eps), _stream()),
+                   'scf_instance_norm_grad')
+    else:
+        _lib.check(lib.scf_instance_norm_res_norm_grad(ptr['g'], ptr['y'], ptr['u'], ptr['r'], ptr['out[0]'], ptr['out[1]'],
+                                                       n * c, h * w, float(eps), _stream()), 'scf_instance_norm_res_norm_grad')
+    return outs[0] if nout == 1 else tuple(outs)
+
+
 # ------------------------------------------------- gate arithmetic of the ConvGRU backward (gru_grad.hip)
 def _gg_rows(what: str, shape, named) -> list:
     """(pointer, sample stride) of every (M, C, H, W) operand of a gate kernel; None stays (None, 0)."""

@@ -293,9 +293,10 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         # materialised here, on the main stream, before the fork event (a copy enqueued after it
         # would not be ordered before the side branch's first read)
         rend = render_images.contiguous()
-        # a context encoder that keeps its activations for backward() runs its own forward, on this stream: the paired walk
-        # below keeps nothing (same kernels per layer, same bits), and what it keeps is read on this stream afterwards
-        keeping = self.context.keep
+        # an encoder that keeps its activations for backward() / in_backward() runs its own forward, on this stream: the
+        # paired walk below keeps nothing (same kernels per layer, same bits), and what it keeps is read on this stream
+        # afterwards
+        keeping = self.context.keep or self.render_encoder.keep or self.real_encoder.keep
         ov_ctx = small_work(n, H, W, 'context') and not keeping
         fork = ops.fork_point() if ov_ctx else None     # the context encoder may start from here
         if (not self.seperate_encoder and not keeping and ops.branch_mode(n, H, W, 'context') == 2
@@ -462,11 +463,40 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             ctx.kept = {}
         return out
 
+    def feature_grads(self, g_render_feat: Tensor, g_real_feat: Tensor, param_grads: Optional[dict] = None) -> dict:
+        """The feature encoders' parameter gradients from the cotangents at ``extract_feat``'s (render_feat, real_feat),
+        after a forward inside ``render_encoder.keeping()`` (and ``real_encoder.keeping()`` with
+        ``seperate_encoder=True``): ``RAFTEncoder.in_backward``.  The shared encoder: ONE pass over the 2N stacked
+        cotangents, render first as the forward stacks the images, so every gradient is the sum over both image sets;
+        keys as ``named_parameters()`` has them (``render_encoder.*``, the shared module's first name).  Separate
+        encoders: two passes, ``render_encoder.*`` and ``real_encoder.*``.  ``param_grads`` as in ``in_backward``.  What
+        the encoders kept is dropped before returning, also on an error.
+
+        Nothing calls this yet: the ``loss_and_*_grads()`` rungs, ``trainable_parameters()`` and ``train_step`` stop at
+        the correlation volume, and joining them waits for the correlation-build backward, which turns d loss / d volume
+        into the two cotangents this takes."""
+        what = 'SCFlowRefiner.feature_grads'
+        fe, re_ = self.render_encoder, self.real_encoder
+        try:
+            for name, g in (('g_render_feat', g_render_feat), ('g_real_feat', g_real_feat)):
+                ops._dev(g, f'{what}: {name}')
+            if g_render_feat.shape != g_real_feat.shape or g_render_feat.dim() != 4:
+                raise ops._lib.ScflowHipError(f'{what}: the two cotangents are (N, C, h, w) tensors of one shape, got '
+                                              f'{tuple(g_render_feat.shape)} and {tuple(g_real_feat.shape)}')
+            if not self.seperate_encoder:
+                return fe.in_backward(fe.kept, torch.cat((g_render_feat, g_real_feat)), param_grads=param_grads,
+                                      prefix='render_encoder.')
+            grads = fe.in_backward(fe.kept, g_render_feat.contiguous(), param_grads=param_grads, prefix='render_encoder.')
+            return re_.in_backward(re_.kept, g_real_feat.contiguous(), param_grads=grads, prefix='real_encoder.')
+        finally:
+            fe.kept, re_.kept = {}, {}
+
     # ------------------------------------------------------------------ training
     def trainable_parameters(self):
         """the (name, parameter) pairs ``train_step`` updates: every parameter of ``decoder.*`` and ``context.*`` in
         ``named_parameters()`` order -- the ones ``loss_and_context_grads()`` has a gradient for.  Never the feature
-        encoders (no backward) and never a buffer (BatchNorm's running statistics stay as loaded)."""
+        encoders (``feature_grads`` has their backward, but no rung reaches it before the correlation-build backward
+        exists) and never a buffer (BatchNorm's running statistics stay as loaded)."""
         return [(n, p) for n, p in self.named_parameters() if n.startswith(('decoder.', 'context.'))]
 
     def train_step(self, data_batch: Optional[Dict], optimizer, data: Optional[Dict] = None) -> Dict:
