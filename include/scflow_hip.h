@@ -1175,6 +1175,25 @@ int scf_gru_gate_state(const float* h, int64_t h_stride, const float* gate, int6
 int scf_corr_lookup_grad(const float* g_corr, const float* flow, const float* mask, float* g_vol, int accumulate, int T,
                          int N, int h, int w, int r, int L, scf_stream_t stream);
 
+/* ---------------------------------------------------------------------------------
+ * Adjoint of scf_corr_build's level 0 with respect to the two feature maps (corr_build_grad.hip).  g_vol (N, hw, hw)
+ * row-major: d loss / d level 0, exactly what scf_corr_lookup_grad writes (the tiled pyramid layout never reaches this
+ * stage); feat1 (queries i) / feat2 (targets j) and both outputs (N, C, h, w) dense.  With s = 1/sqrt(C):
+ *   g_feat1[n][c][i] = s sum_j g_vol[n][i][j] feat2[n][c][j]
+ *   g_feat2[n][c][j] = s sum_i g_vol[n][i][j] feat1[n][c][i]
+ * Two fp32 matrix-instruction GEMMs, one launch each; a block owns 128 channels x 128 positions of one sample and walks
+ * the whole contraction.  Order: per output ONE fma chain from +0 over the contraction index ascending (j resp. i), then
+ * the scale once -- multiplied by s when sqrt(C) is a power of two (exact), otherwise a correctly rounded division by
+ * sqrtf(C): scf_corr_build's rule.  One route: every N, C, h, w >= 1 and any 4-byte aligned pointers, every load and
+ * store under an explicit bound.  No atomics, allocation or synchronisation; bit-identical from run to run; a sample's
+ * result does not depend on N.  A NaN at g_vol[n][i][j] reaches g_feat1[n][:, i] and g_feat2[n][:, j] only.
+ * A null pointer, a non-positive size, or an output that overlaps the other output or an input: SCF_EINVAL; h w or C
+ * within 128 of 2^31, an operand of 2^61 floats and more, or 2^31 tiles and more: SCF_EUNSUPPORTED; nothing launched or
+ * written.  Added without a version bump; the presence of the symbol marks the feature.
+ * --------------------------------------------------------------------------------- */
+int scf_corr_build_grad(const float* g_vol, const float* feat1, const float* feat2, float* g_feat1, float* g_feat2, int N,
+                        int C, int h, int w, scf_stream_t stream);
+
 /* RAFT convex up-sampling (x8, 3x3 neighbourhood).  replaces RAFTDecoder._upsample
  * models/decoder/raft_decoder.py:381-416 and RAFTDecoderMask.upsample_flow/upsample_mask
  * raft_decoder_mask.py:104-160:  out[n,c,8y+sy,8x+sx] = sum_k softmax_k(mask_mul *

@@ -49,8 +49,9 @@ _KEEP = {name: i for i, name in enumerate(KEEP_LEVELS)}
 # how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do; from 'head' on the chain is
 # SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  Behind the last depth the
 # context encoder has RAFTEncoder.backward (from grads['gru']['initial_hidden'] and grads['gru']['context'];
-# SCFlowRefiner.loss_and_context_grads), its own switch and no depth of this ladder.  No backward yet: the correlation build
-# and the feature encoders behind it (they start from grads['motion']['correlation']), and the path from iteration t into
+# SCFlowRefiner.loss_and_context_grads), its own switch and no depth of this ladder; so have the correlation build
+# (SCFlowDecoder.corr_backward, from grads['motion']['correlation']) and the feature encoders behind it
+# (RAFTEncoder.in_backward; SCFlowRefiner.loss_and_network_grads).  No backward yet: the path from iteration t into
 # iteration t - 1 under
 # detach_flow=False or under mask_flow / mask_corr without detach_mask (SCFlowDecoder.check_backward refuses it at 'motion')
 _GRAD_DEPTHS = ('none', 'outputs', 'head') + KEEP_LEVELS[1:]
@@ -396,7 +397,7 @@ class RAFTEncoder(HipModule):
         if self.kind != 'BN':
             raise NotImplementedError(f'{what}: this is the BatchNorm chain; the InstanceNorm feature encoder\'s is '
                                       'RAFTEncoder.in_backward, which takes a cotangent at the encoder\'s output -- the '
-                                      'training step still waits for the correlation-build backward to produce it')
+                                      'correlation-build backward (SCFlowDecoder.corr_backward) produces it')
         if self.stem_stride != 2:
             raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
         blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
@@ -514,8 +515,8 @@ class RAFTEncoder(HipModule):
         The bias of a convolution in front of an InstanceNorm has gradient 0 in exact arithmetic (du sums to 0 over a
         plane); it is computed like any other bias gradient and comes out as rounding noise, as autograd's does.
 
-        Nothing joins this to ``train_step`` yet: the cotangent at the encoder's output comes from the correlation-build
-        backward, which the project does not have."""
+        ``SCFlowRefiner.loss_and_network_grads`` calls this with the correlation-build backward's result
+        (``SCFlowDecoder.corr_backward``); ``train_step`` does not reach it yet."""
         what = 'RAFTEncoder.in_backward'
         if self.kind != 'IN':
             raise NotImplementedError(f'{what}: a BatchNorm encoder takes RAFTEncoder.backward (eval statistics, folded)')
@@ -1503,6 +1504,15 @@ class SCFlowDecoder(HipModule):
             for lst, v in zip(outs, (flow, flow_pred, rot, trans, up_mask, d_rot, d_trans)):
                 lst.append(v)
         return outs
+
+    def corr_backward(self, feat_render: Tensor, feat_real: Tensor, g_vol: Tensor,
+                      out: Optional[Sequence[Optional[Tensor]]] = None) -> Tuple[Tensor, Tensor]:
+        """Backward of ``forward``'s ``corr_block`` call with respect to the two feature maps (``ops.corr_build_grad``):
+        ``g_vol`` is d loss / d (level 0 of the pyramid) (N h w, h, w) row-major with the pools' adjoints folded in, what
+        ``motion_backward`` returns as ``correlation`` -> (d loss / d ``feat_render``, d loss / d ``feat_real``).  ``forward``
+        only reads the two maps (the pyramid is built from them and nothing else touches them), so the maps of that same
+        forward are the operands.  ``out``: a pair of destinations, e.g. the halves of one (2N, C, h, w) buffer."""
+        return ops.corr_build_grad(g_vol, feat_render, feat_real, out=out)
 
     def _keep_iteration(self, level: int, t: int, hv: Tensor, dm: Tensor, ys, clone: bool = False,
                         d_flow: Optional[Tensor] = None, mask: Optional[Tensor] = None, xm: Optional[Tensor] = None,

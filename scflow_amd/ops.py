@@ -1071,6 +1071,46 @@ def corr_lookup_grad(g_corr: Tensor, flow: Tensor, mask: Optional[Tensor] = None
     return out
 
 
+def corr_build_grad(g_vol: Tensor, feat1: Tensor, feat2: Tensor, out: Optional[Sequence[Optional[Tensor]]] = None
+                    ) -> Tuple[Tensor, Tensor]:
+    """Adjoint of ``corr_build``'s level 0 with respect to the two feature maps (``scf_corr_build_grad``): ``g_vol``
+    (N h w, h, w) or (N, h w, h w), d loss / d level 0 row-major as ``corr_lookup_grad`` writes it; ``feat1`` (the queries,
+    render) and ``feat2`` (the targets, real) (N, C, h, w) -> ``(g_feat1, g_feat2)``, both (N, C, h, w).  ``out``: a pair
+    of destinations (None entries are allocated) -- the two halves of one (2N, C, h, w) buffer are what the shared encoder's
+    backward takes.  Every argument contiguous; the outputs alias neither each other nor an input.  The order of every
+    sum is the header's."""
+    what = 'corr_build_grad'
+    pf1 = _dense(feat1, f'{what}: feat1')
+    pf2 = _dense(feat2, f'{what}: feat2')
+    pg = _dense(g_vol, f'{what}: g_vol')
+    if feat1.dim() != 4 or feat1.numel() == 0:
+        raise _lib.ScflowHipError(f'{what}: feat1 must be a non-empty (N, C, h, w) tensor, got {tuple(feat1.shape)}')
+    shape = tuple(feat1.shape)
+    n, c, h, w = shape
+    if tuple(feat2.shape) != shape:
+        raise _lib.ScflowHipError(f'{what}: feat2 must be {shape} like feat1, got {tuple(feat2.shape)}')
+    if tuple(g_vol.shape) not in ((n * h * w, h, w), (n, h * w, h * w)):
+        raise _lib.ScflowHipError(f'{what}: g_vol must be {(n * h * w, h, w)} or {(n, h * w, h * w)}, got '
+                                  f'{tuple(g_vol.shape)}')
+    outs = [None, None] if out is None else ([out] if isinstance(out, torch.Tensor) else list(out))
+    if len(outs) != 2:
+        raise _lib.ScflowHipError(f'{what}: out holds the pair (g_feat1, g_feat2), got {len(outs)} destination(s)')
+    outs = [torch.empty(shape, dtype=torch.float32, device=feat1.device) if o is None else o for o in outs]
+    po = []
+    for i, o in enumerate(outs):
+        po.append(_dense(o, f'{what}: out[{i}]'))
+        if tuple(o.shape) != shape:
+            raise _lib.ScflowHipError(f'{what}: out[{i}] must be {shape}, got {tuple(o.shape)}')
+    spans = [(f'out[{i}]', p, feat1.numel()) for i, p in enumerate(po)]
+    spans += [('feat1', pf1, feat1.numel()), ('feat2', pf2, feat2.numel()), ('g_vol', pg, g_vol.numel())]
+    for i in range(2):
+        for name, p, numel in spans[i + 1:]:
+            if po[i] < p + 4 * numel and p < po[i] + 4 * feat1.numel():
+                raise _lib.ScflowHipError(f'{what}: out[{i}] overlaps {name}')
+    _lib.check(_lib.load().scf_corr_build_grad(pg, pf1, pf2, po[0], po[1], n, c, h, w, _stream()), 'scf_corr_build_grad')
+    return outs[0], outs[1]
+
+
 class _TimerPool:
     """launch-bound timers (scf_timer_*), created up front so that a timed loop only takes one
     from the pool; ``read()`` returns the durations of the timers used since the last reset."""

@@ -10,7 +10,8 @@ keys.  PnP re-mapping is outside the hot path, and
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
 ``loss()`` returns the forward VALUES the reference trains against, ``loss_and_grads()`` adds their gradients at
 the network's outputs, the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) and
-``loss_and_context_grads()`` through the context encoder -- the feature encoders and the correlation build have no backward.
+``loss_and_context_grads()`` through the context encoder, ``loss_and_network_grads()`` through the correlation build and
+the feature encoders to every parameter of the network.
 ``train_step()`` applies those gradients with ``scflow_amd.optim.AdamW`` (the reference's ``freeze_encoder=True,
 freeze_bn=True`` case, nothing else); ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
@@ -18,6 +19,7 @@ and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
 from __future__ import annotations
 
+import contextlib
 from collections import OrderedDict
 from typing import Dict, Optional, Tuple, Union
 
@@ -331,14 +333,22 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         """scflow_refiner.py:112-142 -> 7-tuple of length-``iters`` lists
         (flow_from_pose, flow_from_pred, rotation_preds, translation_preds, mask_preds,
         delta_rotation_preds, delta_translation_preds)."""
+        return self._pose_and_features(render_images, real_images, ref_rotation, ref_translation, depth, internel_k, label,
+                                       init_flow)[0]
+
+    def _pose_and_features(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor, ref_translation: Tensor,
+                           depth: Tensor, internel_k: Tensor, label: Tensor, init_flow: Optional[Tensor] = None):
+        """``get_pose`` -> (its 7-tuple, (feat_render, feat_real)): the two feature maps of this forward for
+        ``loss_and_network_grads``.  The decoder only reads them (``corr_block``), so references are enough."""
         feat_render, feat_real, h_feat, cxt_feat = self.extract_feat(render_images, real_images)
         if init_flow is None:
             n, _, H, W = real_images.shape
             init_flow = ops.constant((n, 2, H, W), 0.0, feat_render.device)      # read-only, filled once
-        return self.decoder(feat_render, feat_real, h_feat, cxt_feat, ref_rotation,
+        outs = self.decoder(feat_render, feat_real, h_feat, cxt_feat, ref_rotation,
                             ref_translation, depth.contiguous(), internel_k.contiguous(),
                             label=label, init_flow=init_flow, invalid_flow_num=0.,
                             _consume_state=True)      # h / cxt are ours: update them in place
+        return outs, (feat_render, feat_real)
 
     def forward_single_pass(self, data: Dict, data_batch: Optional[Dict] = None,
                             return_loss: bool = False) -> Dict:
@@ -444,7 +454,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         through the mask, a reverse scan over whole iterations: NotImplementedError (``SCFlowDecoder.check_backward``)."""
         return self._loss(data_batch, data, 'motion')
 
-    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None, _host_log: bool = True):
+    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None, _host_log: bool = True,
+                               _features: Optional[list] = None):
         """``loss_and_motion_grads()`` (its keys, values and bits, and its refusals) with the context encoder behind it
         (``RAFTEncoder.backward`` from ``gru['initial_hidden']`` and ``gru['context']``, complete only at that rung):
         ``params`` is extended by the 62 ``context.*`` gradients, BatchNorm with running statistics as the forward
@@ -454,13 +465,48 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         ctx = self.context
         try:
             with ctx.keeping():
-                out = self._loss(data_batch, data, 'motion', _host_log)
+                out = self._loss(data_batch, data, 'motion', _host_log, _features)
             grads = out[-1]
             grads['params'].update(ctx.backward(
                 ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
                 head_act2=ACT_RELU, head_split=self.h_channels, prefix='context.'))
         finally:
             ctx.kept = {}
+        return out
+
+    def loss_and_network_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
+        """``loss_and_context_grads()`` (its keys, values and bits, and its refusals) with the correlation build and the
+        feature encoder(s) behind it: ``SCFlowDecoder.corr_backward`` turns ``motion['correlation']`` and the two feature
+        maps of this same forward into ``features`` = ``dict(render, real)``, d loss / d ``extract_feat``'s (render_feat,
+        real_feat) (N, C, h, w); ``RAFTEncoder.in_backward`` carries them on.  ``params`` is extended by the 32
+        ``render_encoder.*`` gradients -- with the shared encoder ONE pass over the (2N, ...) buffer the two cotangents
+        are the halves of, render first, so each is the sum over both image sets -- and with ``seperate_encoder=True`` by
+        32 + 32 (``render_encoder.*``, ``real_encoder.*``): ``params`` then covers all of ``named_parameters()``, and
+        ``scflow_amd.optim.AdamW(list(model.named_parameters()))`` steps the whole network from it.  The encoders keep
+        their activations during this forward and everything kept is dropped before returning, also on an error."""
+        fe, re_ = self.render_encoder, self.real_encoder
+        held = []                                   # receives (feat_render, feat_real) of the rung's own forward
+        try:
+            with contextlib.ExitStack() as stack:
+                stack.enter_context(fe.keeping())
+                if self.seperate_encoder:
+                    stack.enter_context(re_.keeping())
+                out = self.loss_and_context_grads(data_batch, data, _features=held)
+            grads = out[-1]
+            feat_render, feat_real = held
+            n = feat_render.shape[0]
+            both = torch.empty((2 * n,) + tuple(feat_render.shape[1:]), dtype=torch.float32, device=feat_render.device)
+            g_render, g_real = self.decoder.corr_backward(feat_render, feat_real, grads['motion']['correlation'],
+                                                          out=(both[:n], both[n:]))
+            grads['features'] = dict(render=g_render, real=g_real)
+            if not self.seperate_encoder:
+                enc = fe.in_backward(fe.kept, both, prefix='render_encoder.')
+            else:
+                enc = fe.in_backward(fe.kept, g_render, prefix='render_encoder.')
+                enc = re_.in_backward(re_.kept, g_real, param_grads=enc, prefix='real_encoder.')
+            grads['params'].update(enc)
+        finally:
+            fe.kept, re_.kept = {}, {}
         return out
 
     def feature_grads(self, g_render_feat: Tensor, g_real_feat: Tensor, param_grads: Optional[dict] = None) -> dict:
@@ -472,9 +518,9 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         encoders: two passes, ``render_encoder.*`` and ``real_encoder.*``.  ``param_grads`` as in ``in_backward``.  What
         the encoders kept is dropped before returning, also on an error.
 
-        Nothing calls this yet: the ``loss_and_*_grads()`` rungs, ``trainable_parameters()`` and ``train_step`` stop at
-        the correlation volume, and joining them waits for the correlation-build backward, which turns d loss / d volume
-        into the two cotangents this takes."""
+        ``loss_and_network_grads()`` is the rung that reaches this chain (it hands ``in_backward`` the correlation-build
+        backward's (2N, ...) buffer directly); ``trainable_parameters()`` and ``train_step`` still stop at the
+        correlation volume."""
         what = 'SCFlowRefiner.feature_grads'
         fe, re_ = self.render_encoder, self.real_encoder
         try:
@@ -495,8 +541,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
     def trainable_parameters(self):
         """the (name, parameter) pairs ``train_step`` updates: every parameter of ``decoder.*`` and ``context.*`` in
         ``named_parameters()`` order -- the ones ``loss_and_context_grads()`` has a gradient for.  Never the feature
-        encoders (``feature_grads`` has their backward, but no rung reaches it before the correlation-build backward
-        exists) and never a buffer (BatchNorm's running statistics stay as loaded)."""
+        encoders (``loss_and_network_grads()`` has their gradients; ``train_step`` does not take that rung yet) and never a
+        buffer (BatchNorm's running statistics stay as loaded)."""
         return [(n, p) for n, p in self.named_parameters() if n.startswith(('decoder.', 'context.'))]
 
     def train_step(self, data_batch: Optional[Dict], optimizer, data: Optional[Dict] = None) -> Dict:
@@ -558,9 +604,10 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         log_vars['lr'] = optimizer.lr
         return dict(loss=loss, log_vars=log_vars, log_imgs=None, num_samples=num_samples)
 
-    def _loss(self, data_batch, data, depth, host_log=True):
+    def _loss(self, data_batch, data, depth, host_log=True, features=None):
         """``host_log=False`` (train_step): ``log_vars`` stays the list of (key, 0-dim GPU tensor) it is made from, so that
-        the caller can add its own entries and still make ONE device-to-host transfer (``_log_vars``)."""
+        the caller can add its own entries and still make ONE device-to-host transfer (``_log_vars``).  ``features``: a
+        list that receives the forward's (feat_render, feat_real) (``loss_and_network_grads``)."""
         from . import losses as L
         at = _GRAD_DEPTHS.index
         level = at(depth)
@@ -572,8 +619,13 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
         with dec.keeping(depth if depth in KEEP_LEVELS else 'none'):
-            outs = self.get_pose(data['rendered_images'], data['real_images'], data['ref_rotations'],
-                                 data['ref_translations'], data['rendered_depths'], data['internel_k'], labels)
+            pose_args = (data['rendered_images'], data['real_images'], data['ref_rotations'], data['ref_translations'],
+                         data['rendered_depths'], data['internel_k'], labels)
+            if features is None:
+                outs = self.get_pose(*pose_args)
+            else:
+                outs, feats = self._pose_and_features(*pose_args)
+                features.extend(feats)
         flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
         gt_flow = self._supervision(data, self.filter_invalid_flow)
         pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
