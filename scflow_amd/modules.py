@@ -47,14 +47,15 @@ def _lib_error(msg):
 KEEP_LEVELS = ('none', 'pose_tail', 'pose_head', 'decoder_heads', 'gru', 'motion')
 _KEEP = {name: i for i, name in enumerate(KEEP_LEVELS)}
 # how far SCFlowRefiner._loss carries the gradient: every depth does what the ones before it do; from 'head' on the chain is
-# SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  Behind the last depth the
-# context encoder has RAFTEncoder.backward (from grads['gru']['initial_hidden'] and grads['gru']['context'];
-# SCFlowRefiner.loss_and_context_grads), its own switch and no depth of this ladder; so have the correlation build
-# (SCFlowDecoder.corr_backward, from grads['motion']['correlation']) and the feature encoders behind it
-# (RAFTEncoder.in_backward; SCFlowRefiner.loss_and_network_grads).  No backward yet: the path from iteration t into
-# iteration t - 1 under
-# detach_flow=False or under mask_flow / mask_corr without detach_mask (SCFlowDecoder.check_backward refuses it at 'motion')
+# SCFlowDecoder.backward, from 'pose_tail' on the depth is also the keep level its stage reads.  _GRAD_DEPTHS is the
+# decoder's part, seven depths that end at 'motion'; _LOSS_DEPTHS is the whole ladder, nine depths: behind 'motion',
+# 'context' adds the context encoder (RAFTEncoder.backward from grads['gru']['initial_hidden'] and grads['gru']['context'],
+# under its own keeping() switch) and 'network' the correlation build (SCFlowDecoder.corr_backward, from
+# grads['motion']['correlation']) with the feature encoders behind it (RAFTEncoder.in_backward): one walk, two norm kinds.
+# No backward yet: the path from iteration t into iteration t - 1 under detach_flow=False or under mask_flow / mask_corr
+# without detach_mask (SCFlowDecoder.check_backward refuses it from 'motion' on)
 _GRAD_DEPTHS = ('none', 'outputs', 'head') + KEEP_LEVELS[1:]
+_LOSS_DEPTHS = _GRAD_DEPTHS + ('context', 'network')
 
 
 def _kept(what: str, saved, keys: Sequence[str], level: Optional[str]) -> list:
@@ -275,6 +276,68 @@ class _BasicBlock(HipModule):
         return out
 
 
+# What RAFTEncoder._walk_back asks of the norm kind, six closures over one backward's state.  With a layer = (the key of its
+# record, of its convolution, of its norm, the two modules): weight(*layer) -> the weight its dgrad reads (and opens its
+# record); slots(ckey) -> (dw, db, accumulate) of its wgrad; put(*layer, dw, db, **launch): that wgrad's results into grads,
+# the launch's operands into the record; tail(key, G, i, shortcut) -> (conv2's cotangent, the shortcut's) in block i;
+# mid(rkey, g, ukey) -> the cotangent at a raw convolution output from the one behind its norm and ReLU; mask(i, x) -> the
+# ReLU mask of x, the input of block i (the head: the block count), as keywords of the dgrad that produces x's cotangent.
+def _folded_bn_grad(grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+    """BatchNorm on eval statistics: every layer is the folded convolution (W', b'), so a dgrad reads ``bn_fold``'s weight,
+    and (dW', db') are temporaries that ``bn_unfold`` carries to the four raw parameters"""
+    def weight(rkey, ckey, bkey, conv, bn):
+        wf, bf = ops.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+        rec[rkey] = dict(wf=wf, bf=bf)
+        return wf
+
+    def put(rkey, ckey, bkey, conv, bn, dwf, dbf, **launch):
+        ks = [f'{prefix}{ckey}.weight', f'{prefix}{ckey}.bias', f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
+        res = ops.bn_unfold(conv.weight, conv.bias, bn.weight, bn.running_mean, bn.running_var, bn.eps, dwf, dbf,
+                            out=[dst[k] for k in ks], accumulate=acc)
+        grads.update(zip(ks, res))
+        rec[rkey].update(dwf=dwf, dbf=dbf, **launch)
+
+    # nothing sits between the convolution gradients: G is already the cotangent at a block's pre-ReLU sum, which conv2 and
+    # the shortcut both read, because every dgrad masks with its layer's input (the layer in front ends in that ReLU)
+    return (weight, lambda ckey: (None, None, False), put, lambda key, G, i, shortcut: (G, G), lambda rkey, g, ukey: g,
+            lambda i, x: dict(a=x, act=ACT_RELU))
+
+
+def _raw_in_grad(grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+    """InstanceNorm (affine=False): the raw weights, (dW, db) straight into their two ``_grad_slots`` destinations, and
+    ``ops.instance_norm_grad`` between the convolution gradients"""
+    def weight(rkey, ckey, bkey, conv, bn):
+        rec[rkey] = {}
+        return conv.weight
+
+    def slots(ckey):
+        return dst[f'{prefix}{ckey}.weight'], dst[f'{prefix}{ckey}.bias'], acc
+
+    def put(rkey, ckey, bkey, conv, bn, dw, db, **launch):
+        grads[f'{prefix}{ckey}.weight'], grads[f'{prefix}{ckey}.bias'] = dw, db
+        rec[rkey].update(launch)
+
+    def tail(key, G, i, shortcut):
+        # G is the cotangent at the block's OUTPUT y: the tail form masks with y -> g' = G [y > 0], the shortcut's cotangent,
+        # and du2; behind a normalised shortcut (du2, dr)
+        y, u2 = got[f'y{i}'], got[f'u2_{i}']
+        if not shortcut:
+            g_sc, du2 = ops.instance_norm_grad(G, u2, y=y, eps=eps)
+            rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
+        else:
+            du2, g_sc = ops.instance_norm_grad(G, u2, y=y, r=got[f'r{i}'], eps=eps)
+            rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
+        return du2, g_sc
+
+    def mid(rkey, g, ukey):
+        du = ops.instance_norm_grad(g, got[ukey], eps=eps)
+        rec[rkey] = dict(g=g, u=got[ukey], du=du)
+        return du
+
+    # only in front of block 0 the stem's output masks in the epilogue; elsewhere the tail form of the block in front masks
+    return weight, slots, put, tail, mid, lambda i, x: dict(a=x, act=ACT_RELU) if i == 0 else {}
+
+
 @ENCODERS.register_module()
 class RAFTEncoder(HipModule):
     """encoder/raft_encoder.py:13-314, net_type 'Basic' (the SCFlow config):
@@ -371,6 +434,78 @@ class RAFTEncoder(HipModule):
                     kept[f'{k}{i}'] = v
         return kept
 
+    def _saved_for_backward(self, what: str, saved, keys: Sequence[str], nb: int, whose: str) -> Tuple[dict, tuple]:
+        """(the entries ``keys`` of ``saved``, the shape of the head's output behind the last of ``nb`` blocks), or the
+        error that names ``keeping()``; first the refusal of the stem that has no wgrad"""
+        if self.stem_stride != 2:
+            raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
+        try:
+            got = {k: saved[k] for k in keys}
+        except (KeyError, TypeError):
+            raise _lib_error(f"{what}: saved holds {', '.join(keys)}: RAFTEncoder.kept after {whose} under "
+                             'keeping()') from None
+        y_last = got[f'y{nb - 1}']
+        return got, (y_last.shape[0], self.out_channels) + tuple(y_last.shape[2:])
+
+    def _walk_back(self, what: str, norm_grad, got: dict, g_head: Tensor, param_grads: Optional[dict],
+                   intermediates: Optional[dict], prefix: str) -> dict:
+        """The one reverse walk behind ``backward`` and ``in_backward``: the 1x1 head from ``g_head`` (the cotangent at its
+        raw output), the blocks last to first (conv2, conv1, a down-sampling block's shortcut), the stem, on ``got`` (the
+        kept tensors, checked by the caller).  Whatever depends on the norm kind is one of ``norm_grad``'s six closures
+        (``_folded_bn_grad``, ``_raw_in_grad``)."""
+        names = [prefix + k for k, _ in self.named_parameters()]
+        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
+        dst = dict(zip(names, dst))
+        rec = {} if intermediates is None else intermediates
+        tag = self.tag
+        weight, slots, put, tail, mid, mask = norm_grad(grads, dst, acc, rec, prefix, got, getattr(self, tag + '1').eps)
+        i = sum(len(getattr(self, name)) for name in self.res_layers)
+        # ---- head: 1x1, no norm
+        y_last, kw, kb = got[f'y{i - 1}'], f'{prefix}conv2.weight', f'{prefix}conv2.bias'
+        grads[kw], grads[kb] = ops.conv_s1_wgrad(g_head, y_last, (1, 1), dw=dst[kw], db=dst[kb], accumulate=acc)
+        G = ops.conv_s1_dgrad(g_head, self.conv2.weight, **mask(i, y_last))
+        rec['head'] = dict(g=g_head, x=y_last, gx=G)
+        # ---- blocks, last to first
+        for name in reversed(self.res_layers):
+            layer = getattr(self, name)
+            for j in reversed(range(len(layer))):
+                i -= 1
+                blk, key = layer[j], f'{name}.{j}'
+                x_in, t = (got[f'y{i - 1}'] if i else got['stem']), got[f't{i}']
+                g2, g_sc = tail(key, G, i, blk.downsample is not None)
+                c2 = (f'{key}.conv2', f'{key}.conv2', f'{key}.{tag}2', blk.conv2, getattr(blk, tag + '2'))
+                w2 = weight(*c2)
+                dw, db, into = slots(c2[1])
+                dw, db = ops.conv_s1_wgrad(g2, t, (3, 3), dw=dw, db=db, accumulate=into)
+                g_t = ops.conv_s1_dgrad(g2, w2, a=t, act=ACT_RELU)
+                put(*c2, dw, db, g=g2, x=t, gx=g_t)
+                g1 = mid(f'{key}.in1', g_t, f'u1_{i}')
+                c1 = (f'{key}.conv1', f'{key}.conv1', f'{key}.{tag}1', blk.conv1, getattr(blk, tag + '1'))
+                w1 = weight(*c1)
+                dw, db, into = slots(c1[1])
+                if blk.downsample is None:
+                    dw, db = ops.conv_s1_wgrad(g1, x_in, (3, 3), dw=dw, db=db, accumulate=into)
+                    G = ops.conv_s1_dgrad(g1, w1, add=g_sc, **mask(i, x_in))
+                    put(*c1, dw, db, g=g1, x=x_in, add=g_sc, gx=G)
+                else:
+                    in_hw = tuple(x_in.shape[2:])
+                    dw, db = ops.conv_wgrad(g1, x_in, dw=dw, accumulate=into), ops.channel_sum(g1, out=db, accumulate=into)
+                    gx1 = ops.conv_dgrad(g1, w1, in_hw)
+                    put(*c1, dw, db, g=g1, x=x_in, gx=gx1)
+                    ds = (f'{key}.downsample', f'{key}.downsample.0', f'{key}.downsample.1', *blk.downsample)
+                    wd = weight(*ds)
+                    dw, db, into = slots(ds[1])
+                    dw, db = ops.conv_ds_wgrad(g_sc, x_in, dw=dw, db=db, accumulate=into)
+                    G = ops.conv_ds_dgrad(g_sc, wd, in_hw, add=gx1, **mask(i, x_in))
+                    put(*ds, dw, db, g=g_sc, x=x_in, add=gx1, gx=G)
+        # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
+        g0 = mid('in1', G, 'u_stem')
+        rec['conv1'] = {}
+        dw, db, into = slots('conv1')
+        dw, db = ops.conv_stem_wgrad(g0, got['x'], dw=dw, db=db, accumulate=into)
+        put('conv1', 'conv1', tag + '1', self.conv1, getattr(self, tag + '1'), dw, db, g=g0, x=got['x'])
+        return grads
+
     def backward(self, saved: dict, g_out: Union[Tensor, Sequence[Tensor]], out: Optional[Tensor] = None,
                  head_act: int = ACT_NONE, head_act2: int = ACT_NONE, head_split: int = 0,
                  param_grads: Optional[dict] = None, intermediates: Optional[dict] = None, prefix: str = ''):
@@ -398,21 +533,12 @@ class RAFTEncoder(HipModule):
             raise NotImplementedError(f'{what}: this is the BatchNorm chain; the InstanceNorm feature encoder\'s is '
                                       'RAFTEncoder.in_backward, which takes a cotangent at the encoder\'s output -- the '
                                       'correlation-build backward (SCFlowDecoder.corr_backward) produces it')
-        if self.stem_stride != 2:
-            raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
-        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
-        nb = len(blocks)
+        nb = sum(len(getattr(self, name)) for name in self.res_layers)
         keys = ['x', 'stem'] + [f'{k}{i}' for i in range(nb) for k in 'ty'] + ([] if out is not None else ['out'])
-        try:
-            got = {k: saved[k] for k in keys}
-        except (KeyError, TypeError):
-            raise _lib_error(f"{what}: saved holds {', '.join(keys)}: RAFTEncoder.kept after a forward under "
-                             'keeping()') from None
+        got, shape = self._saved_for_backward(what, saved, keys, nb, 'a forward')
         if out is None:
             out = got['out']
-        image, y_last = got['x'], got[f'y{nb - 1}']
-        n, co = y_last.shape[0], self.out_channels
-        shape = (n, co) + tuple(y_last.shape[2:])
+        n, co = shape[:2]
         if tuple(out.shape) != shape:
             raise _lib_error(f'{what}: out must be {shape}, got {tuple(out.shape)}')
         split = int(head_split)
@@ -427,71 +553,11 @@ class RAFTEncoder(HipModule):
         elif len(gs) != len(parts) or any(tuple(g.shape) != (n, b - a) + shape[2:] for g, (a, b, _) in zip(gs, parts)):
             raise _lib_error(f'{what}: g_out is one {shape} tensor or its {len(parts)} channel slices '
                              f'{[(n, b - a) + shape[2:] for a, b, _ in parts]}, got {[tuple(g.shape) for g in gs]}')
-        names = [prefix + k for k, _ in self.named_parameters()]
-        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
-        dst = dict(zip(names, dst))
-        rec = {} if intermediates is None else intermediates
-
-        def folded(key, conv, bn):
-            wf, bf = ops.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-            rec[key] = dict(wf=wf, bf=bf)
-            return wf
-
-        def unfold(key, ckey, bkey, conv, bn, dwf, dbf):
-            ks = [f'{prefix}{ckey}.weight', f'{prefix}{ckey}.bias', f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
-            res = ops.bn_unfold(conv.weight, conv.bias, bn.weight, bn.running_mean, bn.running_var, bn.eps, dwf, dbf,
-                                out=[dst[k] for k in ks], accumulate=acc)
-            grads.update(zip(ks, res))
-            rec[key].update(dwf=dwf, dbf=dbf)
-
-        # ---- head: 1x1, no norm
+        # ---- the head's cotangent: through its activation(s)
         u = torch.empty(shape, dtype=torch.float32, device=out.device)
         for g, (a, b, act) in zip(gs, parts):
             ops.act_grad(g, None if act == ACT_NONE else out[:, a:b], act, out=u[:, a:b])
-        kw, kb = f'{prefix}conv2.weight', f'{prefix}conv2.bias'
-        grads[kw], grads[kb] = ops.conv_s1_wgrad(u, y_last, (1, 1), dw=dst[kw], db=dst[kb], accumulate=acc)
-        G = ops.conv_s1_dgrad(u, self.conv2.weight, a=y_last, act=ACT_RELU)
-        rec['head'] = dict(g=u, x=y_last, gx=G)
-        # ---- blocks, last to first
-        i = nb
-        for name in reversed(self.res_layers):
-            layer = getattr(self, name)
-            for j in reversed(range(len(layer))):
-                i -= 1
-                blk, key = layer[j], f'{name}.{j}'
-                x_in, t = (got[f'y{i - 1}'] if i else got['stem']), got[f't{i}']
-                bn1, bn2 = getattr(blk, blk.tag + '1'), getattr(blk, blk.tag + '2')
-                w2 = folded(f'{key}.conv2', blk.conv2, bn2)
-                dwf, dbf = ops.conv_s1_wgrad(G, t, (3, 3))
-                g_t = ops.conv_s1_dgrad(G, w2, a=t, act=ACT_RELU)
-                unfold(f'{key}.conv2', f'{key}.conv2', f'{key}.{blk.tag}2', blk.conv2, bn2, dwf, dbf)
-                rec[f'{key}.conv2'].update(g=G, x=t, gx=g_t)
-                w1 = folded(f'{key}.conv1', blk.conv1, bn1)
-                if blk.downsample is None:
-                    dwf, dbf = ops.conv_s1_wgrad(g_t, x_in, (3, 3))
-                    g_prev = ops.conv_s1_dgrad(g_t, w1, add=G, a=x_in, act=ACT_RELU)
-                    unfold(f'{key}.conv1', f'{key}.conv1', f'{key}.{blk.tag}1', blk.conv1, bn1, dwf, dbf)
-                    rec[f'{key}.conv1'].update(g=g_t, x=x_in, add=G, gx=g_prev)
-                else:
-                    in_hw = tuple(x_in.shape[2:])
-                    dwf, dbf = ops.conv_wgrad(g_t, x_in), ops.channel_sum(g_t)
-                    gx1 = ops.conv_dgrad(g_t, w1, in_hw)
-                    unfold(f'{key}.conv1', f'{key}.conv1', f'{key}.{blk.tag}1', blk.conv1, bn1, dwf, dbf)
-                    rec[f'{key}.conv1'].update(g=g_t, x=x_in, gx=gx1)
-                    ds, dsn = blk.downsample
-                    wd = folded(f'{key}.downsample', ds, dsn)
-                    dwf, dbf = ops.conv_ds_wgrad(G, x_in)
-                    g_prev = ops.conv_ds_dgrad(G, wd, in_hw, add=gx1, a=x_in, act=ACT_RELU)
-                    unfold(f'{key}.downsample', f'{key}.downsample.0', f'{key}.downsample.1', ds, dsn, dwf, dbf)
-                    rec[f'{key}.downsample'].update(g=G, x=x_in, add=gx1, gx=g_prev)
-                G = g_prev
-        # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
-        n1 = getattr(self, self.tag + '1')
-        rec['conv1'] = {}
-        dwf, dbf = ops.conv_stem_wgrad(G, image)
-        unfold('conv1', 'conv1', self.tag + '1', self.conv1, n1, dwf, dbf)
-        rec['conv1'].update(g=G, x=image)
-        return grads
+        return self._walk_back(what, _folded_bn_grad, got, u, param_grads, intermediates, prefix)
 
     def in_backward(self, saved: dict, g_out: Tensor, param_grads: Optional[dict] = None,
                     intermediates: Optional[dict] = None, prefix: str = ''):
@@ -520,80 +586,14 @@ class RAFTEncoder(HipModule):
         what = 'RAFTEncoder.in_backward'
         if self.kind != 'IN':
             raise NotImplementedError(f'{what}: a BatchNorm encoder takes RAFTEncoder.backward (eval statistics, folded)')
-        if self.stem_stride != 2:
-            raise NotImplementedError(f'{what}: the stride-1 stem (scale 1/4) has no weight gradient')
         blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
-        nb = len(blocks)
-        keys = (['x', 'stem', 'u_stem'] + [f'{k}{i}' for i in range(nb) for k in ('t', 'y', 'u1_', 'u2_')]
+        keys = (['x', 'stem', 'u_stem'] + [f'{k}{i}' for i in range(len(blocks)) for k in ('t', 'y', 'u1_', 'u2_')]
                 + [f'r{i}' for i, blk in enumerate(blocks) if blk.downsample is not None])
-        try:
-            got = {k: saved[k] for k in keys}
-        except (KeyError, TypeError):
-            raise _lib_error(f"{what}: saved holds {', '.join(keys)}: RAFTEncoder.kept after an InstanceNorm encoder's "
-                             'forward under keeping()') from None
-        image, y_last = got['x'], got[f'y{nb - 1}']
-        shape = (y_last.shape[0], self.out_channels) + tuple(y_last.shape[2:])
+        got, shape = self._saved_for_backward(what, saved, keys, len(blocks), "an InstanceNorm encoder's forward")
         if not isinstance(g_out, torch.Tensor) or tuple(g_out.shape) != shape:
             raise _lib_error(f'{what}: g_out must be a {shape} tensor, got '
                              f'{tuple(g_out.shape) if isinstance(g_out, torch.Tensor) else type(g_out).__name__}')
-        names = [prefix + k for k, _ in self.named_parameters()]
-        grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
-        dst = dict(zip(names, dst))
-        rec = {} if intermediates is None else intermediates
-        eps = getattr(self, self.tag + '1').eps
-
-        def put(key, dw, db):
-            grads[f'{prefix}{key}.weight'], grads[f'{prefix}{key}.bias'] = dw, db
-
-        def slots(key):
-            return dict(dw=dst[f'{prefix}{key}.weight'], db=dst[f'{prefix}{key}.bias'], accumulate=acc)
-
-        # ---- head: 1x1, no norm, no activation
-        put('conv2', *ops.conv_s1_wgrad(g_out, y_last, (1, 1), **slots('conv2')))
-        G = ops.conv_s1_dgrad(g_out, self.conv2.weight)
-        rec['head'] = dict(g=g_out, x=y_last, gx=G)
-        # ---- blocks, last to first
-        i = nb
-        for name in reversed(self.res_layers):
-            layer = getattr(self, name)
-            for j in reversed(range(len(layer))):
-                i -= 1
-                blk, key = layer[j], f'{name}.{j}'
-                x_in, t, y = (got[f'y{i - 1}'] if i else got['stem']), got[f't{i}'], got[f'y{i}']
-                u1, u2 = got[f'u1_{i}'], got[f'u2_{i}']
-                if blk.downsample is None:
-                    g_sc, du2 = ops.instance_norm_grad(G, u2, y=y, eps=eps)
-                    rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
-                else:
-                    du2, dr = ops.instance_norm_grad(G, u2, y=y, r=got[f'r{i}'], eps=eps)
-                    rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=dr)
-                put(f'{key}.conv2', *ops.conv_s1_wgrad(du2, t, (3, 3), **slots(f'{key}.conv2')))
-                g_t = ops.conv_s1_dgrad(du2, blk.conv2.weight, a=t, act=ACT_RELU)
-                rec[f'{key}.conv2'] = dict(g=du2, x=t, gx=g_t)
-                du1 = ops.instance_norm_grad(g_t, u1, eps=eps)
-                rec[f'{key}.in1'] = dict(g=g_t, u=u1, du=du1)
-                if blk.downsample is None:
-                    put(f'{key}.conv1', *ops.conv_s1_wgrad(du1, x_in, (3, 3), **slots(f'{key}.conv1')))
-                    mask = dict(a=x_in, act=ACT_RELU) if i == 0 else {}
-                    g_prev = ops.conv_s1_dgrad(du1, blk.conv1.weight, add=g_sc, **mask)
-                    rec[f'{key}.conv1'] = dict(g=du1, x=x_in, add=g_sc, gx=g_prev)
-                else:
-                    in_hw = tuple(x_in.shape[2:])
-                    s = slots(f'{key}.conv1')
-                    put(f'{key}.conv1', ops.conv_wgrad(du1, x_in, dw=s['dw'], accumulate=acc),
-                        ops.channel_sum(du1, out=s['db'], accumulate=acc))
-                    gx1 = ops.conv_dgrad(du1, blk.conv1.weight, in_hw)
-                    rec[f'{key}.conv1'] = dict(g=du1, x=x_in, gx=gx1)
-                    put(f'{key}.downsample.0', *ops.conv_ds_wgrad(dr, x_in, **slots(f'{key}.downsample.0')))
-                    g_prev = ops.conv_ds_dgrad(dr, blk.downsample[0].weight, in_hw, add=gx1)
-                    rec[f'{key}.downsample'] = dict(g=dr, x=x_in, add=gx1, gx=g_prev)
-                G = g_prev
-        # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
-        du = ops.instance_norm_grad(G, got['u_stem'], eps=eps)
-        rec['in1'] = dict(g=G, u=got['u_stem'], du=du)
-        put('conv1', *ops.conv_stem_wgrad(du, image, **slots('conv1')))
-        rec['conv1'] = dict(g=du, x=image)
-        return grads
+        return self._walk_back(what, _raw_in_grad, got, g_out, param_grads, intermediates, prefix)   # the head has no activation
 
 
 def encoder_pair_supported(fe: 'RAFTEncoder', ce: 'RAFTEncoder') -> bool:
@@ -1539,9 +1539,10 @@ class SCFlowDecoder(HipModule):
         self.kept['tail_inputs'].append(ys[2].clone() if clone else ys[2])
 
     def check_backward(self, depth: str) -> None:
-        """refuse, before any launch, what ``backward(depth, ...)`` cannot carry: at ``'motion'`` a configuration in which
-        something flows from ``x_t`` back into iteration t - 1; the depths before it refuse nothing"""
-        if _GRAD_DEPTHS.index(depth) < _GRAD_DEPTHS.index('motion'):
+        """refuse, before any launch, what ``backward(depth, ...)`` cannot carry: at ``'motion'`` (and the two depths of
+        ``_LOSS_DEPTHS`` behind it) a configuration in which something flows from ``x_t`` back into iteration t - 1; the
+        depths before it refuse nothing"""
+        if _LOSS_DEPTHS.index(depth) < _LOSS_DEPTHS.index('motion'):
             return
         if not self.detach_flow:
             raise NotImplementedError('loss_and_motion_grads: detach_flow=False needs the path from flow_lr of iteration t into '

@@ -2282,12 +2282,17 @@ def conv_dgrad(g: Tensor, weight: Tensor, in_hw: Tuple[int, int], split: Optiona
     return gx0 if split is None else (gx0, gx1)
 
 
+def _workspace_floats(query: str, *sizes: int) -> int:
+    """what the library's ``scf_<query>`` answers for ``sizes``; a negative answer is its refusal of them"""
+    n = int(getattr(_lib.load(), 'scf_' + query)(*sizes))
+    if n < 0:
+        raise _lib.ScflowHipError(f'{query}: invalid sizes {sizes}')
+    return n
+
+
 def conv_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
     """floats of workspace ``conv_wgrad`` needs (``scf_conv_wgrad_workspace``)."""
-    n = int(_lib.load().scf_conv_wgrad_workspace(m, cout, cin, ho, wo))
-    if n < 0:
-        raise _lib.ScflowHipError(f'conv_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
-    return n
+    return _workspace_floats('conv_wgrad_workspace', m, cout, cin, ho, wo)
 
 
 def conv_wgrad(g: Tensor, x0: Tensor, x1: Optional[Tensor] = None, dw: Optional[Tensor] = None, accumulate: bool = False,
@@ -2308,12 +2313,7 @@ def conv_wgrad(g: Tensor, x0: Tensor, x1: Optional[Tensor] = None, dw: Optional[
     _, cout, ho, wo, _, _, _ = _conv_grad_geometry(what, g, (g.shape[1], cin, kernel_size, kernel_size), (hin, win), stride,
                                                    padding)
     dw = _fc_grad_out(dw, (cout, cin, 3, 3), g, what, 'dw', accumulate)
-    need = conv_wgrad_workspace(m, cout, cin, ho, wo)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.float32, device=g.device)
-    _dev(workspace, f'{what}: workspace')
-    if not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.ScflowHipError(f'{what}: workspace must be contiguous with at least {need} floats, got {workspace.numel()}')
+    workspace = _grad_workspace(what, workspace, conv_wgrad_workspace(m, cout, cin, ho, wo), g)
     _lib.check(_lib.load().scf_conv_wgrad(g.data_ptr(), x0.data_ptr(), c0, None if x1 is None else x1.data_ptr(), c1,
                                           dw.data_ptr(), int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m,
                                           cout, ho, wo, hin, win, 3, 3, stride, padding, _stream()), 'scf_conv_wgrad')
@@ -2404,10 +2404,7 @@ def conv_s1_dgrad(g: Tensor, weight: Tensor, add: Optional[Tensor] = None, a: Op
 
 def conv_s1_wgrad_workspace(m: int, cout: int, cin: int, h: int, w: int, kh: int, kw: int) -> int:
     """floats of workspace ``conv_s1_wgrad`` needs (``scf_conv_s1_wgrad_workspace``)."""
-    n = int(_lib.load().scf_conv_s1_wgrad_workspace(m, cout, cin, h, w, kh, kw))
-    if n < 0:
-        raise _lib.ScflowHipError(f'conv_s1_wgrad_workspace: invalid sizes {(m, cout, cin, h, w, kh, kw)}')
-    return n
+    return _workspace_floats('conv_s1_wgrad_workspace', m, cout, cin, h, w, kh, kw)
 
 
 def conv_s1_wgrad(g: Tensor, x: Tensor, kernel_size, dw: Optional[Tensor] = None, db: Optional[Tensor] = None,
@@ -2430,12 +2427,7 @@ def conv_s1_wgrad(g: Tensor, x: Tensor, kernel_size, dw: Optional[Tensor] = None
     dw = _fc_grad_out(dw, (cout, cin, kh, kw), g, what, 'dw', accumulate)
     if bias or db is not None:
         db = _fc_grad_out(db, (cout,), g, what, 'db', accumulate)
-    need = conv_s1_wgrad_workspace(m, cout, cin, h, w, kh, kw)
-    if workspace is None:
-        workspace = torch.empty((need,), dtype=torch.float32, device=g.device)
-    _dev(workspace, f'{what}: workspace')
-    if not workspace.is_contiguous() or workspace.numel() < need:
-        raise _lib.ScflowHipError(f'{what}: workspace must be contiguous with at least {need} floats, got {workspace.numel()}')
+    workspace = _grad_workspace(what, workspace, conv_s1_wgrad_workspace(m, cout, cin, h, w, kh, kw), g)
     _lib.check(_lib.load().scf_conv_s1_wgrad(pg, gs, px, xs, dw.data_ptr(), None if db is None else db.data_ptr(),
                                              int(bool(accumulate)), workspace.data_ptr(), workspace.numel(), m, cout, cin,
                                              h, w, kh, kw, _stream()), 'scf_conv_s1_wgrad')
@@ -2451,8 +2443,6 @@ def _half_map(what: str, g: Tensor, x_shape) -> None:
 
 
 def _grad_workspace(what: str, workspace: Optional[Tensor], need: int, like: Tensor) -> Tensor:
-    if need < 0:
-        raise _lib.ScflowHipError(f'{what}: invalid sizes')
     if workspace is None:
         workspace = torch.empty((need,), dtype=torch.float32, device=like.device)
     _dev(workspace, f'{what}: workspace')
@@ -2463,10 +2453,7 @@ def _grad_workspace(what: str, workspace: Optional[Tensor], need: int, like: Ten
 
 def conv_stem_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
     """floats of workspace ``conv_stem_wgrad`` needs (``scf_conv_stem_wgrad_workspace``)."""
-    n = int(_lib.load().scf_conv_stem_wgrad_workspace(m, cout, cin, ho, wo))
-    if n < 0:
-        raise _lib.ScflowHipError(f'conv_stem_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
-    return n
+    return _workspace_floats('conv_stem_wgrad_workspace', m, cout, cin, ho, wo)
 
 
 def conv_stem_wgrad(g: Tensor, x: Tensor, dw: Optional[Tensor] = None, db: Optional[Tensor] = None, bias: bool = True,
@@ -2526,10 +2513,7 @@ def conv_ds_dgrad(g: Tensor, weight: Tensor, in_hw: Tuple[int, int], add: Option
 
 def conv_ds_wgrad_workspace(m: int, cout: int, cin: int, ho: int, wo: int) -> int:
     """floats of workspace ``conv_ds_wgrad`` needs (``scf_conv_ds_wgrad_workspace``)."""
-    n = int(_lib.load().scf_conv_ds_wgrad_workspace(m, cout, cin, ho, wo))
-    if n < 0:
-        raise _lib.ScflowHipError(f'conv_ds_wgrad_workspace: invalid sizes {(m, cout, cin, ho, wo)}')
-    return n
+    return _workspace_floats('conv_ds_wgrad_workspace', m, cout, cin, ho, wo)
 
 
 def conv_ds_wgrad(g: Tensor, x: Tensor, dw: Optional[Tensor] = None, db: Optional[Tensor] = None, bias: bool = True,
@@ -2557,10 +2541,7 @@ def conv_ds_wgrad(g: Tensor, x: Tensor, dw: Optional[Tensor] = None, db: Optiona
 
 def channel_sum_workspace(m: int, c: int, n: int) -> int:
     """floats of workspace ``channel_sum`` needs (``scf_channel_sum_workspace``)."""
-    k = int(_lib.load().scf_channel_sum_workspace(m, c, n))
-    if k < 0:
-        raise _lib.ScflowHipError(f'channel_sum_workspace: invalid sizes {(m, c, n)}')
-    return k
+    return _workspace_floats('channel_sum_workspace', m, c, n)
 
 
 def channel_sum(g: Tensor, out: Optional[Tensor] = None, accumulate: bool = False,

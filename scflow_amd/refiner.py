@@ -9,7 +9,7 @@ keys.  PnP re-mapping is outside the hot path, and
 ``BaseRefiner.format_data_test`` produces, base_refiner.py:79-133).  The loss
 configs are kept as given and built at the first ``loss()`` call (scflow_amd/losses.py):
 ``loss()`` returns the forward VALUES the reference trains against, ``loss_and_grads()`` adds their gradients at
-the network's outputs, the ``loss_and_*_grads()`` ladder carries them through the decoder (``_GRAD_DEPTHS``) and
+the network's outputs, the ``loss_and_*_grads()`` ladder (``_LOSS_DEPTHS``, nine depths) carries them through the decoder,
 ``loss_and_context_grads()`` through the context encoder, ``loss_and_network_grads()`` through the correlation build and
 the feature encoders to every parameter of the network.
 ``train_step()`` applies those gradients with ``scflow_amd.optim.AdamW`` (the reference's ``freeze_encoder=True,
@@ -26,7 +26,7 @@ from typing import Dict, Optional, Tuple, Union
 import torch
 
 from . import ops
-from .modules import _GRAD_DEPTHS, KEEP_LEVELS, HipModule, encoder_pair_supported, raft_encoder_pair
+from .modules import _GRAD_DEPTHS, _LOSS_DEPTHS, KEEP_LEVELS, HipModule, encoder_pair_supported, raft_encoder_pair  # noqa: F401
 from .ops import ACT_RELU, ACT_TANH, small_work
 from .registry import REFINERS, build_decoder, build_encoder
 
@@ -333,13 +333,13 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         """scflow_refiner.py:112-142 -> 7-tuple of length-``iters`` lists
         (flow_from_pose, flow_from_pred, rotation_preds, translation_preds, mask_preds,
         delta_rotation_preds, delta_translation_preds)."""
-        return self._pose_and_features(render_images, real_images, ref_rotation, ref_translation, depth, internel_k, label,
-                                       init_flow)[0]
+        return self._pose_and_feats(render_images, real_images, ref_rotation, ref_translation, depth, internel_k, label,
+                                    init_flow)[0]
 
-    def _pose_and_features(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor, ref_translation: Tensor,
-                           depth: Tensor, internel_k: Tensor, label: Tensor, init_flow: Optional[Tensor] = None):
-        """``get_pose`` -> (its 7-tuple, (feat_render, feat_real)): the two feature maps of this forward for
-        ``loss_and_network_grads``.  The decoder only reads them (``corr_block``), so references are enough."""
+    def _pose_and_feats(self, render_images: Tensor, real_images: Tensor, ref_rotation: Tensor, ref_translation: Tensor,
+                        depth: Tensor, internel_k: Tensor, label: Tensor, init_flow: Optional[Tensor] = None):
+        """``get_pose`` -> (its 7-tuple, (feat_render, feat_real)): the two feature maps of this forward for the
+        ``'network'`` depth of ``_loss``.  The decoder only reads them (``corr_block``), so references are enough."""
         feat_render, feat_real, h_feat, cxt_feat = self.extract_feat(render_images, real_images)
         if init_flow is None:
             n, _, H, W = real_images.shape
@@ -388,7 +388,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         way to call this without an attached renderer; it needs ``gt_masks`` when ``filter_invalid_flow`` is set."""
         return self._loss(data_batch, data, 'none')
 
-    # loss_and_*_grads(): one method per rung of _GRAD_DEPTHS (modules.py, where what has no backward yet is stated once).
+    # loss_and_*_grads(): one method per rung of _LOSS_DEPTHS (modules.py, where what has no backward yet is stated once).
     # Every one returns (loss, None, log_vars, seq_rotations, seq_translations, grads); the values are the bits of loss(),
     # log_vars still costs one transfer, and from 'head' on every entry the rung before returns keeps its key and its bits.
     def loss_and_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
@@ -454,25 +454,14 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         through the mask, a reverse scan over whole iterations: NotImplementedError (``SCFlowDecoder.check_backward``)."""
         return self._loss(data_batch, data, 'motion')
 
-    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None, _host_log: bool = True,
-                               _features: Optional[list] = None):
+    def loss_and_context_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
         """``loss_and_motion_grads()`` (its keys, values and bits, and its refusals) with the context encoder behind it
         (``RAFTEncoder.backward`` from ``gru['initial_hidden']`` and ``gru['context']``, complete only at that rung):
         ``params`` is extended by the 62 ``context.*`` gradients, BatchNorm with running statistics as the forward
         computes it (the reference's ``freeze_bn=True``).  Every parameter of the network except the feature encoder's
         now has a gradient: the reference's ``freeze_encoder=True`` training case.  The context encoder keeps its
         activations during this forward (``RAFTEncoder.keeping``) and drops them before returning."""
-        ctx = self.context
-        try:
-            with ctx.keeping():
-                out = self._loss(data_batch, data, 'motion', _host_log, _features)
-            grads = out[-1]
-            grads['params'].update(ctx.backward(
-                ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
-                head_act2=ACT_RELU, head_split=self.h_channels, prefix='context.'))
-        finally:
-            ctx.kept = {}
-        return out
+        return self._loss(data_batch, data, 'context')
 
     def loss_and_network_grads(self, data_batch: Optional[Dict], data: Optional[Dict] = None):
         """``loss_and_context_grads()`` (its keys, values and bits, and its refusals) with the correlation build and the
@@ -484,30 +473,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         32 + 32 (``render_encoder.*``, ``real_encoder.*``): ``params`` then covers all of ``named_parameters()``, and
         ``scflow_amd.optim.AdamW(list(model.named_parameters()))`` steps the whole network from it.  The encoders keep
         their activations during this forward and everything kept is dropped before returning, also on an error."""
-        fe, re_ = self.render_encoder, self.real_encoder
-        held = []                                   # receives (feat_render, feat_real) of the rung's own forward
-        try:
-            with contextlib.ExitStack() as stack:
-                stack.enter_context(fe.keeping())
-                if self.seperate_encoder:
-                    stack.enter_context(re_.keeping())
-                out = self.loss_and_context_grads(data_batch, data, _features=held)
-            grads = out[-1]
-            feat_render, feat_real = held
-            n = feat_render.shape[0]
-            both = torch.empty((2 * n,) + tuple(feat_render.shape[1:]), dtype=torch.float32, device=feat_render.device)
-            g_render, g_real = self.decoder.corr_backward(feat_render, feat_real, grads['motion']['correlation'],
-                                                          out=(both[:n], both[n:]))
-            grads['features'] = dict(render=g_render, real=g_real)
-            if not self.seperate_encoder:
-                enc = fe.in_backward(fe.kept, both, prefix='render_encoder.')
-            else:
-                enc = fe.in_backward(fe.kept, g_render, prefix='render_encoder.')
-                enc = re_.in_backward(re_.kept, g_real, param_grads=enc, prefix='real_encoder.')
-            grads['params'].update(enc)
-        finally:
-            fe.kept, re_.kept = {}, {}
-        return out
+        return self._loss(data_batch, data, 'network')
 
     def feature_grads(self, g_render_feat: Tensor, g_real_feat: Tensor, param_grads: Optional[dict] = None) -> dict:
         """The feature encoders' parameter gradients from the cotangents at ``extract_feat``'s (render_feat, real_feat),
@@ -529,13 +495,21 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             if g_render_feat.shape != g_real_feat.shape or g_render_feat.dim() != 4:
                 raise ops._lib.ScflowHipError(f'{what}: the two cotangents are (N, C, h, w) tensors of one shape, got '
                                               f'{tuple(g_render_feat.shape)} and {tuple(g_real_feat.shape)}')
-            if not self.seperate_encoder:
-                return fe.in_backward(fe.kept, torch.cat((g_render_feat, g_real_feat)), param_grads=param_grads,
-                                      prefix='render_encoder.')
-            grads = fe.in_backward(fe.kept, g_render_feat.contiguous(), param_grads=param_grads, prefix='render_encoder.')
-            return re_.in_backward(re_.kept, g_real_feat.contiguous(), param_grads=grads, prefix='real_encoder.')
+            return self._feature_backward(g_render_feat, g_real_feat, param_grads=param_grads)
         finally:
             fe.kept, re_.kept = {}, {}
+
+    def _feature_backward(self, g_render: Tensor, g_real: Tensor, stacked: Optional[Tensor] = None,
+                          param_grads: Optional[dict] = None) -> dict:
+        """``RAFTEncoder.in_backward`` on what the feature encoder(s) kept.  Shared encoder: one pass under
+        ``render_encoder.`` over ``stacked``, the (2N, ...) buffer the two cotangents are the halves of (None: a copy that
+        stacks them).  Separate encoders: two passes, the second accumulating into the first's dict under ``real_encoder.``"""
+        fe, re_ = self.render_encoder, self.real_encoder
+        if not self.seperate_encoder:
+            return fe.in_backward(fe.kept, torch.cat((g_render, g_real)) if stacked is None else stacked,
+                                  param_grads=param_grads, prefix='render_encoder.')
+        grads = fe.in_backward(fe.kept, g_render.contiguous(), param_grads=param_grads, prefix='render_encoder.')
+        return re_.in_backward(re_.kept, g_real.contiguous(), param_grads=grads, prefix='real_encoder.')
 
     # ------------------------------------------------------------------ training
     def trainable_parameters(self):
@@ -587,7 +561,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             else len(data['real_images'])
         named = []
         for i in range(cycles):
-            loss, _, log, seq_r, seq_t, grads = self.loss_and_context_grads(data_batch, data=data, _host_log=False)
+            loss, _, log, seq_r, seq_t, grads = self._loss(data_batch, data, 'context', host_log=False)
             norm = optimizer.step(grads['params'], end_of_iteration=i == cycles - 1)
             if optimizer.model is not self:
                 self.invalidate_packed()
@@ -604,67 +578,89 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         log_vars['lr'] = optimizer.lr
         return dict(loss=loss, log_vars=log_vars, log_imgs=None, num_samples=num_samples)
 
-    def _loss(self, data_batch, data, depth, host_log=True, features=None):
-        """``host_log=False`` (train_step): ``log_vars`` stays the list of (key, 0-dim GPU tensor) it is made from, so that
-        the caller can add its own entries and still make ONE device-to-host transfer (``_log_vars``).  ``features``: a
-        list that receives the forward's (feat_render, feat_real) (``loss_and_network_grads``)."""
+    def _loss(self, data_batch, data, depth, host_log=True):
+        """The ladder, to the rung ``depth`` of ``_LOSS_DEPTHS``: the only place that knows its order.  ``host_log=False``
+        (train_step): ``log_vars`` stays the list of (key, 0-dim GPU tensor) it is made from, so that the caller can add
+        its own entries and still make ONE device-to-host transfer (``_log_vars``)."""
         from . import losses as L
-        at = _GRAD_DEPTHS.index
+        at = _LOSS_DEPTHS.index
         level = at(depth)
         with_grads = level >= at('outputs')
-        dec = self.decoder
+        dec, ctx = self.decoder, self.context
+        dec_depth = _LOSS_DEPTHS[min(level, at('motion'))]           # the decoder's part of the ladder ends there
         dec.check_backward(depth)
         self._build_loss_funcs()
         if data is None:
             data = self.format_data_train_sup(data_batch)
         labels, valid = data['labels'], data['rendered_masks']
-        with dec.keeping(depth if depth in KEEP_LEVELS else 'none'):
-            pose_args = (data['rendered_images'], data['real_images'], data['ref_rotations'], data['ref_translations'],
-                         data['rendered_depths'], data['internel_k'], labels)
-            if features is None:
-                outs = self.get_pose(*pose_args)
+        # the encoders behind the decoder keep their activations during the forward, each under its own switch
+        keepers = [ctx] if level >= at('context') else []
+        if level >= at('network'):
+            keepers += [self.render_encoder, self.real_encoder] if self.seperate_encoder else [self.render_encoder]
+        try:
+            with contextlib.ExitStack() as stack:
+                for enc in keepers:
+                    stack.enter_context(enc.keeping())
+                stack.enter_context(dec.keeping(dec_depth if dec_depth in KEEP_LEVELS else 'none'))
+                pose_args = (data['rendered_images'], data['real_images'], data['ref_rotations'], data['ref_translations'],
+                             data['rendered_depths'], data['internel_k'], labels)
+                if level >= at('network'):          # the correlation-build backward reads this forward's two feature maps
+                    outs, (feat_render, feat_real) = self._pose_and_feats(*pose_args)
+                else:
+                    outs = self.get_pose(*pose_args)
+            flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
+            gt_flow = self._supervision(data, self.filter_invalid_flow)
+            pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
+            if pose_is_flow:
+                (flow_out, pose_out), mask_out = self._pixel_losses(
+                    gt_flow, valid, [self.flow_loss_func, self.pose_loss_func], [flow_from_pred, flow_from_pose],
+                    self.mask_loss_func, sequence_masks, with_grads)
             else:
-                outs, feats = self._pose_and_features(*pose_args)
-                features.extend(feats)
-        flow_from_pose, flow_from_pred, seq_rotations, seq_translations, sequence_masks = outs[:5]
-        gt_flow = self._supervision(data, self.filter_invalid_flow)
-        pose_is_flow = isinstance(getattr(self.pose_loss_func, 'loss_func', None), L.RAFTLoss)
-        if pose_is_flow:
-            (flow_out, pose_out), mask_out = self._pixel_losses(
-                gt_flow, valid, [self.flow_loss_func, self.pose_loss_func], [flow_from_pred, flow_from_pose],
-                self.mask_loss_func, sequence_masks, with_grads)
-        else:
-            pose_call = self.pose_loss_func.value_and_grad if with_grads else self.pose_loss_func
-            pose_out = pose_call(seq_rotations, seq_translations, gt_r=data['gt_rotations'],
-                                 gt_t=data['gt_translations'], labels=labels,
-                                 scale_factors=self._scale_factors(data, data_batch, gt_flow.device))
-            (flow_out,), mask_out = self._pixel_losses(gt_flow, valid, [self.flow_loss_func], [flow_from_pred],
-                                                       self.mask_loss_func, sequence_masks, with_grads)
-        (loss_pose, seq_pose), (loss_flow, seq_flow), (loss_mask, seq_mask) = pose_out[:2], flow_out[:2], mask_out[:2]
-        loss = loss_pose + loss_flow + loss_mask
-        named = []
-        if 'init_add_error_mean' in data:
-            named += [('init_add_mean', data['init_add_error_mean']), ('init_add_std', data['init_add_error_std'])]
-        for i in range(len(seq_flow)):
-            named += [(f'seq_{i}_pose_loss', seq_pose[i]), (f'seq_{i}_flow_loss', seq_flow[i]),
-                      (f'seq_{i}_mask_loss', seq_mask[i])]
-        named += [('loss_mask', loss_mask), ('loss_flow', loss_flow), ('loss_pose', loss_pose), ('loss', loss)]
-        out = (loss, None, self._log_vars(named) if host_log else named, seq_rotations, seq_translations)
-        if not with_grads:
-            return out
-        grads = dict(sequence_flow_from_pred=flow_out[2], sequence_masks=mask_out[2])
-        if pose_is_flow:
-            grads['sequence_flow_from_pose'] = pose_out[2]
-        else:
-            grads['seq_rotations'] = pose_out[2][0]
-            if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
-                grads['seq_translations'] = pose_out[2][1]
-        if level >= at('head'):
-            grads = dec.backward(depth, outs, grads, labels, data['ref_rotations'], data['ref_translations'],
-                                 data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
-        if 'params' in grads:
-            grads['params'] = {'decoder.' + key: val for key, val in grads['params'].items()}
-        return out + (grads,)
+                pose_call = self.pose_loss_func.value_and_grad if with_grads else self.pose_loss_func
+                pose_out = pose_call(seq_rotations, seq_translations, gt_r=data['gt_rotations'],
+                                     gt_t=data['gt_translations'], labels=labels,
+                                     scale_factors=self._scale_factors(data, data_batch, gt_flow.device))
+                (flow_out,), mask_out = self._pixel_losses(gt_flow, valid, [self.flow_loss_func], [flow_from_pred],
+                                                           self.mask_loss_func, sequence_masks, with_grads)
+            (loss_pose, seq_pose), (loss_flow, seq_flow), (loss_mask, seq_mask) = pose_out[:2], flow_out[:2], mask_out[:2]
+            loss = loss_pose + loss_flow + loss_mask
+            named = []
+            if 'init_add_error_mean' in data:
+                named += [('init_add_mean', data['init_add_error_mean']), ('init_add_std', data['init_add_error_std'])]
+            for i in range(len(seq_flow)):
+                named += [(f'seq_{i}_pose_loss', seq_pose[i]), (f'seq_{i}_flow_loss', seq_flow[i]),
+                          (f'seq_{i}_mask_loss', seq_mask[i])]
+            named += [('loss_mask', loss_mask), ('loss_flow', loss_flow), ('loss_pose', loss_pose), ('loss', loss)]
+            out = (loss, None, self._log_vars(named) if host_log else named, seq_rotations, seq_translations)
+            if not with_grads:
+                return out
+            grads = dict(sequence_flow_from_pred=flow_out[2], sequence_masks=mask_out[2])
+            if pose_is_flow:
+                grads['sequence_flow_from_pose'] = pose_out[2]
+            else:
+                grads['seq_rotations'] = pose_out[2][0]
+                if len(pose_out[2]) > 1 and pose_out[2][1] is not None:
+                    grads['seq_translations'] = pose_out[2][1]
+            if level >= at('head'):
+                grads = dec.backward(dec_depth, outs, grads, labels, data['ref_rotations'], data['ref_translations'],
+                                     data['rendered_depths'].contiguous(), data['internel_k'].contiguous())
+            if 'params' in grads:
+                grads['params'] = {'decoder.' + key: val for key, val in grads['params'].items()}
+            if level >= at('context'):
+                grads['params'].update(ctx.backward(
+                    ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
+                    head_act2=ACT_RELU, head_split=self.h_channels, prefix='context.'))
+            if level >= at('network'):
+                n = feat_render.shape[0]
+                both = torch.empty((2 * n,) + tuple(feat_render.shape[1:]), dtype=torch.float32, device=feat_render.device)
+                g_render, g_real = dec.corr_backward(feat_render, feat_real, grads['motion']['correlation'],
+                                                     out=(both[:n], both[n:]))
+                grads['features'] = dict(render=g_render, real=g_real)
+                grads['params'].update(self._feature_backward(g_render, g_real, stacked=both))
+            return out + (grads,)
+        finally:
+            for enc in keepers:                     # what an encoder kept is dropped before returning, also on an error
+                enc.kept = {}
 
     def forward(self, data, data_batch=None, return_loss=False):
         if return_loss:

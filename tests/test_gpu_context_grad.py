@@ -335,6 +335,9 @@ def test_encoder_backward_launch_by_launch(hw, n):
     grads = enc.backward(saved, D(g), **HEAD, intermediates=im)
     assert list(grads) and sorted(grads) == sorted(dict(enc.named_parameters())) and len(grads) == 62
     assert all(grads[k].shape == v.shape for k, v in enc.named_parameters())
+    # the records come in launch order: the head, the blocks last to first (conv2, conv1, the shortcut), the stem
+    assert list(im) == ['head'] + [f'res_layer{L}.{j}.{c}' for L in (3, 2, 1) for j in (1, 0)
+                                   for c in ('conv2', 'conv1') + (('downsample',) if j == 0 and L > 1 else ())] + ['conv1']
     for kind, v in sorted(check_launches(enc, im, grads).items()):
         measured(f'RAFTEncoder.backward {hw} N {n}, {kind}: worst error / bound', v)
         assert v <= 1.0, kind

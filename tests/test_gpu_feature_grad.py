@@ -205,6 +205,10 @@ def test_in_backward_launch_by_launch(hw, n):
     grads = enc.in_backward(saved, D(g), intermediates=im)
     assert sorted(grads) == sorted(dict(enc.named_parameters())) and len(grads) == 32
     assert all(grads[k].shape == v.shape for k, v in enc.named_parameters())
+    # the records come in launch order: the head, the blocks last to first (each norm in front of its convolution), the stem
+    assert list(im) == ['head'] + [f'res_layer{L}.{j}.{c}' for L in (3, 2, 1) for j in (1, 0)
+                                   for c in ('in2', 'conv2', 'in1', 'conv1') + (('downsample',) if j == 0 and L > 1 else ())
+                                   ] + ['in1', 'conv1']
     v = check_launches(im)
     measured(f'RAFTEncoder.in_backward {hw} N {n}, the InstanceNorm launches: worst error / bound', v)
     assert v <= 1.0
