@@ -7,13 +7,14 @@ import torch
 import torch.nn.functional as F
 from scflow_amd import ops
 DEV = 'cuda:0'
-def run(cases: int, seed: int, verbose: bool = True) -> int:
-    """-> number of failing cases"""
+def run(cases: int, seed: int, verbose: bool = True, stats: dict = None) -> int:
+    """-> number of failing cases.  ``stats`` (a dict, optional) receives 'families' (launches per kernel family) and 'worst'
+    (the largest err / limit over the cases that ran)."""
     _print = print if verbose else (lambda *a, **k: None)
     rs = random.Random(seed)
     torch.set_num_threads(16)
     KS = [((1, 1), (0, 0)), ((3, 3), (1, 1)), ((3, 3), (1, 1)), ((1, 5), (0, 2)), ((5, 1), (2, 0)), ((7, 7), (3, 3)), ((5, 5), (2, 2)), ((3, 3), (0, 0)), ((3, 1), (1, 0))]
-    bad, fam = 0, {}
+    bad, fam, worst = 0, {}, 0.0
     for ci in range(cases):
         k, p = rs.choice(KS)
         stride = rs.choice([1, 1, 1, 2])
@@ -68,10 +69,13 @@ def run(cases: int, seed: int, verbose: bool = True) -> int:
         err = float((got.cpu().double() - want).abs().max())
         lim = 40 * 1.19e-7 * max(scale, 1.0) + 1e-6
         ok = err <= lim and bool(torch.isfinite(got).all())
+        worst = max(worst, err / lim) if err == err else float('inf')
         if not ok:
             bad += 1
         print(f'{"ok  " if ok else "FAIL"} {tag} [{name}] err {err:.2e} (limit {lim:.2e})', flush=True)
     print('families:', fam)
+    if stats is not None:
+        stats['families'], stats['worst'] = dict(fam), worst
     print('FUZZ', 'FAILED' if bad else 'ok', bad, 'of', cases)
     return bad
 
