@@ -1114,6 +1114,52 @@ int scf_instance_norm_res_norm_grad(const float* g, const float* y, const float*
                                     int64_t planes, int HW, float eps, scf_stream_t stream);
 
 /* ---------------------------------------------------------------------------------
+ * BatchNorm2d on the statistics of the batch, forward and backward (batch_norm_train.hip): affine, eps inside the root,
+ * biased variance for normalising, unbiased (x M / (M - 1)) for the running estimate, M = N HW values per channel -- the
+ * context encoder under freeze_bn=False.  u, res / r, y, g, gp, du, dr are (N, C, HW) dense; gamma, beta, the running
+ * statistics and dgamma, dbeta are (C,); saved is (2, C): mean, then rstd = 1 / sqrt(var + eps).
+ * scf_batch_norm_train, with xhat = (u - mean) rstd (one rounding each) and v = xhat gamma + beta:
+ *   res == NULL: y = v ("mid" with relu != 0); res != NULL, gamma_r == NULL ("tail"): y = v + res; gamma_r != NULL
+ *   ("tail + shortcut"): res is the raw shortcut output r, y = v + (rhat gamma_r + beta_r) with r's own statistics, kept in
+ *   saved_r; beta_r, saved_r required, every *_r NULL in the other forms.  relu != 0: y = y > 0 ? y : 0.
+ *   running = (1 - momentum) running + momentum batch; both running pointers of an operand NULL: none are kept.
+ * Two launches.  (1) a workgroup per plane, or per 16384-element chunk of a larger plane (K chunks): count, mean = sum /
+ *   count, then the sum of (x - mean)^2 -- never a raw sum of x^2 -- to workspace[3 ((n C + c) K + k)], r's behind u's.
+ *   HW % 4 == 0 and u, res, y 16-byte aligned: the chunk stays in registers, thread t of 256 owns the float4 t, t + 256, ...
+ *   and adds each as (a + b) + (c + d) to one chain from +0; otherwise thread t adds elements t, t + 256, ... in two sweeps;
+ *   then the workgroup's tree.  (2) every wave combines its channel's N K triples, p = n K + k, with Chan's formula
+ *   (n = na + nb, d = mean_b - mean_a, f = nb / n, mean = mean_a + d f, m2 = (m2_a + m2_b) + (d d) (na f)): groups of 64
+ *   consecutive p in a butterfly over lane distance 1, 2, ..., 32 with the lower lane as a, the groups folded in ascending
+ *   order; var = m2 / M.  The block of sample 0 that holds a plane's first element writes saved and the running statistics.
+ * scf_batch_norm_train_grad, with g' the cotangent at BN(u), S1 = sum g', S2 = sum g' xhat over the channel:
+ *   du = ((g' - S1 / M) - xhat (S2 / M)) (gamma rstd)   (one rounding each),   dbeta = S1, dgamma = S2.
+ *   y == NULL, gp == NULL, r == NULL ("mid"): g' = g, which the consumer's dgrad epilogue has already masked.
+ *   y, gp != NULL, r == NULL ("tail"): g' = y > 0 ? g : +0, written to gp (the cotangent of res) as well.
+ *   y, r != NULL, gp == NULL ("tail + shortcut"): g' as in the tail form; du from saved / gamma / S2, dr from saved_r /
+ *   gamma_r / S2r = sum g' rhat; dbeta_r = S1; saved_r, gamma_r, dr, dgamma_r, dbeta_r required, NULL in the other forms.
+ *   mean and rstd are read from saved, never recomputed; the mask is read from y, the forward's own bits.
+ *   Two launches.  (1) per plane or chunk (S1, S2, S2r), a thread's elements in one chain from +0 (float4: (a + b) +
+ *   (c + d)), the workgroup's tree, to workspace[3 ((n C + c) K + k)].  (2) lane l of a wave adds the triples p = l, l + 64,
+ *   ... in one chain from +0, then v[l] += v[l ^ j] for j = 32, ..., 1; accumulate != 0: the previous value of dgamma /
+ *   dbeta is added last.  du may alias g element for element in the mid form; nothing else may alias.
+ * workspace: scf_batch_norm_train_workspace(N, C, HW) floats for either call (or its error code).
+ * No atomics, allocation or synchronisation; bit-identical from run to run, the order fixed by (N, HW) and the alignment.
+ * A null required pointer, a pointer that is not 4-byte aligned, a form's NULL rule broken, a size <= 0, a workspace too
+ * small, or M == 1 (no unbiased variance; torch raises there too): SCF_EINVAL.  M > 2^24 (the counts travel as floats) or
+ * more than 2^31 - 1 blocks: SCF_EUNSUPPORTED.  Nothing is launched or written then.
+ * Added without a version bump; the presence of scf_batch_norm_train marks the feature.
+ * --------------------------------------------------------------------------------- */
+int64_t scf_batch_norm_train_workspace(int N, int C, int HW);
+int scf_batch_norm_train(const float* u, const float* gamma, const float* beta, float* running_mean, float* running_var,
+                         const float* res, const float* gamma_r, const float* beta_r, float* running_mean_r,
+                         float* running_var_r, int relu, float momentum, float eps, float* y, float* saved, float* saved_r,
+                         float* workspace, int64_t workspace_floats, int N, int C, int HW, scf_stream_t stream);
+int scf_batch_norm_train_grad(const float* g, const float* y, const float* u, const float* r, const float* saved,
+                              const float* saved_r, const float* gamma, const float* gamma_r, float* gp, float* du, float* dr,
+                              float* dgamma, float* dbeta, float* dgamma_r, float* dbeta_r, int accumulate, float* workspace,
+                              int64_t workspace_floats, int N, int C, int HW, scf_stream_t stream);
+
+/* ---------------------------------------------------------------------------------
  * Gate arithmetic of the ConvGRU backward (raft_decoder.py:168-253; gru_grad.hip), between the convolution gradients
  * above.  One pass of the forward: z = sigmoid(conv_z([h|x])), r = sigmoid(conv_r([h|x])), q = tanh(conv_q([r h|x])),
  * h' = (1 - z) h + z q.  With g = d loss / d h':  u_q = g z (1 - q^2), u_z = g (q - h) z (1 - z), [g_rh | g_x] =

@@ -327,6 +327,10 @@ SIGNATURES = {
                                 C.c_int64, _fp]),
     'scf_instance_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
     'scf_instance_norm_res_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
+    'scf_batch_norm_train_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'scf_batch_norm_train': (C.c_int, [_fp] * 10 + [C.c_int, C.c_float, C.c_float, _fp, _fp, _fp, _fp, C.c_int64, C.c_int,
+                                       C.c_int, C.c_int, _fp]),
+    'scf_batch_norm_train_grad': (C.c_int, [_fp] * 15 + [C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_gru_gate_grad_q': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,
                                       C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int, C.c_int64, _fp]),
     'scf_gru_gate_grad_r': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp,

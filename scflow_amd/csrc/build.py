@@ -6,7 +6,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SOURCES = ['capi.hip', 'corr_lookup.hip', 'corr_gemm.hip', 'conv_mfma.hip', 'conv_f16x3.hip', 'conv_dma.hip', 'conv_thin.hip', 'conv_taps.hip', 'conv_wino.hip', 'conv_wino1d.hip', 'conv_wino1d4.hip', 'resample.hip', 'pose.hip', 'pnp.hip', 'render.hip', 'patch.hip', 'patch_train.hip', 'scflow_iter.hip',
-           'norm.hip', 'metrics.hip', 'loss.hip', 'fc.hip', 'tail_grad.hip', 'fc_grad.hip', 'conv_grad.hip', 'conv_s1_grad.hip', 'gru_grad.hip', 'corr_lookup_grad.hip', 'corr_build_grad.hip', 'encoder_grad.hip', 'instance_norm_grad.hip', 'optim.hip']
+           'norm.hip', 'metrics.hip', 'loss.hip', 'fc.hip', 'tail_grad.hip', 'fc_grad.hip', 'conv_grad.hip', 'conv_s1_grad.hip', 'gru_grad.hip', 'corr_lookup_grad.hip', 'corr_build_grad.hip', 'encoder_grad.hip', 'instance_norm_grad.hip', 'batch_norm_train.hip', 'optim.hip']
 OUT = os.path.join(HERE, 'libscflow_hip.so')
 # conv_wino.hip: the SLP vectoriser turns the input transform's 32 adds into packed adds PLUS as many register
 # moves to pair their operands up; vector-ALU instructions cost matrix-pipe time there (see the file), so the

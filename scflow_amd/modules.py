@@ -106,6 +106,7 @@ class HipModule(nn.Module):
             if isinstance(m, HipModule):
                 m.__dict__['_packed'] = None
                 m.__dict__.pop('_pack_refs', None)
+                m.__dict__.pop('_raw_packed', None)
 
     def _apply(self, fn, *a, **k):
         out = super()._apply(fn, *a, **k)
@@ -198,6 +199,28 @@ class ConvBlock(HipModule):
 
 
 # =============================================================== encoder
+def _raw_packs(mod: HipModule, convs: dict) -> dict:
+    """the convolutions ``convs`` (key -> nn.Conv2d) of ``mod`` packed WITHOUT the norm behind them folded in: the second
+    packed set, what a forward on batch statistics launches.  Cached in ``mod`` under the identity and version of the
+    convolutions' own tensors (the running statistics move at every such forward and are no part of it); dropped with
+    ``packed`` by ``invalidate_packed()``."""
+    key = tuple((t.data_ptr(), t._version) for c in convs.values() for t in (c.weight, c.bias))
+    d = mod.__dict__
+    if d.get('_raw_packed') is None or d.get('_raw_packed_key') != key:
+        with torch.no_grad():
+            d['_raw_packed'] = {k: PackedConv.from_weight(c.weight, c.bias, c.stride[0], c.padding) for k, c in convs.items()}
+        d['_raw_packed_key'] = key
+    return d['_raw_packed']
+
+
+def _bn_step(bn, u: Tensor, **form):
+    """``ops.batch_norm_train`` of ``u`` with the parameters of the nn.BatchNorm2d ``bn``, whose running statistics and
+    batch count it moves"""
+    out = ops.batch_norm_train(u, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, **form)
+    bn.num_batches_tracked += 1
+    return out
+
+
 class _BasicBlock(HipModule):
     """backbone/resnet.py:14-94 parameters: conv1, {in,bn}1, conv2, {in,bn}2, downsample."""
 
@@ -275,6 +298,28 @@ class _BasicBlock(HipModule):
         kept.append((t, out, u1, u2, r))
         return out
 
+    def _forward_batch_stats(self, x: Tensor, kept: Optional[list]) -> Tensor:
+        """the BatchNorm block on the statistics of the batch: ``_forward_keeping``'s launches with the raw convolutions and
+        ``ops.batch_norm_train`` in place of ``instance_norm``; each layer's (mean, rstd) is kept next to its raw output"""
+        convs = dict(c1=self.conv1, c2=self.conv2)
+        if self.downsample is not None:
+            convs['ds'] = self.downsample[0]
+        p = _raw_packs(self, convs)
+        if 'ds' in p:
+            u1, r = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
+        else:
+            u1, r = ops.conv2d(p['c1'], x), None
+        t, s1 = _bn_step(self.bn1, u1, relu=True)
+        u2 = ops.conv2d(p['c2'], t)
+        if r is None:
+            (out, s2), sr = _bn_step(self.bn2, u2, res=x, relu=True), None
+        else:
+            out, s2, sr = _bn_step(self.bn2, u2, res=r, relu=True, res_bn=self._bn(self.downsample[1]))
+            self.downsample[1].num_batches_tracked += 1
+        if kept is not None:
+            kept.append((t, out, u1, u2, r, s1, s2, sr))
+        return out
+
 
 # What RAFTEncoder._walk_back asks of the norm kind, six closures over one backward's state.  With a layer = (the key of its
 # record, of its convolution, of its norm, the two modules): weight(*layer) -> the weight its dgrad reads (and opens its
@@ -338,6 +383,44 @@ def _raw_in_grad(grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got:
     return weight, slots, put, tail, mid, lambda i, x: dict(a=x, act=ACT_RELU) if i == 0 else {}
 
 
+def _batch_bn_grad(enc: 'RAFTEncoder', grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+    """BatchNorm on the statistics of the batch: ``_raw_in_grad`` (raw weights, unmasked joins, the stem's mask in front of
+    block 0 only) with ``ops.batch_norm_train_grad`` between the convolution gradients, on the (mean, rstd) the forward
+    kept, and its (dgamma, dbeta) into the slots of the norm's two parameters"""
+    weight, slots, put, _, _, mask = _raw_in_grad(grads, dst, acc, rec, prefix, got, eps)
+
+    def norm(bkey):
+        ks = [f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
+        return enc.get_submodule(bkey).weight, ks, [dst[k] for k in ks]
+
+    def tail(key, G, i, shortcut):
+        y, u2 = got[f'y{i}'], got[f'u2_{i}']
+        gamma, ks, into = norm(f'{key}.bn2')
+        if not shortcut:
+            g_sc, du2, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, out=[None, None] + into,
+                                                       accumulate=acc)
+            rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
+        else:
+            gamma_r, ks_r, into_r = norm(f'{key}.downsample.1')
+            du2, g_sc, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, r=got[f'r{i}'],
+                                                       saved_r=got[f'sr{i}'], gamma_r=gamma_r,
+                                                       out=[None, None] + into + into_r, accumulate=acc)
+            rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
+            ks = ks + ks_r
+        grads.update(zip(ks, dp))
+        return du2, g_sc
+
+    def mid(rkey, g, ukey):
+        bkey = rkey[:-3] + 'bn1'                     # 'in1' -> 'bn1', '<block>.in1' -> '<block>.bn1'
+        gamma, ks, into = norm(bkey)
+        du, *dp = ops.batch_norm_train_grad(g, got[ukey], got['s' + ukey[1:]], gamma, out=[None] + into, accumulate=acc)
+        grads.update(zip(ks, dp))
+        rec[bkey] = dict(g=g, u=got[ukey], du=du)
+        return du
+
+    return weight, slots, put, tail, mid, mask
+
+
 @ENCODERS.register_module()
 class RAFTEncoder(HipModule):
     """encoder/raft_encoder.py:13-314, net_type 'Basic' (the SCFlow config):
@@ -382,6 +465,26 @@ class RAFTEncoder(HipModule):
         # outputs of the stem and of a block's two convolutions) and r{i} (the raw output of a shortcut convolution, i = 2, 4)
         self.keep = False
         self.kept = {}
+        # under batch_stats() a BatchNorm encoder normalises with the statistics of the batch and moves its running
+        # statistics (the reference's freeze_bn=False); while keeping it then leaves the InstanceNorm set (u_stem, u1_{i},
+        # u2_{i}, r{i}) plus each layer's (2, C) mean / rstd: s_stem, s1_{i}, s2_{i}, sr{i} -- what bn_backward() reads
+        self.batch = False
+
+    @contextlib.contextmanager
+    def batch_stats(self):
+        """forwards inside the body run BatchNorm on the statistics of the batch (``ops.batch_norm_train`` behind the raw
+        convolutions) and move ``running_mean``, ``running_var`` and ``num_batches_tracked`` of all 15 layers, as
+        ``nn.BatchNorm2d`` does in ``train()`` mode; a setting of the caller's stays.  BatchNorm encoders only.  ``SyncBN``
+        configs map to BN here as everywhere: the statistics are those of this process's own batch, nothing is exchanged
+        between processes."""
+        if self.kind != 'BN':
+            raise NotImplementedError('RAFTEncoder.batch_stats: an InstanceNorm encoder has no batch statistics')
+        prev = self.batch
+        self.batch = True
+        try:
+            yield self
+        finally:
+            self.batch = prev
 
     @contextlib.contextmanager
     def keeping(self):
@@ -404,6 +507,8 @@ class RAFTEncoder(HipModule):
                 head_act2: int = ACT_NONE, head_split: int = 0) -> Tensor:
         """raft_encoder.py:286-314.  ``out`` / ``head_*`` let the caller have the 1x1 head
         write (with a split tanh/relu epilogue) straight into a slice of a larger buffer."""
+        if self.batch:
+            return self._forward_batch_stats(x, out, head_act, head_act2, head_split)
         p = self.packed
         blocks = [] if self.keep else None
         image = x
@@ -424,12 +529,34 @@ class RAFTEncoder(HipModule):
             self.kept['u_stem'] = raw
         return y
 
+    def _forward_batch_stats(self, x: Tensor, out: Optional[Tensor], head_act: int, head_act2: int, head_split: int) -> Tensor:
+        """``forward`` under ``batch_stats()``: every layer is its raw convolution and ``ops.batch_norm_train``, two more
+        launches per norm than the folded form.  The folded packs go stale as the running statistics move, so they are
+        marked invalid here and the next eval forward folds again."""
+        p = _raw_packs(self, dict(stem=self.conv1, head=self.conv2))
+        blocks = [] if self.keep else None
+        raw = ops.conv2d(p['stem'], x)
+        stem, s_stem = _bn_step(self.bn1, raw, relu=True)
+        y = stem
+        for name in self.res_layers:
+            for blk in getattr(self, name):
+                y = blk._forward_batch_stats(y, blocks)
+        y = ops.conv2d(p['head'], y, out=out, act=head_act, act2=head_act2, act_split=head_split)
+        for m in self.modules():
+            if isinstance(m, HipModule):
+                m.__dict__['_packed'] = None
+        self.kept = {} if blocks is None else self._kept_dict(x, stem, blocks, y, out is not None)
+        if blocks is not None:
+            self.kept.update(u_stem=raw, s_stem=s_stem)
+        return y
+
     @staticmethod
     def _kept_dict(image: Tensor, stem: Tensor, blocks, y: Tensor, clone_out: bool) -> dict:
         kept = dict(x=image, stem=stem, out=y.clone() if clone_out else y)
         for i, (t, o, *raws) in enumerate(blocks):
             kept[f't{i}'], kept[f'y{i}'] = t, o
-            for k, v in zip(('u1_', 'u2_', 'r'), raws):       # an InstanceNorm block's raw convolution outputs
+            # an InstanceNorm block's raw convolution outputs; on batch statistics also each norm's (mean, rstd)
+            for k, v in zip(('u1_', 'u2_', 'r', 's1_', 's2_', 'sr'), raws):
                 if v is not None:
                     kept[f'{k}{i}'] = v
         return kept
@@ -534,8 +661,17 @@ class RAFTEncoder(HipModule):
                                       'RAFTEncoder.in_backward, which takes a cotangent at the encoder\'s output -- the '
                                       'correlation-build backward (SCFlowDecoder.corr_backward) produces it')
         nb = sum(len(getattr(self, name)) for name in self.res_layers)
-        keys = ['x', 'stem'] + [f'{k}{i}' for i in range(nb) for k in 'ty'] + ([] if out is not None else ['out'])
-        got, shape = self._saved_for_backward(what, saved, keys, nb, 'a forward')
+        keys = ['x', 'stem'] + [f'{k}{i}' for i in range(nb) for k in 'ty']
+        got, u = self._head_cotangent(what, saved, keys, 'a forward', g_out, out, head_act, head_act2, head_split)
+        return self._walk_back(what, _folded_bn_grad, got, u, param_grads, intermediates, prefix)
+
+    def _head_cotangent(self, what: str, saved, keys: list, whose: str, g_out, out: Optional[Tensor], head_act: int,
+                        head_act2: int, head_split: int) -> Tuple[dict, Tensor]:
+        """what ``backward`` and ``bn_backward`` do in front of the walk: (the entries ``keys`` of ``saved``, the cotangent
+        at the 1x1 head's raw output from ``g_out`` through the head's activation(s))"""
+        nb = sum(len(getattr(self, name)) for name in self.res_layers)
+        keys = keys + ([] if out is not None else ['out'])
+        got, shape = self._saved_for_backward(what, saved, keys, nb, whose)
         if out is None:
             out = got['out']
         n, co = shape[:2]
@@ -557,7 +693,37 @@ class RAFTEncoder(HipModule):
         u = torch.empty(shape, dtype=torch.float32, device=out.device)
         for g, (a, b, act) in zip(gs, parts):
             ops.act_grad(g, None if act == ACT_NONE else out[:, a:b], act, out=u[:, a:b])
-        return self._walk_back(what, _folded_bn_grad, got, u, param_grads, intermediates, prefix)
+        return got, u
+
+    def bn_backward(self, saved: dict, g_out: Union[Tensor, Sequence[Tensor]], out: Optional[Tensor] = None,
+                    head_act: int = ACT_NONE, head_act2: int = ACT_NONE, head_split: int = 0,
+                    param_grads: Optional[dict] = None, intermediates: Optional[dict] = None, prefix: str = ''):
+        """Backward of the BatchNorm encoder on the statistics of the batch with respect to its parameters: the reference's
+        context encoder under ``freeze_bn=False``.  The input image gets no gradient, the running statistics have none.
+
+        ``saved``: ``kept`` of a forward under ``batch_stats()`` and ``keeping()``: what ``in_backward`` reads (x, stem,
+        u_stem and per block t, y, u1_, u2_, with r for the two down-sampling blocks) plus every norm's (2, C) batch mean and
+        rstd (s_stem, s1_, s2_, sr).  ``g_out``, ``out``, ``head_*``, ``param_grads``, ``intermediates``, ``prefix``: as in
+        ``backward``, whose head handling this is.  -> the gradients of all 62 parameters.
+
+        Chain: ``in_backward``'s, with ``ops.batch_norm_train_grad`` where that has ``ops.instance_norm_grad``: the
+        statistics couple the samples of the batch, so d loss / d u carries the two channel sums S1 and S2, which are also
+        (dbeta, dgamma).  Raw weights, unmasked joins, the stem's mask in front of block 0 only.
+
+        The bias of a convolution in front of a BatchNorm has gradient 0 in exact arithmetic (du sums to 0 over a channel);
+        it is computed like any other bias gradient and comes out as rounding noise, as autograd's does.
+
+        ``SyncBN`` configs map to BN: the statistics, and so this derivative, are those of the process's own batch."""
+        what = 'RAFTEncoder.bn_backward'
+        if self.kind != 'BN':
+            raise NotImplementedError(f'{what}: an InstanceNorm encoder takes RAFTEncoder.in_backward')
+        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
+        keys = (['x', 'stem', 'u_stem', 's_stem']
+                + [f'{k}{i}' for i in range(len(blocks)) for k in ('t', 'y', 'u1_', 'u2_', 's1_', 's2_')]
+                + [f'{k}{i}' for i, blk in enumerate(blocks) if blk.downsample is not None for k in ('r', 'sr')])
+        got, u = self._head_cotangent(what, saved, keys, 'a forward under batch_stats()', g_out, out, head_act, head_act2,
+                                      head_split)
+        return self._walk_back(what, partial(_batch_bn_grad, self), got, u, param_grads, intermediates, prefix)
 
     def in_backward(self, saved: dict, g_out: Tensor, param_grads: Optional[dict] = None,
                     intermediates: Optional[dict] = None, prefix: str = ''):

@@ -30,7 +30,7 @@ __all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scfl
            'instance_norm', 'group_norm_relu', 'linear', 'fc_splitk', 'fc_slices', 'pose_update', 'reproject_flow',
            'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
            'unproject_depth', 'linear_pair', 'resize_bilinear', 'resize_bilinear_grad', 'reproject_flow_grad', 'pose_update_grad', 'convex_upsample', 'avgpool2x2', 'copy_channels',
-           'fc_operand', 'fc_dgrad', 'fc_wgrad', 'pose_select_grad', 'group_norm_flat_grad',
+           'fc_operand', 'fc_dgrad', 'fc_wgrad', 'pose_select_grad', 'group_norm_flat_grad', 'batch_norm_train', 'batch_norm_train_grad',
            'ADAMW_CHUNK', 'ADAMW_NORM_THREADS', 'adamw_chunk_table', 'adamw_chunk_rows', 'AdamwChunks', 'grad_sqnorm', 'adamw_step',
            'ACT_NONE', 'ACT_RELU', 'ACT_SIGMOID', 'ACT_TANH', 'CONV_PLAIN', 'CONV_GRU_ZR',
            'CONV_GRU_Q']
@@ -2658,6 +2658,142 @@ def instance_norm_grad(g: Tensor, u: Tensor, y: Optional[Tensor] = None, r: Opti
         _lib.check(lib.scf_instance_norm_res_norm_grad(ptr['g'], ptr['y'], ptr['u'], ptr['r'], ptr['out[0]'], ptr['out[1]'],
                                                        n * c, h * w, float(eps), _stream()), 'scf_instance_norm_res_norm_grad')
     return outs[0] if nout == 1 else tuple(outs)
+
+
+# ------------------------------------------------- BatchNorm on batch statistics (batch_norm_train.hip)
+def batch_norm_train_workspace(n: int, c: int, hw: int) -> int:
+    """floats of workspace ``batch_norm_train`` / ``batch_norm_train_grad`` need (``scf_batch_norm_train_workspace``)."""
+    return _workspace_floats('batch_norm_train_workspace', n, c, hw)
+
+
+def _bnt_maps(what: str, shape, named: dict) -> dict:
+    """the data pointers of the (N, C, H, W) operands ``named`` (None stays None), each dense and of ``shape``"""
+    ptr = {}
+    for k, t in named.items():
+        if t is None:
+            ptr[k] = None
+            continue
+        ptr[k] = _dense(t, f'{what}: {k}')
+        if tuple(t.shape) != shape:
+            raise _lib.ScflowHipError(f'{what}: {k} must be {shape} like {next(iter(named))}, got {tuple(t.shape)}')
+    return ptr
+
+
+def _bnt_shape(what: str, t: Tensor, name: str) -> Tuple[int, int, int, int]:
+    if not isinstance(t, torch.Tensor) or t.dim() != 4 or t.numel() == 0:
+        raise _lib.ScflowHipError(f'{what}: {name} must be a non-empty (N, C, H, W) tensor, got '
+                                  f'{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}')
+    n, c, h, w = t.shape
+    if n * h * w == 1:
+        raise _lib.ScflowHipError(f'{what}: one value per channel ({tuple(t.shape)}) has no batch statistics')
+    return n, c, h, w
+
+
+def _bnt_out(t: Optional[Tensor], shape, like: Tensor) -> Tensor:
+    return torch.empty(shape, dtype=torch.float32, device=like.device) if t is None else t
+
+
+def batch_norm_train(u: Tensor, gamma: Tensor, beta: Tensor, running_mean: Optional[Tensor], running_var: Optional[Tensor],
+                     momentum: Optional[float] = 0.1, eps: float = 1e-5, res: Optional[Tensor] = None, relu: bool = False,
+                     res_bn: Optional[Sequence[Optional[Tensor]]] = None, out: Optional[Tensor] = None,
+                     workspace: Optional[Tensor] = None):
+    """Training-mode ``BatchNorm2d`` of the raw convolution output ``u`` (N, C, H, W) on the statistics of the batch
+    (``scf_batch_norm_train``): biased variance for normalising, ``running = (1 - momentum) running + momentum batch`` with
+    the unbiased variance, updated in place (both None: none are kept).  Three forms:
+
+    * ``res`` None: ``BN(u)``, with ``relu`` the encoder's ``relu(BN(u))`` -> ``(y, saved)``;
+    * ``res`` given: ``BN(u) + res`` -> ``(y, saved)``;
+    * ``res`` and ``res_bn = (gamma, beta, running_mean, running_var)`` given: ``BN(u) + BN_b(res)``, ``res`` the raw
+      output of a shortcut convolution with its own parameters and statistics -> ``(y, saved, saved_r)``.
+
+    ``saved``: (2, C), the batch mean and ``rstd = 1 / sqrt(var + eps)``, what ``batch_norm_train_grad`` reads.  ``out``:
+    the destination of ``y`` (it must not alias an operand).  ``momentum=None`` (torch's cumulative average) is not built."""
+    what = 'batch_norm_train'
+    if momentum is None:
+        raise NotImplementedError(f'{what}: momentum=None (the cumulative moving average) is not implemented')
+    n, c, h, w = _bnt_shape(what, u, 'u')
+    shape = (n, c, h, w)
+    if res_bn is not None and res is None:
+        raise _lib.ScflowHipError(f'{what}: res_bn (a normalised shortcut\'s parameters) comes with res, its raw output')
+    if res_bn is not None and len(res_bn) != 4:
+        raise _lib.ScflowHipError(f'{what}: res_bn holds (gamma, beta, running_mean, running_var)')
+    y = _bnt_out(out, shape, u)
+    ptr = _bnt_maps(what, shape, dict(u=u, res=res, out=y))
+    if any(y.data_ptr() == t.data_ptr() for t in (u, res) if t is not None):
+        raise _lib.ScflowHipError(f'{what}: out must not alias u or res (the backward reads the raw u)')
+
+    def vectors(tag, g, b, rm, rv):
+        if (rm is None) != (rv is None):
+            raise _lib.ScflowHipError(f'{what}: running_mean{tag} and running_var{tag} come together')
+        named = {f'gamma{tag}': g, f'beta{tag}': b}
+        if rm is not None:
+            named.update({f'running_mean{tag}': rm, f'running_var{tag}': rv})
+        ptrs = _bn_vectors(what, c, **named)
+        return ptrs + [None] * (4 - len(ptrs))
+
+    pa = vectors('', gamma, beta, running_mean, running_var)
+    pb = [None] * 4 if res_bn is None else vectors('_r', *res_bn)
+    saved = torch.empty((2, c), dtype=torch.float32, device=u.device)
+    saved_r = None if res_bn is None else torch.empty((2, c), dtype=torch.float32, device=u.device)
+    workspace = _grad_workspace(what, workspace, batch_norm_train_workspace(n, c, h * w), u)
+    _lib.check(_lib.load().scf_batch_norm_train(
+        ptr['u'], *pa, ptr['res'], *pb, int(bool(relu)), float(momentum), float(eps), ptr['out'], saved.data_ptr(),
+        None if saved_r is None else saved_r.data_ptr(), workspace.data_ptr(), workspace.numel(), n, c, h * w, _stream()),
+        'scf_batch_norm_train')
+    return (y, saved) if saved_r is None else (y, saved, saved_r)
+
+
+def batch_norm_train_grad(g: Tensor, u: Tensor, saved: Tensor, gamma: Tensor, y: Optional[Tensor] = None,
+                          r: Optional[Tensor] = None, saved_r: Optional[Tensor] = None, gamma_r: Optional[Tensor] = None,
+                          out: Optional[Sequence[Optional[Tensor]]] = None, accumulate: bool = False,
+                          workspace: Optional[Tensor] = None):
+    """Backward of ``batch_norm_train`` with respect to its raw input(s) and its affine parameters
+    (``scf_batch_norm_train_grad``).  ``u``: the raw convolution output the forward normalised, ``saved`` its (2, C)
+    statistics from that forward (they are not recomputed).  Every map a contiguous (N, C, H, W) tensor of one shape.
+
+    * ``y`` None (``relu(BN(u))``): ``g`` is the cotangent at ``BN(u)``, already masked by the consumer
+      -> ``(du, dgamma, dbeta)``;
+    * ``y`` given (``y = relu(BN(u) + res)``): ``g`` the cotangent at ``y`` -> ``(g', du, dgamma, dbeta)`` with
+      ``g' = g [y > 0]``, which is also the cotangent of ``res``;
+    * ``y``, ``r``, ``saved_r``, ``gamma_r`` given (``y = relu(BN(u) + BN_b(r))``)
+      -> ``(du, dr, dgamma, dbeta, dgamma_r, dbeta_r)``.
+
+    ``out``: the destinations in the order returned (None entries are allocated); ``accumulate``: the parameter gradients
+    are added to their destinations, as ``bn_unfold`` has it.  ``du`` may be ``g`` itself in the first form."""
+    what = 'batch_norm_train_grad'
+    n, c, h, w = _bnt_shape(what, g, 'g')
+    shape = (n, c, h, w)
+    if r is not None and y is None:
+        raise _lib.ScflowHipError(f'{what}: r (a normalised shortcut) comes with y, the block\'s output')
+    if (r is None) != (saved_r is None) or (r is None) != (gamma_r is None):
+        raise _lib.ScflowHipError(f'{what}: r, saved_r and gamma_r (a normalised shortcut) come together')
+    nmap = 1 if y is None else 2
+    nvec = 2 if r is None else 4
+    outs = [None] * (nmap + nvec) if out is None else list(out)
+    if len(outs) != nmap + nvec:
+        raise _lib.ScflowHipError(f'{what}: out holds {nmap} + {nvec} destinations in this form, got {len(outs)}')
+    maps = [_bnt_out(o, shape, g) for o in outs[:nmap]]
+    vecs = [_fc_grad_out(o, (c,), g, what, f'out[{nmap + i}]', accumulate) for i, o in enumerate(outs[nmap:])]
+    named = dict(g=g, u=u, y=y, r=r)
+    named.update({f'out[{i}]': o for i, o in enumerate(maps)})
+    ptr = _bnt_maps(what, shape, named)
+    stats = dict(saved=saved) if r is None else dict(saved=saved, saved_r=saved_r)
+    for k, t in stats.items():
+        _dense(t, f'{what}: {k}')
+        if tuple(t.shape) != (2, c):
+            raise _lib.ScflowHipError(f'{what}: {k} must be (2, {c}), the forward\'s (mean, rstd), got {tuple(t.shape)}')
+    pg = _bn_vectors(what, c, **(dict(gamma=gamma) if r is None else dict(gamma=gamma, gamma_r=gamma_r)))
+    if r is None:
+        gp, du, dr = (None, ptr['out[0]'], None) if y is None else (ptr['out[0]'], ptr['out[1]'], None)
+    else:
+        gp, du, dr = None, ptr['out[0]'], ptr['out[1]']
+    pv = [v.data_ptr() for v in vecs] + [None] * (4 - nvec)
+    workspace = _grad_workspace(what, workspace, batch_norm_train_workspace(n, c, h * w), g)
+    _lib.check(_lib.load().scf_batch_norm_train_grad(
+        ptr['g'], ptr['y'], ptr['u'], ptr['r'], saved.data_ptr(), None if r is None else saved_r.data_ptr(), pg[0],
+        None if r is None else pg[1], gp, du, dr, *pv, int(bool(accumulate)), workspace.data_ptr(), workspace.numel(),
+        n, c, h * w, _stream()), 'scf_batch_norm_train_grad')
+    return (*maps, *vecs)
 
 
 # ------------------------------------------------- gate arithmetic of the ConvGRU backward (gru_grad.hip)

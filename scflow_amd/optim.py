@@ -231,10 +231,12 @@ class AdamW:
             self.exp_avg_sq[i].copy_(s['exp_avg_sq'])
 
 
-def build_optimizer(model, optimizer_cfg: dict, optimizer_config: Optional[dict] = None, lr_config: Optional[dict] = None) -> AdamW:
+def build_optimizer(model, optimizer_cfg: dict, optimizer_config: Optional[dict] = None, lr_config: Optional[dict] = None,
+                    network: bool = False) -> AdamW:
     """the ``optimizer``, ``optimizer_config`` and ``lr_config`` dicts of a reference config file -> ``AdamW`` over
     ``model.trainable_parameters()``, clipping at ``optimizer_config['grad_clip']['max_norm']`` and following the
-    ``OneCycle`` schedule of ``lr_config``.  Any other optimizer type or policy is refused by name."""
+    ``OneCycle`` schedule of ``lr_config``.  Any other optimizer type or policy is refused by name.
+    ``network=True``: over ``model.network_parameters()``, for ``SCFlowRefiner.train_step_network``."""
     cfg = dict(optimizer_cfg)
     kind = cfg.pop('type', None)
     if kind != 'AdamW':
@@ -264,4 +266,5 @@ def build_optimizer(model, optimizer_cfg: dict, optimizer_config: Optional[dict]
         if unknown:
             raise NotImplementedError(f'OneCycle options {sorted(unknown)} are not implemented')
         schedule = OneCycle(**lr_cfg)
-    return AdamW(model.trainable_parameters(), max_norm=max_norm, model=model, schedule=schedule, **cfg)
+    params = model.network_parameters() if network else model.trainable_parameters()
+    return AdamW(params, max_norm=max_norm, model=model, schedule=schedule, **cfg)

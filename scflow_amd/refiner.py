@@ -13,7 +13,9 @@ the network's outputs, the ``loss_and_*_grads()`` ladder (``_LOSS_DEPTHS``, nine
 ``loss_and_context_grads()`` through the context encoder, ``loss_and_network_grads()`` through the correlation build and
 the feature encoders to every parameter of the network.
 ``train_step()`` applies those gradients with ``scflow_amd.optim.AdamW`` (the reference's ``freeze_encoder=True,
-freeze_bn=True`` case, nothing else); ``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
+freeze_bn=True`` case, nothing else); ``train_step_network()`` takes the configuration as given, the shipped
+``freeze_encoder=False, freeze_bn=False`` with BatchNorm on batch statistics (``batch_norm_training()``) included;
+``forward(return_loss=True)`` keeps raising.  The config's ``renderer`` dict is ignored too;
 ``attach_renderer(MeshRenderer(...))`` enables ``format_data_test``, ``update_data``
 and ``test_cfg['cycles'] > 1`` on the HIP renderer (scflow_amd/mesh.py).
 """
@@ -298,7 +300,8 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         # an encoder that keeps its activations for backward() / in_backward() runs its own forward, on this stream: the
         # paired walk below keeps nothing (same kernels per layer, same bits), and what it keeps is read on this stream
         # afterwards
-        keeping = self.context.keep or self.render_encoder.keep or self.real_encoder.keep
+        # afterwards; so does a context encoder on batch statistics (the paired walk assumes the folded form)
+        keeping = self.context.keep or self.render_encoder.keep or self.real_encoder.keep or self.context.batch
         ov_ctx = small_work(n, H, W, 'context') and not keeping
         fork = ops.fork_point() if ov_ctx else None     # the context encoder may start from here
         if (not self.seperate_encoder and not keeping and ops.branch_mode(n, H, W, 'context') == 2
@@ -534,7 +537,9 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         that one to the runner's hook), and every cycle of one call uses the same learning rate.
 
         Trains what has a backward: NotImplementedError unless ``freeze_encoder and freeze_bn``, and everything
-        ``loss_and_motion_grads()`` refuses.  ``data``: an already formatted dict (it is not modified)."""
+        ``loss_and_motion_grads()`` refuses.  ``data``: an already formatted dict (it is not modified).
+        ``train_step_network()`` is this step for the other settings of the two flags, the reference's shipped
+        ``freeze_encoder=False, freeze_bn=False`` among them."""
         from .optim import AdamW
         if not isinstance(optimizer, AdamW):
             raise TypeError(f'train_step needs a scflow_amd.optim.AdamW (build_optimizer), got {type(optimizer).__name__}: there '
@@ -550,10 +555,49 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
         mine = self.trainable_parameters()
         if len(mine) != len(optimizer.params) or any(a is not b for (_, a), b in zip(mine, optimizer.params)):
             raise ValueError('train_step: the optimizer was not built over this model\'s trainable_parameters()')
+        return self._train_cycles(data_batch, optimizer, data, 'context', 'motion')
+
+    @contextlib.contextmanager
+    def batch_norm_training(self):
+        """inside the body the context encoder runs on the statistics of the batch (``RAFTEncoder.batch_stats``): every
+        ``loss*()`` rung normalises with them and moves the 15 layers' running statistics, and the rungs ``'context'`` and
+        ``'network'`` take ``RAFTEncoder.bn_backward``.  The reference's ``freeze_bn=False``; off by default."""
+        with self.context.batch_stats():
+            yield self
+
+    def network_parameters(self):
+        """the (name, parameter) pairs of the reference's training recipe, which ``train_step_network`` updates: all of
+        ``named_parameters()``, less the feature encoder(s) when ``freeze_encoder``"""
+        frozen = ('render_encoder.', 'real_encoder.') if self.freeze_encoder else ()
+        return [(n, p) for n, p in self.named_parameters() if not n.startswith(frozen)]
+
+    def train_step_network(self, data_batch: Optional[Dict], optimizer, data: Optional[Dict] = None) -> Dict:
+        """``train_step``'s contract (return value, ``cycles``, one device-to-host transfer, the packs invalidated after
+        every step) for the model's configuration as given: the rung ``loss_and_network_grads()``, or
+        ``loss_and_context_grads()`` when ``freeze_encoder``, taken inside ``batch_norm_training()`` unless ``freeze_bn``.
+        With ``freeze_encoder=False, freeze_bn=False``, what the reference ships, every parameter and all BatchNorm
+        running statistics move.  ``optimizer``: ``build_optimizer(..., network=True)``, an ``AdamW`` over
+        ``network_parameters()``.  Refuses what ``SCFlowDecoder.check_backward('network')`` refuses, nothing else."""
+        from .optim import AdamW
+        if not isinstance(optimizer, AdamW):
+            raise TypeError(f'train_step_network needs a scflow_amd.optim.AdamW (build_optimizer), got '
+                            f'{type(optimizer).__name__}: there is no autograd graph behind the loss and no .grad for another '
+                            'optimizer to read')
+        mine = self.network_parameters()
+        if len(mine) != len(optimizer.params) or any(a is not b for (_, a), b in zip(mine, optimizer.params)):
+            raise ValueError('train_step_network: the optimizer was not built over this model\'s network_parameters() '
+                             '(build_optimizer(..., network=True))')
+        with contextlib.nullcontext() if self.freeze_bn else self.batch_norm_training():
+            return self._train_cycles(data_batch, optimizer, data, 'context' if self.freeze_encoder else 'network',
+                                      'network')
+
+    def _train_cycles(self, data_batch, optimizer, data, depth: str, refuse: str) -> Dict:
+        """the cycles of one training iteration behind ``train_step`` and ``train_step_network``: loss and gradients at
+        the rung ``depth``, step, ``update_data``; ``refuse``: the depth whose refusals come before anything is rendered"""
         cycles = int(self.train_cfg.get('cycles', 1))
         if cycles > 1:
             self._need_renderer("train_cfg['cycles'] > 1")
-        self.decoder.check_backward('motion')           # refuse before anything is rendered or stepped
+        self.decoder.check_backward(refuse)             # refuse before anything is rendered or stepped
         if data is None:
             data = self.format_data_train_sup(data_batch)
         data = dict(data)
@@ -561,7 +605,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             else len(data['real_images'])
         named = []
         for i in range(cycles):
-            loss, _, log, seq_r, seq_t, grads = self._loss(data_batch, data, 'context', host_log=False)
+            loss, _, log, seq_r, seq_t, grads = self._loss(data_batch, data, depth, host_log=False)
             norm = optimizer.step(grads['params'], end_of_iteration=i == cycles - 1)
             if optimizer.model is not self:
                 self.invalidate_packed()
@@ -647,7 +691,7 @@ class SCFlowRefiner(_RenderingRefiner, HipModule):
             if 'params' in grads:
                 grads['params'] = {'decoder.' + key: val for key, val in grads['params'].items()}
             if level >= at('context'):
-                grads['params'].update(ctx.backward(
+                grads['params'].update((ctx.bn_backward if ctx.batch else ctx.backward)(     # batch_norm_training()
                     ctx.kept, (grads['gru']['initial_hidden'], grads['gru']['context']), head_act=ACT_TANH,
                     head_act2=ACT_RELU, head_split=self.h_channels, prefix='context.'))
             if level >= at('network'):
