@@ -101,10 +101,17 @@ class HipModule(nn.Module):
         for m in self.modules():
             m.__dict__.pop('_ctx_cache', None)
 
-    def _drop_packed(self) -> None:
+    def _drop_folded(self) -> None:
+        """drop ``packed`` of this module and its children and leave the raw packs (``_raw_packs``): for a forward that moved
+        the running statistics ``packed`` folds in, and read the raw packs itself"""
         for m in self.modules():
             if isinstance(m, HipModule):
                 m.__dict__['_packed'] = None
+
+    def _drop_packed(self) -> None:
+        self._drop_folded()
+        for m in self.modules():
+            if isinstance(m, HipModule):
                 m.__dict__.pop('_pack_refs', None)
                 m.__dict__.pop('_raw_packed', None)
 
@@ -221,6 +228,13 @@ def _bn_step(bn, u: Tensor, **form):
     return out
 
 
+def _bn_params(norm):
+    """(weight, bias, running_mean, running_var) of a BatchNorm layer: what ``PackedConv.from_weight`` folds into the
+    convolution in front as ``bn=`` and ``ops.batch_norm_train`` takes as ``res_bn=``; None for an InstanceNorm layer, which
+    has nothing to fold"""
+    return (norm.weight, norm.bias, norm.running_mean, norm.running_var) if isinstance(norm, nn.BatchNorm2d) else None
+
+
 class _BasicBlock(HipModule):
     """backbone/resnet.py:14-94 parameters: conv1, {in,bn}1, conv2, {in,bn}2, downsample."""
 
@@ -238,187 +252,253 @@ class _BasicBlock(HipModule):
             self.downsample = nn.Sequential(nn.Conv2d(inplanes, planes, 1, stride=stride, bias=True),
                                             mk(planes))
 
-    def _bn(self, m):
-        return (m.weight, m.bias, m.running_mean, m.running_var) if self.kind == 'BN' else None
+    def _convs(self) -> dict:
+        """the block's convolutions under the keys of its packed sets"""
+        convs = dict(c1=self.conv1, c2=self.conv2)
+        if self.downsample is not None:
+            convs['ds'] = self.downsample[0]
+        return convs
 
     def _pack(self):
         n1, n2 = getattr(self, self.tag + '1'), getattr(self, self.tag + '2')
         eps = n1.eps
         p = dict(c1=PackedConv.from_weight(self.conv1.weight, self.conv1.bias, self.stride, 1,
-                                           bn=self._bn(n1), eps=eps),
+                                           bn=_bn_params(n1), eps=eps),
                  c2=PackedConv.from_weight(self.conv2.weight, self.conv2.bias, 1, 1,
-                                           bn=self._bn(n2), eps=eps))
+                                           bn=_bn_params(n2), eps=eps))
         if self.downsample is not None:
             ds = self.downsample[0]
             p['ds'] = PackedConv.from_weight(ds.weight, ds.bias, self.stride, 0,
-                                             bn=self._bn(self.downsample[1]), eps=eps)
+                                             bn=_bn_params(self.downsample[1]), eps=eps)
         return p
 
-    def forward(self, x: Tensor, kept: Optional[list] = None) -> Tensor:
-        """resnet.py:67-94.  BN (eval) is folded into the conv epilogue; IN needs the
-        whole plane, so it is its own kernel (residual add + ReLU fused there).
-        ``kept``: a list that receives (the post-ReLU conv1 output, the block's output), the forward's own tensors.  An
-        InstanceNorm block then normalises out of place and appends the raw outputs of conv1, conv2 and the shortcut
-        convolution (None without one) as well: ``RAFTEncoder.in_backward`` recomputes the statistics from them."""
-        p = self.packed
-        if kept is not None and self.kind != 'BN':
-            return self._forward_keeping(x, kept)
+    def forward(self, x: Tensor, norm, kept: Optional[dict] = None, i: int = 0) -> Tensor:
+        """resnet.py:67-94, the one walk of a block: conv1 -> norm and ReLU -> conv2 -> norm, residual and ReLU.  ``norm``
+        is the norm kind (``_FoldedBN``, ``_RawIN``, ``_BatchBN`` below) and supplies what differs: the packed set, what
+        rides in the convolutions' epilogues, the two norm calls and whether they write in place.
+        ``kept``: the encoder's dict while it keeps; block ``i`` leaves t{i} (the post-ReLU conv1 output) and y{i} (its
+        output) there, the forward's own tensors, and the norm kind what its backward reads besides."""
+        p = norm.packs(self)
         # a block with a shortcut convolution hands both layers that read x to ops.conv2d_pair: on full grids the blocks of a
         # 3x3 / s2 conv1 compute the 1x1 / s2 shortcut from the patch they stage anyway (conv_dma.hip, shared-input form)
-        if self.kind == 'BN':
-            if 'ds' in p:
-                y, idt = ops.conv2d_pair((p['c1'], x, dict(act=ACT_RELU)), (p['ds'], x))
-            else:
-                y, idt = ops.conv2d(p['c1'], x, act=ACT_RELU), x
-            out = ops.conv2d(p['c2'], y, res=idt, act=ACT_RELU)
+        if 'ds' in p:
+            u1, r = ops.conv2d_pair((p['c1'], x, norm.rides), (p['ds'], x))
         else:
-            if 'ds' in p:
-                y, idt = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
-            else:
-                y, idt = ops.conv2d(p['c1'], x), x
-            ops.instance_norm(y, relu=True, out=y)
-            y2 = ops.conv2d(p['c2'], y)
-            # (the shortcut's own normalisation rides in the block's final pass)
-            out = ops.instance_norm(y2, res=idt, relu=True, out=y2, res_norm='ds' in p)
+            u1, r = ops.conv2d(p['c1'], x, **norm.rides), None
+        t = norm.mid(self, u1, kept, f'1_{i}')
+        u2 = ops.conv2d(p['c2'], t, res=(x if r is None else r) if norm.fused else None, **norm.rides)
+        # (a shortcut's own normalisation rides in the block's final pass)
+        out = norm.tail(self, u2, x, r, kept, i)
         if kept is not None:
-            kept.append((y, out))
+            kept[f't{i}'], kept[f'y{i}'] = t, out
         return out
 
-    def _forward_keeping(self, x: Tensor, kept: list) -> Tensor:
-        """the InstanceNorm block's launches with every normalisation out of place: the same kernels on the same values,
-        so the same bits.  The shortcut's raw output is normalised in a copy where the final pass uses it as scratch."""
-        p = self.packed
-        if 'ds' in p:
-            u1, r = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
-        else:
-            u1, r = ops.conv2d(p['c1'], x), None
-        t = ops.instance_norm(u1, relu=True)
-        u2 = ops.conv2d(p['c2'], t)
-        out = ops.instance_norm(u2, res=x if r is None else r.clone(), relu=True, res_norm=r is not None)
-        kept.append((t, out, u1, u2, r))
-        return out
 
-    def _forward_batch_stats(self, x: Tensor, kept: Optional[list]) -> Tensor:
-        """the BatchNorm block on the statistics of the batch: ``_forward_keeping``'s launches with the raw convolutions and
-        ``ops.batch_norm_train`` in place of ``instance_norm``; each layer's (mean, rstd) is kept next to its raw output"""
-        convs = dict(c1=self.conv1, c2=self.conv2)
-        if self.downsample is not None:
-            convs['ds'] = self.downsample[0]
-        p = _raw_packs(self, convs)
-        if 'ds' in p:
-            u1, r = ops.conv2d_pair((p['c1'], x), (p['ds'], x))
-        else:
-            u1, r = ops.conv2d(p['c1'], x), None
-        t, s1 = _bn_step(self.bn1, u1, relu=True)
-        u2 = ops.conv2d(p['c2'], t)
+# The three norm kinds of an encoder, each with both directions side by side.
+#
+# Forward, what _BasicBlock.forward and RAFTEncoder.forward ask: packs(mod) -> the packed set the walk launches; rides: the
+# conv2d keywords of every launch but the head's; fused: conv2's launch also takes the residual (the block's input, or its
+# shortcut's raw output); mid(mod, u, kept, k) -> the map behind the stem (mod the encoder, k = '_stem') or behind conv1
+# (mod the block, k = '1_<i>') from the raw output u; tail(block, u2, x, r, kept, i) -> block i's output from conv2's output,
+# the block's input x and the shortcut's raw output r (None without one).  kept is None outside keeping(): a norm may then
+# write in place; otherwise it leaves there what KEPT names: per kind the keys behind the walk's own (x, stem, t<i>, y<i>,
+# out) at the stem, in every block, in a block with a shortcut convolution.  _kept_keys spells them out.  _Norm has the
+# pieces of a kind that launches the folded packs bare and has no norm launch; a kind overrides what it does otherwise.
+#
+# Backward, what RAFTEncoder._walk_back asks: grad(...) -> six closures over one backward's state.  With a layer = (the key
+# of its record, of its convolution, of its norm, the two modules): weight(*layer) -> the weight its dgrad reads (and opens
+# its record); slots(ckey) -> (dw, db, accumulate) of its wgrad; put(*layer, dw, db, **launch): that wgrad's results into
+# grads, the launch's operands into the record; tail(key, G, i, shortcut) -> (conv2's cotangent, the shortcut's) in block i;
+# mid(nkey, g, ukey, skey) -> the cotangent at a raw convolution output (kept under ukey, its statistics under skey) from the
+# one behind its norm nkey and ReLU; mask(i, x) -> the ReLU mask of x, the input of block i (the head: the block count), as
+# keywords of the dgrad that produces x's cotangent.
+class _Norm:
+    """the forward pieces of a kind that launches ``packed`` with nothing in the epilogues and no norm behind them"""
+    rides, fused = {}, False
+
+    @staticmethod
+    def packs(mod):
+        return mod.packed
+
+    @staticmethod
+    def mid(mod, u, kept, k):
+        return u
+
+    @staticmethod
+    def tail(blk, u2, x, r, kept, i):
+        return u2
+
+
+class _FoldedBN(_Norm):
+    """BatchNorm on eval statistics: every layer is the folded convolution (W', b') of ``packed`` with the ReLU, and behind
+    conv2 the residual, in its epilogue; no norm launch at all.  A dgrad reads ``bn_fold``'s weight, and (dW', db') are
+    temporaries that ``bn_unfold`` carries to the four raw parameters"""
+    KEPT = dict(stem=(), block=(), shortcut=())
+    rides, fused = dict(act=ACT_RELU), True
+
+    @staticmethod
+    def grad(enc: 'RAFTEncoder', grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+        def weight(rkey, ckey, bkey, conv, bn):
+            wf, bf = ops.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
+            rec[rkey] = dict(wf=wf, bf=bf)
+            return wf
+
+        def put(rkey, ckey, bkey, conv, bn, dwf, dbf, **launch):
+            ks = [f'{prefix}{ckey}.weight', f'{prefix}{ckey}.bias', f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
+            res = ops.bn_unfold(conv.weight, conv.bias, bn.weight, bn.running_mean, bn.running_var, bn.eps, dwf, dbf,
+                                out=[dst[k] for k in ks], accumulate=acc)
+            grads.update(zip(ks, res))
+            rec[rkey].update(dwf=dwf, dbf=dbf, **launch)
+
+        # nothing sits between the convolution gradients: G is already the cotangent at a block's pre-ReLU sum, which conv2
+        # and the shortcut both read, because every dgrad masks with its layer's input (the layer in front ends in that ReLU)
+        return (weight, lambda ckey: (None, None, False), put, lambda key, G, i, shortcut: (G, G),
+                lambda nkey, g, ukey, skey: g, lambda i, x: dict(a=x, act=ACT_RELU))
+
+
+class _RawIN(_Norm):
+    """InstanceNorm (affine=False): the convolutions of ``packed``, which fold nothing, with ``ops.instance_norm`` behind
+    each, into the convolution's own output -- while keeping out of place (the same kernel on the same values, so the same
+    bits), because ``in_backward`` recomputes the statistics from the raw outputs.  Backward: the raw weights, (dW, db)
+    straight into their two ``_grad_slots`` destinations, and ``ops.instance_norm_grad`` between the convolution gradients"""
+    KEPT = dict(stem=('u_stem',), block=('u1_', 'u2_'), shortcut=('r',))
+
+    @staticmethod
+    def mid(mod, u, kept, k):
+        if kept is not None:
+            kept['u' + k] = u
+        return ops.instance_norm(u, relu=True, out=u if kept is None else None)
+
+    @staticmethod
+    def tail(blk, u2, x, r, kept, i):
+        if kept is None:
+            return ops.instance_norm(u2, res=x if r is None else r, relu=True, out=u2, res_norm=r is not None)
+        kept[f'u2_{i}'] = u2
+        if r is not None:
+            kept[f'r{i}'] = r
+        # the shortcut's raw output is normalised in a copy: the res_norm pass uses res as scratch
+        return ops.instance_norm(u2, res=x if r is None else r.clone(), relu=True, res_norm=r is not None)
+
+    @staticmethod
+    def grad(enc: 'RAFTEncoder', grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+        def weight(rkey, ckey, bkey, conv, bn):
+            rec[rkey] = {}
+            return conv.weight
+
+        def slots(ckey):
+            return dst[f'{prefix}{ckey}.weight'], dst[f'{prefix}{ckey}.bias'], acc
+
+        def put(rkey, ckey, bkey, conv, bn, dw, db, **launch):
+            grads[f'{prefix}{ckey}.weight'], grads[f'{prefix}{ckey}.bias'] = dw, db
+            rec[rkey].update(launch)
+
+        def tail(key, G, i, shortcut):
+            # G is the cotangent at the block's OUTPUT y: the tail form masks with y -> g' = G [y > 0], the shortcut's
+            # cotangent, and du2; behind a normalised shortcut (du2, dr)
+            y, u2 = got[f'y{i}'], got[f'u2_{i}']
+            if not shortcut:
+                g_sc, du2 = ops.instance_norm_grad(G, u2, y=y, eps=eps)
+                rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
+            else:
+                du2, g_sc = ops.instance_norm_grad(G, u2, y=y, r=got[f'r{i}'], eps=eps)
+                rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
+            return du2, g_sc
+
+        def mid(nkey, g, ukey, skey):
+            du = ops.instance_norm_grad(g, got[ukey], eps=eps)
+            rec[nkey] = dict(g=g, u=got[ukey], du=du)
+            return du
+
+        # only in front of block 0 the stem's output masks in the epilogue; elsewhere the tail form of the block in front masks
+        return weight, slots, put, tail, mid, lambda i, x: dict(a=x, act=ACT_RELU) if i == 0 else {}
+
+
+class _BatchBN(_Norm):
+    """BatchNorm on the statistics of the batch: the raw convolutions (``_raw_packs``) with ``ops.batch_norm_train`` behind
+    each, two more launches per norm than the folded form; it never writes in place (the backward reads the raw output),
+    moves the layer's running statistics and batch count, and keeps each layer's (2, C) mean / rstd next to its raw output.
+    Backward: ``_RawIN``'s (raw weights, unmasked joins, the stem's mask in front of block 0 only) with
+    ``ops.batch_norm_train_grad`` between the convolution gradients, on the kept statistics, and its (dgamma, dbeta) into
+    the slots of the norm's two parameters"""
+    KEPT = dict(stem=('u_stem', 's_stem'), block=('u1_', 'u2_', 's1_', 's2_'), shortcut=('r', 'sr'))
+
+    @staticmethod
+    def packs(mod):
+        return _raw_packs(mod, mod._convs())
+
+    @staticmethod
+    def mid(mod, u, kept, k):
+        t, s = _bn_step(mod.bn1, u, relu=True)
+        if kept is not None:
+            kept['u' + k], kept['s' + k] = u, s
+        return t
+
+    @staticmethod
+    def tail(blk, u2, x, r, kept, i):
         if r is None:
-            (out, s2), sr = _bn_step(self.bn2, u2, res=x, relu=True), None
+            out, s2 = _bn_step(blk.bn2, u2, res=x, relu=True)
         else:
-            out, s2, sr = _bn_step(self.bn2, u2, res=r, relu=True, res_bn=self._bn(self.downsample[1]))
-            self.downsample[1].num_batches_tracked += 1
+            bn_r = blk.downsample[1]
+            out, s2, sr = _bn_step(blk.bn2, u2, res=r, relu=True, res_bn=_bn_params(bn_r))
+            bn_r.num_batches_tracked += 1
         if kept is not None:
-            kept.append((t, out, u1, u2, r, s1, s2, sr))
+            kept[f'u2_{i}'], kept[f's2_{i}'] = u2, s2
+            if r is not None:
+                kept[f'r{i}'], kept[f'sr{i}'] = r, sr
         return out
 
+    @staticmethod
+    def grad(enc: 'RAFTEncoder', grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
+        weight, slots, put, _, _, mask = _RawIN.grad(enc, grads, dst, acc, rec, prefix, got, eps)
 
-# What RAFTEncoder._walk_back asks of the norm kind, six closures over one backward's state.  With a layer = (the key of its
-# record, of its convolution, of its norm, the two modules): weight(*layer) -> the weight its dgrad reads (and opens its
-# record); slots(ckey) -> (dw, db, accumulate) of its wgrad; put(*layer, dw, db, **launch): that wgrad's results into grads,
-# the launch's operands into the record; tail(key, G, i, shortcut) -> (conv2's cotangent, the shortcut's) in block i;
-# mid(rkey, g, ukey) -> the cotangent at a raw convolution output from the one behind its norm and ReLU; mask(i, x) -> the
-# ReLU mask of x, the input of block i (the head: the block count), as keywords of the dgrad that produces x's cotangent.
-def _folded_bn_grad(grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
-    """BatchNorm on eval statistics: every layer is the folded convolution (W', b'), so a dgrad reads ``bn_fold``'s weight,
-    and (dW', db') are temporaries that ``bn_unfold`` carries to the four raw parameters"""
-    def weight(rkey, ckey, bkey, conv, bn):
-        wf, bf = ops.bn_fold(conv.weight, conv.bias, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.eps)
-        rec[rkey] = dict(wf=wf, bf=bf)
-        return wf
+        def norm(bkey):
+            ks = [f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
+            return enc.get_submodule(bkey).weight, ks, [dst[k] for k in ks]
 
-    def put(rkey, ckey, bkey, conv, bn, dwf, dbf, **launch):
-        ks = [f'{prefix}{ckey}.weight', f'{prefix}{ckey}.bias', f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
-        res = ops.bn_unfold(conv.weight, conv.bias, bn.weight, bn.running_mean, bn.running_var, bn.eps, dwf, dbf,
-                            out=[dst[k] for k in ks], accumulate=acc)
-        grads.update(zip(ks, res))
-        rec[rkey].update(dwf=dwf, dbf=dbf, **launch)
+        def tail(key, G, i, shortcut):
+            y, u2 = got[f'y{i}'], got[f'u2_{i}']
+            gamma, ks, into = norm(f'{key}.bn2')
+            if not shortcut:
+                g_sc, du2, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, out=[None, None] + into,
+                                                           accumulate=acc)
+                rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
+            else:
+                gamma_r, ks_r, into_r = norm(f'{key}.downsample.1')
+                du2, g_sc, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, r=got[f'r{i}'],
+                                                           saved_r=got[f'sr{i}'], gamma_r=gamma_r,
+                                                           out=[None, None] + into + into_r, accumulate=acc)
+                rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
+                ks = ks + ks_r
+            grads.update(zip(ks, dp))
+            return du2, g_sc
 
-    # nothing sits between the convolution gradients: G is already the cotangent at a block's pre-ReLU sum, which conv2 and
-    # the shortcut both read, because every dgrad masks with its layer's input (the layer in front ends in that ReLU)
-    return (weight, lambda ckey: (None, None, False), put, lambda key, G, i, shortcut: (G, G), lambda rkey, g, ukey: g,
-            lambda i, x: dict(a=x, act=ACT_RELU))
+        def mid(nkey, g, ukey, skey):
+            gamma, ks, into = norm(nkey)
+            du, *dp = ops.batch_norm_train_grad(g, got[ukey], got[skey], gamma, out=[None] + into, accumulate=acc)
+            grads.update(zip(ks, dp))
+            rec[nkey] = dict(g=g, u=got[ukey], du=du)
+            return du
 
-
-def _raw_in_grad(grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
-    """InstanceNorm (affine=False): the raw weights, (dW, db) straight into their two ``_grad_slots`` destinations, and
-    ``ops.instance_norm_grad`` between the convolution gradients"""
-    def weight(rkey, ckey, bkey, conv, bn):
-        rec[rkey] = {}
-        return conv.weight
-
-    def slots(ckey):
-        return dst[f'{prefix}{ckey}.weight'], dst[f'{prefix}{ckey}.bias'], acc
-
-    def put(rkey, ckey, bkey, conv, bn, dw, db, **launch):
-        grads[f'{prefix}{ckey}.weight'], grads[f'{prefix}{ckey}.bias'] = dw, db
-        rec[rkey].update(launch)
-
-    def tail(key, G, i, shortcut):
-        # G is the cotangent at the block's OUTPUT y: the tail form masks with y -> g' = G [y > 0], the shortcut's cotangent,
-        # and du2; behind a normalised shortcut (du2, dr)
-        y, u2 = got[f'y{i}'], got[f'u2_{i}']
-        if not shortcut:
-            g_sc, du2 = ops.instance_norm_grad(G, u2, y=y, eps=eps)
-            rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
-        else:
-            du2, g_sc = ops.instance_norm_grad(G, u2, y=y, r=got[f'r{i}'], eps=eps)
-            rec[f'{key}.in2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
-        return du2, g_sc
-
-    def mid(rkey, g, ukey):
-        du = ops.instance_norm_grad(g, got[ukey], eps=eps)
-        rec[rkey] = dict(g=g, u=got[ukey], du=du)
-        return du
-
-    # only in front of block 0 the stem's output masks in the epilogue; elsewhere the tail form of the block in front masks
-    return weight, slots, put, tail, mid, lambda i, x: dict(a=x, act=ACT_RELU) if i == 0 else {}
+        return weight, slots, put, tail, mid, mask
 
 
-def _batch_bn_grad(enc: 'RAFTEncoder', grads: dict, dst: dict, acc: bool, rec: dict, prefix: str, got: dict, eps: float):
-    """BatchNorm on the statistics of the batch: ``_raw_in_grad`` (raw weights, unmasked joins, the stem's mask in front of
-    block 0 only) with ``ops.batch_norm_train_grad`` between the convolution gradients, on the (mean, rstd) the forward
-    kept, and its (dgamma, dbeta) into the slots of the norm's two parameters"""
-    weight, slots, put, _, _, mask = _raw_in_grad(grads, dst, acc, rec, prefix, got, eps)
+def _kept_keys(norm, blocks: Sequence['_BasicBlock'], out: bool = True) -> List[str]:
+    """The keys a forward of norm kind ``norm`` under ``keeping()`` leaves in ``RAFTEncoder.kept``, which are the keys the
+    kind's backward reads, for the encoder's blocks ``blocks``; ``out=False``: without the head's output, for a backward
+    whose caller passes it.
 
-    def norm(bkey):
-        ks = [f'{prefix}{bkey}.weight', f'{prefix}{bkey}.bias']
-        return enc.get_submodule(bkey).weight, ks, [dst[k] for k in ks]
-
-    def tail(key, G, i, shortcut):
-        y, u2 = got[f'y{i}'], got[f'u2_{i}']
-        gamma, ks, into = norm(f'{key}.bn2')
-        if not shortcut:
-            g_sc, du2, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, out=[None, None] + into,
-                                                       accumulate=acc)
-            rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, gp=g_sc, du=du2)
-        else:
-            gamma_r, ks_r, into_r = norm(f'{key}.downsample.1')
-            du2, g_sc, *dp = ops.batch_norm_train_grad(G, u2, got[f's2_{i}'], gamma, y=y, r=got[f'r{i}'],
-                                                       saved_r=got[f'sr{i}'], gamma_r=gamma_r,
-                                                       out=[None, None] + into + into_r, accumulate=acc)
-            rec[f'{key}.bn2'] = dict(g=G, y=y, u=u2, r=got[f'r{i}'], du=du2, dr=g_sc)
-            ks = ks + ks_r
-        grads.update(zip(ks, dp))
-        return du2, g_sc
-
-    def mid(rkey, g, ukey):
-        bkey = rkey[:-3] + 'bn1'                     # 'in1' -> 'bn1', '<block>.in1' -> '<block>.bn1'
-        gamma, ks, into = norm(bkey)
-        du, *dp = ops.batch_norm_train_grad(g, got[ukey], got['s' + ukey[1:]], gamma, out=[None] + into, accumulate=acc)
-        grads.update(zip(ks, dp))
-        rec[bkey] = dict(g=g, u=got[ukey], du=du)
-        return du
-
-    return weight, slots, put, tail, mid, mask
+    Every kind: x (the input image), stem (the stem's output), per block i t{i} (the post-ReLU conv1 output) and y{i} (the
+    block's output), and out (the head's post-activation output): what ``backward()`` reads.  The forward's own tensors; out
+    is a copy when the caller owns its destination.  An InstanceNorm encoder normalises out of place while keeping (same
+    bits) and adds what ``in_backward()`` reads: u_stem, u1_{i}, u2_{i} (the raw outputs of the stem and of a block's two
+    convolutions) and r{i} (the raw output of a shortcut convolution, i = 2, 4).  Under ``batch_stats()`` a BatchNorm
+    encoder leaves the InstanceNorm set plus each layer's (2, C) batch mean / rstd: s_stem, s1_{i}, s2_{i}, sr{i} -- what
+    ``bn_backward()`` reads."""
+    more = norm.KEPT
+    return (['x', 'stem', *more['stem']]
+            + [f'{k}{i}' for i in range(len(blocks)) for k in ('t', 'y') + more['block']]
+            + [f'{k}{i}' for i, blk in enumerate(blocks) if blk.downsample is not None for k in more['shortcut']]
+            + (['out'] if out else []))
 
 
 @ENCODERS.register_module()
@@ -457,17 +537,12 @@ class RAFTEncoder(HipModule):
             self.res_layers.append(f'res_layer{i}')
             inplanes = planes
         self.conv2 = nn.Conv2d(128, out_channels, 1)
-        # under keeping() a forward leaves in ``kept`` what backward() reads: x (the input image), stem (the stem's output), per
-        # block i = 0 .. 5 t{i} (the post-ReLU conv1 output) and y{i} (the block's output), and out (the head's
-        # post-activation output).  The forward's own tensors; out is a copy when the caller owns its destination.  Its own
-        # switch, not a level of SCFlowDecoder.keep; a forward outside keeping() empties it.  An InstanceNorm encoder
-        # normalises out of place while keeping (same bits) and adds what in_backward() reads: u_stem, u1_{i}, u2_{i} (the raw
-        # outputs of the stem and of a block's two convolutions) and r{i} (the raw output of a shortcut convolution, i = 2, 4)
+        # under keeping() a forward leaves in ``kept`` what the backward of its norm kind reads (_kept_keys).  Its own switch,
+        # not a level of SCFlowDecoder.keep; a forward outside keeping() empties it
         self.keep = False
         self.kept = {}
         # under batch_stats() a BatchNorm encoder normalises with the statistics of the batch and moves its running
-        # statistics (the reference's freeze_bn=False); while keeping it then leaves the InstanceNorm set (u_stem, u1_{i},
-        # u2_{i}, r{i}) plus each layer's (2, C) mean / rstd: s_stem, s1_{i}, s2_{i}, sr{i} -- what bn_backward() reads
+        # statistics (the reference's freeze_bn=False)
         self.batch = False
 
     @contextlib.contextmanager
@@ -496,70 +571,45 @@ class RAFTEncoder(HipModule):
         finally:
             self.keep = prev
 
+    def _convs(self) -> dict:
+        """the encoder's own convolutions under the keys of its packed sets"""
+        return dict(stem=self.conv1, head=self.conv2)
+
     def _pack(self):
         n1 = getattr(self, self.tag + '1')
-        bn = (n1.weight, n1.bias, n1.running_mean, n1.running_var) if self.kind == 'BN' else None
-        return dict(stem=PackedConv.from_weight(self.conv1.weight, self.conv1.bias,
-                                                self.stem_stride, 3, bn=bn, eps=n1.eps),
+        return dict(stem=PackedConv.from_weight(self.conv1.weight, self.conv1.bias, self.stem_stride, 3,
+                                                bn=_bn_params(n1), eps=n1.eps),
                     head=PackedConv.from_weight(self.conv2.weight, self.conv2.bias, 1, 0))
+
+    def _blocks(self) -> List[_BasicBlock]:
+        return [blk for name in self.res_layers for blk in getattr(self, name)]
+
+    def _norm(self):
+        """the norm kind the next forward runs"""
+        return _BatchBN if self.batch else (_FoldedBN if self.kind == 'BN' else _RawIN)
 
     def forward(self, x: Tensor, out: Optional[Tensor] = None, head_act: int = ACT_NONE,
                 head_act2: int = ACT_NONE, head_split: int = 0) -> Tensor:
-        """raft_encoder.py:286-314.  ``out`` / ``head_*`` let the caller have the 1x1 head
-        write (with a split tanh/relu epilogue) straight into a slice of a larger buffer."""
-        if self.batch:
-            return self._forward_batch_stats(x, out, head_act, head_act2, head_split)
-        p = self.packed
-        blocks = [] if self.keep else None
-        image = x
-        if self.kind == 'BN':
-            x = ops.conv2d(p['stem'], x, act=ACT_RELU)
-        else:
-            x = raw = ops.conv2d(p['stem'], x)
-            # keeping: out of place (the same kernel on the same values), the raw output stays for in_backward()
-            x = ops.instance_norm(raw, relu=True, out=None if self.keep else raw)
-        stem = x
-        for name in self.res_layers:
-            for blk in getattr(self, name):
-                x = blk(x, blocks)
-        y = ops.conv2d(p['head'], x, out=out, act=head_act, act2=head_act2,
-                       act_split=head_split)
-        self.kept = {} if blocks is None else self._kept_dict(image, stem, blocks, y, out is not None)
-        if blocks is not None and self.kind == 'IN':
-            self.kept['u_stem'] = raw
-        return y
-
-    def _forward_batch_stats(self, x: Tensor, out: Optional[Tensor], head_act: int, head_act2: int, head_split: int) -> Tensor:
-        """``forward`` under ``batch_stats()``: every layer is its raw convolution and ``ops.batch_norm_train``, two more
-        launches per norm than the folded form.  The folded packs go stale as the running statistics move, so they are
-        marked invalid here and the next eval forward folds again."""
-        p = _raw_packs(self, dict(stem=self.conv1, head=self.conv2))
-        blocks = [] if self.keep else None
-        raw = ops.conv2d(p['stem'], x)
-        stem, s_stem = _bn_step(self.bn1, raw, relu=True)
-        y = stem
-        for name in self.res_layers:
-            for blk in getattr(self, name):
-                y = blk._forward_batch_stats(y, blocks)
+        """raft_encoder.py:286-314, the one walk of the encoder: stem, blocks, 1x1 head, with whatever depends on the norm
+        from the norm kind (``_BasicBlock.forward``).  ``out`` / ``head_*`` let the caller have the 1x1 head write (with a
+        split tanh/relu epilogue) straight into a slice of a larger buffer."""
+        norm, blocks = self._norm(), self._blocks()
+        p = norm.packs(self)
+        kept = dict(x=x) if self.keep else None
+        u = ops.conv2d(p['stem'], x, **norm.rides)
+        y = norm.mid(self, u, kept, '_stem')
+        if kept is not None:
+            kept['stem'] = y
+        for i, blk in enumerate(blocks):
+            y = blk(y, norm, kept, i)
         y = ops.conv2d(p['head'], y, out=out, act=head_act, act2=head_act2, act_split=head_split)
-        for m in self.modules():
-            if isinstance(m, HipModule):
-                m.__dict__['_packed'] = None
-        self.kept = {} if blocks is None else self._kept_dict(x, stem, blocks, y, out is not None)
-        if blocks is not None:
-            self.kept.update(u_stem=raw, s_stem=s_stem)
+        if self.batch:
+            # the folded packs went stale as the running statistics moved: the next eval forward folds again
+            self._drop_folded()
+        if kept is not None:
+            kept['out'] = y.clone() if out is not None else y         # with the kind's entries: _kept_keys(norm, blocks)
+        self.kept = kept or {}
         return y
-
-    @staticmethod
-    def _kept_dict(image: Tensor, stem: Tensor, blocks, y: Tensor, clone_out: bool) -> dict:
-        kept = dict(x=image, stem=stem, out=y.clone() if clone_out else y)
-        for i, (t, o, *raws) in enumerate(blocks):
-            kept[f't{i}'], kept[f'y{i}'] = t, o
-            # an InstanceNorm block's raw convolution outputs; on batch statistics also each norm's (mean, rstd)
-            for k, v in zip(('u1_', 'u2_', 'r', 's1_', 's2_', 'sr'), raws):
-                if v is not None:
-                    kept[f'{k}{i}'] = v
-        return kept
 
     def _saved_for_backward(self, what: str, saved, keys: Sequence[str], nb: int, whose: str) -> Tuple[dict, tuple]:
         """(the entries ``keys`` of ``saved``, the shape of the head's output behind the last of ``nb`` blocks), or the
@@ -574,19 +624,19 @@ class RAFTEncoder(HipModule):
         y_last = got[f'y{nb - 1}']
         return got, (y_last.shape[0], self.out_channels) + tuple(y_last.shape[2:])
 
-    def _walk_back(self, what: str, norm_grad, got: dict, g_head: Tensor, param_grads: Optional[dict],
+    def _walk_back(self, what: str, norm, got: dict, g_head: Tensor, param_grads: Optional[dict],
                    intermediates: Optional[dict], prefix: str) -> dict:
-        """The one reverse walk behind ``backward`` and ``in_backward``: the 1x1 head from ``g_head`` (the cotangent at its
-        raw output), the blocks last to first (conv2, conv1, a down-sampling block's shortcut), the stem, on ``got`` (the
-        kept tensors, checked by the caller).  Whatever depends on the norm kind is one of ``norm_grad``'s six closures
-        (``_folded_bn_grad``, ``_raw_in_grad``)."""
+        """The one reverse walk behind ``backward``, ``bn_backward`` and ``in_backward``: the 1x1 head from ``g_head`` (the
+        cotangent at its raw output), the blocks last to first (conv2, conv1, a down-sampling block's shortcut), the stem,
+        on ``got`` (the kept tensors, checked by the caller).  Whatever depends on the norm kind is one of the six closures
+        of ``norm.grad`` (``_FoldedBN``, ``_RawIN``, ``_BatchBN``)."""
         names = [prefix + k for k, _ in self.named_parameters()]
         grads, dst, acc = _grad_slots(f'{what}: param_grads holds some of the encoder\'s gradients', names, param_grads)
         dst = dict(zip(names, dst))
         rec = {} if intermediates is None else intermediates
         tag = self.tag
-        weight, slots, put, tail, mid, mask = norm_grad(grads, dst, acc, rec, prefix, got, getattr(self, tag + '1').eps)
-        i = sum(len(getattr(self, name)) for name in self.res_layers)
+        weight, slots, put, tail, mid, mask = norm.grad(self, grads, dst, acc, rec, prefix, got, getattr(self, tag + '1').eps)
+        i = len(self._blocks())
         # ---- head: 1x1, no norm
         y_last, kw, kb = got[f'y{i - 1}'], f'{prefix}conv2.weight', f'{prefix}conv2.bias'
         grads[kw], grads[kb] = ops.conv_s1_wgrad(g_head, y_last, (1, 1), dw=dst[kw], db=dst[kb], accumulate=acc)
@@ -606,7 +656,7 @@ class RAFTEncoder(HipModule):
                 dw, db = ops.conv_s1_wgrad(g2, t, (3, 3), dw=dw, db=db, accumulate=into)
                 g_t = ops.conv_s1_dgrad(g2, w2, a=t, act=ACT_RELU)
                 put(*c2, dw, db, g=g2, x=t, gx=g_t)
-                g1 = mid(f'{key}.in1', g_t, f'u1_{i}')
+                g1 = mid(f'{key}.{tag}1', g_t, f'u1_{i}', f's1_{i}')
                 c1 = (f'{key}.conv1', f'{key}.conv1', f'{key}.{tag}1', blk.conv1, getattr(blk, tag + '1'))
                 w1 = weight(*c1)
                 dw, db, into = slots(c1[1])
@@ -626,7 +676,7 @@ class RAFTEncoder(HipModule):
                     G = ops.conv_ds_dgrad(g_sc, wd, in_hw, add=gx1, **mask(i, x_in))
                     put(*ds, dw, db, g=g_sc, x=x_in, add=gx1, gx=G)
         # ---- stem: G carries the ReLU mask of the stem's output; the image needs no gradient
-        g0 = mid('in1', G, 'u_stem')
+        g0 = mid(f'{tag}1', G, 'u_stem', 's_stem')
         rec['conv1'] = {}
         dw, db, into = slots('conv1')
         dw, db = ops.conv_stem_wgrad(g0, got['x'], dw=dw, db=db, accumulate=into)
@@ -660,18 +710,16 @@ class RAFTEncoder(HipModule):
             raise NotImplementedError(f'{what}: this is the BatchNorm chain; the InstanceNorm feature encoder\'s is '
                                       'RAFTEncoder.in_backward, which takes a cotangent at the encoder\'s output -- the '
                                       'correlation-build backward (SCFlowDecoder.corr_backward) produces it')
-        nb = sum(len(getattr(self, name)) for name in self.res_layers)
-        keys = ['x', 'stem'] + [f'{k}{i}' for i in range(nb) for k in 'ty']
-        got, u = self._head_cotangent(what, saved, keys, 'a forward', g_out, out, head_act, head_act2, head_split)
-        return self._walk_back(what, _folded_bn_grad, got, u, param_grads, intermediates, prefix)
+        got, u = self._head_cotangent(what, _FoldedBN, saved, 'a forward', g_out, out, head_act, head_act2, head_split)
+        return self._walk_back(what, _FoldedBN, got, u, param_grads, intermediates, prefix)
 
-    def _head_cotangent(self, what: str, saved, keys: list, whose: str, g_out, out: Optional[Tensor], head_act: int,
+    def _head_cotangent(self, what: str, norm, saved, whose: str, g_out, out: Optional[Tensor], head_act: int,
                         head_act2: int, head_split: int) -> Tuple[dict, Tensor]:
-        """what ``backward`` and ``bn_backward`` do in front of the walk: (the entries ``keys`` of ``saved``, the cotangent
-        at the 1x1 head's raw output from ``g_out`` through the head's activation(s))"""
-        nb = sum(len(getattr(self, name)) for name in self.res_layers)
-        keys = keys + ([] if out is not None else ['out'])
-        got, shape = self._saved_for_backward(what, saved, keys, nb, whose)
+        """what ``backward`` and ``bn_backward`` do in front of the walk: (the entries of ``saved`` that the norm kind
+        keeps, with the head's output where the caller passes none; the cotangent at the 1x1 head's raw output from
+        ``g_out`` through the head's activation(s))"""
+        blocks = self._blocks()
+        got, shape = self._saved_for_backward(what, saved, _kept_keys(norm, blocks, out=out is None), len(blocks), whose)
         if out is None:
             out = got['out']
         n, co = shape[:2]
@@ -717,13 +765,9 @@ class RAFTEncoder(HipModule):
         what = 'RAFTEncoder.bn_backward'
         if self.kind != 'BN':
             raise NotImplementedError(f'{what}: an InstanceNorm encoder takes RAFTEncoder.in_backward')
-        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
-        keys = (['x', 'stem', 'u_stem', 's_stem']
-                + [f'{k}{i}' for i in range(len(blocks)) for k in ('t', 'y', 'u1_', 'u2_', 's1_', 's2_')]
-                + [f'{k}{i}' for i, blk in enumerate(blocks) if blk.downsample is not None for k in ('r', 'sr')])
-        got, u = self._head_cotangent(what, saved, keys, 'a forward under batch_stats()', g_out, out, head_act, head_act2,
+        got, u = self._head_cotangent(what, _BatchBN, saved, 'a forward under batch_stats()', g_out, out, head_act, head_act2,
                                       head_split)
-        return self._walk_back(what, partial(_batch_bn_grad, self), got, u, param_grads, intermediates, prefix)
+        return self._walk_back(what, _BatchBN, got, u, param_grads, intermediates, prefix)
 
     def in_backward(self, saved: dict, g_out: Tensor, param_grads: Optional[dict] = None,
                     intermediates: Optional[dict] = None, prefix: str = ''):
@@ -752,14 +796,13 @@ class RAFTEncoder(HipModule):
         what = 'RAFTEncoder.in_backward'
         if self.kind != 'IN':
             raise NotImplementedError(f'{what}: a BatchNorm encoder takes RAFTEncoder.backward (eval statistics, folded)')
-        blocks = [blk for name in self.res_layers for blk in getattr(self, name)]
-        keys = (['x', 'stem', 'u_stem'] + [f'{k}{i}' for i in range(len(blocks)) for k in ('t', 'y', 'u1_', 'u2_')]
-                + [f'r{i}' for i, blk in enumerate(blocks) if blk.downsample is not None])
-        got, shape = self._saved_for_backward(what, saved, keys, len(blocks), "an InstanceNorm encoder's forward")
+        blocks = self._blocks()
+        got, shape = self._saved_for_backward(what, saved, _kept_keys(_RawIN, blocks, out=False), len(blocks),
+                                              "an InstanceNorm encoder's forward")
         if not isinstance(g_out, torch.Tensor) or tuple(g_out.shape) != shape:
             raise _lib_error(f'{what}: g_out must be a {shape} tensor, got '
                              f'{tuple(g_out.shape) if isinstance(g_out, torch.Tensor) else type(g_out).__name__}')
-        return self._walk_back(what, _raw_in_grad, got, g_out, param_grads, intermediates, prefix)   # the head has no activation
+        return self._walk_back(what, _RawIN, got, g_out, param_grads, intermediates, prefix)   # the head has no activation
 
 
 def encoder_pair_supported(fe: 'RAFTEncoder', ce: 'RAFTEncoder') -> bool:

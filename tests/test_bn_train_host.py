@@ -509,6 +509,39 @@ def test_switches_are_off_by_default_and_refuse_by_name():
         ops.batch_norm_train(torch.zeros(2, 1, 2, 2), torch.ones(1), torch.zeros(1), None, None, momentum=None)
 
 
+def test_kept_keys_of_the_three_norm_kinds():
+    """what a keeping forward leaves and a backward reads, per norm kind: the sets as tests/test_gpu_context_grad.py,
+    tests/test_gpu_feature_grad.py (KEPT_KEYS) and tests/test_gpu_bn_train.py (KEPT_KEYS) assert them on the GPU, stated
+    here again and not taken from the module"""
+    from scflow_amd import modules
+    from scflow_amd.modules import RAFTEncoder
+    walk = ['x', 'stem', 'out'] + [f'{k}{i}' for i in range(6) for k in ('t', 'y')]
+    raw = ['u_stem', 'r2', 'r4'] + [f'{k}{i}' for i in range(6) for k in ('u1_', 'u2_')]
+    stats = ['s_stem', 'sr2', 'sr4'] + [f'{k}{i}' for i in range(6) for k in ('s1_', 's2_')]
+    assert len(walk) == 15 and len(raw) == 15 and len(stats) == 15
+    ctx, feat = (RAFTEncoder(3, 8, norm_cfg=dict(type=kind)) for kind in ('BN', 'IN'))
+    for enc, norm, want in ((ctx, modules._FoldedBN, walk), (feat, modules._RawIN, walk + raw),
+                            (ctx, modules._BatchBN, walk + raw + stats)):
+        keys = modules._kept_keys(norm, enc._blocks())
+        assert sorted(keys) == sorted(want) and len(set(keys)) == len(keys), norm.__name__
+        # a backward whose caller passes the head's output reads the rest
+        assert modules._kept_keys(norm, enc._blocks(), out=False) == [k for k in keys if k != 'out']
+    # the kind a forward runs follows the encoder's norm and its batch_stats() switch
+    assert feat._norm() is modules._RawIN and ctx._norm() is modules._FoldedBN
+    with ctx.batch_stats():
+        assert ctx._norm() is modules._BatchBN
+    assert ctx._norm() is modules._FoldedBN
+    # the shortcut keys follow the blocks that have a shortcut convolution
+    assert [i for i, blk in enumerate(ctx._blocks()) if blk.downsample is not None] == [2, 4]
+    # the error of a backward names exactly these keys
+    from scflow_amd._lib import ScflowHipError
+    for enc, back, norm, out in ((ctx, ctx.backward, modules._FoldedBN, True), (ctx, ctx.bn_backward, modules._BatchBN, True),
+                                 (feat, feat.in_backward, modules._RawIN, False)):
+        with pytest.raises(ScflowHipError) as err:
+            back({}, torch.zeros(1))
+        assert f"saved holds {', '.join(modules._kept_keys(norm, enc._blocks(), out=out))}: RAFTEncoder.kept" in str(err.value)
+
+
 def test_train_step_still_refuses_freeze_bn_false():
     """the additive contract: the old entry point and its words are as they were"""
     from scflow_amd import optim

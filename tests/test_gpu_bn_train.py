@@ -2,6 +2,7 @@
 restatement and the derived bound of tests/test_bn_train_host.py on every route of batch_norm_train.hip;
 RAFTEncoder.batch_stats() / bn_backward against float64 autograd of a plain-torch restatement written here;
 SCFlowRefiner.batch_norm_training() and train_step_network on the shipped flags."""
+import contextlib
 import json
 import os
 
@@ -10,7 +11,7 @@ import pytest
 import torch
 
 import scflow_amd
-from scflow_amd import ops, optim
+from scflow_amd import modules, ops, optim
 from scflow_amd._lib import ScflowHipError
 from scflow_amd.modules import RAFTEncoder, _bn_step
 from scflow_amd.ops import ACT_RELU
@@ -406,6 +407,110 @@ def folded_forward(enc, x):
                 t, idt = ops.conv2d(p['c1'], y, act=ACT_RELU), y
             y = ops.conv2d(p['c2'], t, res=idt, act=ACT_RELU)
     return ops.conv2d(enc.packed['head'], y)
+
+
+def raw_packs(enc):
+    """every convolution of the encoder packed without the norm behind it, keyed by the nn.Conv2d"""
+    convs = [enc.conv1, enc.conv2] + [m for name in enc.res_layers for blk in getattr(enc, name)
+                                      for m in (blk.conv1, blk.conv2) + (() if blk.downsample is None else (blk.downsample[0],))]
+    return {c: ops.PackedConv.from_weight(c.weight, c.bias, c.stride[0], c.padding) for c in convs}
+
+
+def batch_stats_forward(enc, p, x):
+    """the forward under batch_stats() and keeping() as the parent commit launches it: ops.conv2d / conv2d_pair on the raw
+    packs ``p``, ops.batch_norm_train behind each, layer by layer -> (the head's output, what the forward keeps)"""
+    def norm(bn, u, **form):
+        res = ops.batch_norm_train(u, bn.weight, bn.bias, bn.running_mean, bn.running_var, bn.momentum, bn.eps, **form)
+        bn.num_batches_tracked += 1
+        return res
+
+    kept = dict(x=x, u_stem=ops.conv2d(p[enc.conv1], x))
+    kept['stem'], kept['s_stem'] = norm(enc.bn1, kept['u_stem'], relu=True)
+    y = kept['stem']
+    for i, blk in enumerate(blk for name in enc.res_layers for blk in getattr(enc, name)):
+        if blk.downsample is not None:
+            u1, r = ops.conv2d_pair((p[blk.conv1], y), (p[blk.downsample[0]], y))
+        else:
+            u1, r = ops.conv2d(p[blk.conv1], y), None
+        t, s1 = norm(blk.bn1, u1, relu=True)
+        u2 = ops.conv2d(p[blk.conv2], t)
+        if r is None:
+            y, s2 = norm(blk.bn2, u2, res=y, relu=True)
+        else:
+            d = blk.downsample[1]
+            y, s2, sr = norm(blk.bn2, u2, res=r, relu=True, res_bn=(d.weight, d.bias, d.running_mean, d.running_var))
+            d.num_batches_tracked += 1
+            kept[f'r{i}'], kept[f'sr{i}'] = r, sr
+        kept.update({f't{i}': t, f'y{i}': y, f'u1_{i}': u1, f'u2_{i}': u2, f's1_{i}': s1, f's2_{i}': s2})
+    kept['out'] = ops.conv2d(p[enc.conv2], y)
+    return kept['out'], kept
+
+
+def recorded(fn):
+    """fn() -> (its result, (ran, paired, variants) of ops.record_conv_kernels around it)"""
+    rec = ops.record_conv_kernels()
+    with rec:
+        res = fn()
+    return res, (rec.ran, rec.paired, rec.variants)
+
+
+def no_shared_storage(kept):
+    ptrs = [v.data_ptr() for v in kept.values()]
+    return len(set(ptrs)) == len(ptrs)
+
+
+@pytest.mark.parametrize('n', [1, 3])
+@pytest.mark.parametrize('hw', [(18, 26), (16, 24)], ids=lambda v: f'{v[0]}x{v[1]}')
+def test_forward_modes_launch_what_the_lists_do(hw, n):
+    """the BatchNorm encoder's four forward modes against the launch lists above: the bits of the output and of every kept
+    tensor, the convolution routes, the moved statistics; 18 x 26 has 3 x 4 planes at the coarsest level (HW % 4 != 0)"""
+    sd = CH.encoder_params(FH.CASE_SEED, prefix='')
+    x = D(CH.encoder_inputs(FH.CASE_SEED, n, *hw, tag='.bn_train')[0])
+    folded_keys = sorted(['x', 'stem', 'out'] + [f'{k}{i}' for i in range(6) for k in ('t', 'y')])
+
+    def forward(enc, keep, batch):
+        with (enc.batch_stats() if batch else contextlib.nullcontext()), (enc.keeping() if keep else contextlib.nullcontext()):
+            return enc(x), dict(enc.kept)
+
+    # folded on the running statistics, plain and keeping
+    enc = build_encoder(sd)
+    want, routes = recorded(lambda: folded_forward(enc, x))
+    for keep in (False, True):
+        (y, kept), ran = recorded(lambda: forward(enc, keep, False))
+        assert same_bits(y, want) and ran == routes, keep
+        assert sorted(kept) == (folded_keys if keep else [])
+        assert not keep or sorted(kept) == sorted(modules._kept_keys(modules._FoldedBN, enc._blocks()))
+        if keep:
+            assert kept['x'] is x and kept['out'] is y and no_shared_storage(kept)
+            assert same_bits(ops.conv2d(enc.packed['head'], kept['y5']), want)
+    assert all(int(v) == 0 for k, v in enc.state_dict().items() if k.endswith('num_batches_tracked'))
+    # on the statistics of the batch, plain and keeping: each against the list run on a second module of the same state
+    for keep in (False, True):
+        enc, ref = build_encoder(sd), build_encoder(sd)
+        packs = raw_packs(ref)
+        (want, want_kept), routes = recorded(lambda: batch_stats_forward(ref, packs, x))
+        (y, kept), ran = recorded(lambda: forward(enc, keep, True))
+        assert same_bits(y, want) and ran == routes, keep
+        assert sorted(kept) == (KEPT_KEYS if keep else [])
+        assert not keep or sorted(kept) == sorted(modules._kept_keys(modules._BatchBN, enc._blocks()))
+        assert all(same_bits(kept[k], want_kept[k]) for k in kept)
+        if keep:
+            assert kept['x'] is x and kept['out'] is y and no_shared_storage(kept)
+        now, ref_now = enc.state_dict(), ref.state_dict()
+        stats = [k for k in now if 'running_' in k]
+        counts = [k for k in now if k.endswith('num_batches_tracked')]
+        assert len(stats) == 30 and len(counts) == 15 and len(now) == len(stats) + len(counts) + 62
+        assert all(same_bits(now[k], ref_now[k]) and not same_bits(now[k], D(sd[k])) for k in stats)
+        assert all(int(now[k]) == int(ref_now[k]) == 1 for k in counts)
+        assert all(same_bits(now[k], D(sd[k])) for k in now if k not in stats and k not in counts)
+    # a caller-owned destination: the kept output is a copy of it
+    guard = Guarded()
+    dest = guard(tuple(want.shape))
+    with enc.batch_stats(), enc.keeping():
+        y = enc(x, out=dest)
+    guard.check()
+    assert y.data_ptr() == dest.data_ptr() and enc.kept['out'].data_ptr() != y.data_ptr()
+    assert same_bits(enc.kept['out'], y) and no_shared_storage(enc.kept)
 
 
 def test_eval_forward_is_unchanged_and_follows_the_moved_statistics(encoder_run):

@@ -10,7 +10,7 @@ import pytest
 import torch
 
 import scflow_amd
-from scflow_amd import ops
+from scflow_amd import modules, ops
 from scflow_amd._lib import ScflowHipError
 from scflow_amd.modules import RAFTEncoder
 import test_feature_grad_host as FH
@@ -157,6 +157,104 @@ def keep_forward(enc, x):
 
 
 KEPT_KEYS = sorted(['x', 'stem', 'u_stem', 'out', 'r2', 'r4'] + [f'{k}{i}' for i in range(6) for k in ('t', 'y', 'u1_', 'u2_')])
+
+
+def in_place_forward(enc, x):
+    """the InstanceNorm forward outside keeping() as the parent commit launches it: every normalisation into the
+    convolution's own output, the shortcut's inside the block's final pass"""
+    def block(q, y):                                                # a block's tensors live as long as the block runs
+        if 'ds' in q:
+            t, idt = ops.conv2d_pair((q['c1'], y), (q['ds'], y))
+        else:
+            t, idt = ops.conv2d(q['c1'], y), y
+        ops.instance_norm(t, relu=True, out=t)
+        u2 = ops.conv2d(q['c2'], t)
+        return ops.instance_norm(u2, res=idt, relu=True, out=u2, res_norm='ds' in q)
+
+    p = enc.packed
+    y = ops.conv2d(p['stem'], x)
+    stem = ops.instance_norm(y, relu=True, out=y)                   # the stem's output lives to the end of the forward
+    for name in enc.res_layers:
+        for blk in getattr(enc, name):
+            y = block(blk.packed, y)
+    out = ops.conv2d(p['head'], y)
+    del stem
+    return out
+
+
+def out_of_place_forward(enc, x):
+    """the InstanceNorm forward under keeping() as the parent commit launches it: the same launches with every
+    normalisation out of place, a shortcut's raw output normalised in a copy -> (the head's output, what it keeps)"""
+    p = enc.packed
+    kept = dict(x=x, u_stem=ops.conv2d(p['stem'], x))
+    y = kept['stem'] = ops.instance_norm(kept['u_stem'], relu=True)
+    for i, blk in enumerate(blk for name in enc.res_layers for blk in getattr(enc, name)):
+        q = blk.packed
+        if 'ds' in q:
+            u1, r = ops.conv2d_pair((q['c1'], y), (q['ds'], y))
+            kept[f'r{i}'] = r
+        else:
+            u1, r = ops.conv2d(q['c1'], y), None
+        t = ops.instance_norm(u1, relu=True)
+        u2 = ops.conv2d(q['c2'], t)
+        y = ops.instance_norm(u2, res=y if r is None else r.clone(), relu=True, res_norm=r is not None)
+        kept.update({f't{i}': t, f'y{i}': y, f'u1_{i}': u1, f'u2_{i}': u2})
+    kept['out'] = ops.conv2d(p['head'], y)
+    return kept['out'], kept
+
+
+def recorded(fn):
+    """fn() -> (its result, (ran, paired, variants) of ops.record_conv_kernels around it)"""
+    rec = ops.record_conv_kernels()
+    with rec:
+        res = fn()
+    return res, (rec.ran, rec.paired, rec.variants)
+
+
+def peak_over_baseline(fn):
+    """the most device memory allocated during fn() over what was allocated before it"""
+    torch.cuda.synchronize()
+    base = torch.cuda.memory_allocated()
+    torch.cuda.reset_peak_memory_stats()
+    res = fn()
+    torch.cuda.synchronize()
+    del res
+    return torch.cuda.max_memory_allocated() - base
+
+
+@pytest.mark.parametrize('n', [1, 3])
+@pytest.mark.parametrize('hw', [(18, 26), (16, 24)], ids=lambda v: f'{v[0]}x{v[1]}')
+def test_forward_modes_launch_what_the_lists_do(hw, n):
+    """the InstanceNorm encoder's two forward modes against the launch lists above: the bits of the output and of every
+    kept tensor, the convolution routes, and what may alias; 18 x 26 has 3 x 4 planes at the coarsest level (HW % 4 != 0)"""
+    sd = FH.encoder_params(FH.CASE_SEED)
+    x = D(FH.encoder_inputs(FH.CASE_SEED, n, *hw)[0])
+    enc = build_encoder(sd)
+    want, routes = recorded(lambda: in_place_forward(enc, x))
+    y, ran = recorded(lambda: enc(x))
+    assert same_bits(y, want) and ran == routes and enc.kept == {}
+    (want_k, want_kept), routes_k = recorded(lambda: out_of_place_forward(enc, x))
+    (y_k, kept), ran_k = recorded(lambda: keep_forward(enc, x))
+    assert same_bits(y_k, want_k) and same_bits(y_k, want) and ran_k == routes_k == routes
+    assert sorted(kept) == sorted(want_kept) == KEPT_KEYS and all(same_bits(kept[k], want_kept[k]) for k in kept)
+    assert sorted(kept) == sorted(modules._kept_keys(modules._RawIN, enc._blocks()))
+    # keeping: no raw output shares storage with its normalised map, nor any kept tensor with another; the output is the
+    # forward's own unless the caller owns its destination, then a copy
+    ptrs = [v.data_ptr() for v in kept.values()]
+    assert len(set(ptrs)) == len(ptrs) and kept['x'] is x and kept['out'] is y_k
+    dest = torch.empty_like(want)
+    with enc.keeping():
+        y_d = enc(x, out=dest)
+    ptrs = [v.data_ptr() for v in enc.kept.values()]
+    assert y_d.data_ptr() == dest.data_ptr() and dest.data_ptr() not in ptrs and len(set(ptrs)) == len(ptrs)
+    assert same_bits(enc.kept['out'], dest) and same_bits(dest, want)
+    # plain: the norms write into the convolutions' own outputs, so the forward allocates no more than the list does
+    del y, y_k, kept, want_k, want_kept, y_d
+    enc(x)
+    assert enc.kept == {}
+    peak, peak_list = peak_over_baseline(lambda: enc(x)), peak_over_baseline(lambda: in_place_forward(enc, x))
+    measured(f'RAFTEncoder forward {hw} N {n}, in place: peak bytes over the baseline, module / list', peak / peak_list)
+    assert 0 < peak <= peak_list
 
 
 def compare_composed(tag, grads, saved, x, sd, g_out, prefix=''):
