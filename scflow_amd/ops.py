@@ -25,7 +25,7 @@ from ._lib import (ACT_NONE, ACT_RELU, ACT_SIGMOID, ACT_TANH, CONV_GRU_Q, CONV_G
 
 Tensor = torch.Tensor
 
-__all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scflow_iteration', 'side_stream_handle', 'pyramid_layout', 'untile_level', 'level_storage_shape', 'sepconv_gru', 'pack_conv_weight', 'pack_conv_weight_f16x3', 'set_conv_precision', 'set_conv_winograd', 'get_conv_winograd', 'pack_conv_weight_wino', 'pack_conv_weight_wino1d', 'pack_conv_weight_wino1d4',
+__all__ = ['record_conv_kernels', 'PackedConv', 'conv_desc', 'gru_passes', 'scflow_iteration', 'side_stream_handle', 'pyramid_layout', 'untile_level', 'level_storage_shape', 'sepconv_gru', 'pack_conv_weight', 'pack_conv_weight_f16x3', 'f16x3_weight_excess', 'set_conv_precision', 'set_conv_winograd', 'get_conv_winograd', 'pack_conv_weight_wino', 'pack_conv_weight_wino1d', 'pack_conv_weight_wino1d4',
            'get_conv_precision', 'set_conv_kslices', 'conv_kslices', 'conv_kslices_for', 'constant', 'clear_constants', 'register_conv_workspace', 'choose_kc', 'conv2d', 'conv2d_pair', 'corr_build', 'corr_lookup',
            'instance_norm', 'group_norm_relu', 'linear', 'fc_splitk', 'fc_slices', 'pose_update', 'reproject_flow',
            'flow_corr_2d3d', 'pnp_params', 'pnp_ransac', 'pnp',
@@ -253,6 +253,28 @@ def pack_conv_weight_f16x3(weight: Tensor) -> Tensor:
     return out.reshape(nchunk * t * 2, 2, mld, 8).contiguous()
 
 
+F16X3_WEIGHT_EXCESS_MAX = 2.0
+
+
+def f16x3_weight_excess(weight: Tensor) -> float:
+    """how far a layer's weights are outside the split's domain: with w = hi + w_l + e_w (hi = fp16(w), w_l = lo' 2**-11,
+    lo' = fp16((w - hi) 2**11), roundings on the host: nearest even, fp16 subnormals kept), the worst output channel's
+    (sum |e_w| + 2**-11 sum |w_l|) / (2**-22 sum |w|); 0 for an all-zero channel, inf where some hi is not finite.  For
+    weights in 2**-14 <= |w| < 65520 both terms are bounded by 2**-22 |w|, so the figure is at most 2
+    (``F16X3_WEIGHT_EXCESS_MAX``); it grows as 2**-14 / |w| below that (843 units of 2**-24 sum|w||x| measured on weights
+    of 1e-6 by the host restatement, tests/test_conv_f16x3_host.py)."""
+    w = weight.detach().to('cpu', torch.float32)
+    hi = w.half().float()
+    lo = ((w - hi) * 2048.0).half().double()
+    w, hi = w.double(), hi.double()
+    e = w - hi - lo / 2048.0
+    num = (e.abs() + lo.abs() / (2048.0 * 2048.0)).flatten(1).sum(1)
+    den = 2.0 ** -22 * w.abs().flatten(1).sum(1)
+    ratio = torch.where(num == 0, torch.zeros_like(num), num / den)
+    ratio = torch.where(torch.isfinite(ratio), ratio, torch.full_like(ratio, float('inf')))
+    return float(ratio.max())
+
+
 def choose_a4_groups(cin: int, kh: int, kw: int, stride: int) -> int:
     """8G channels per staged chunk of the LDS-DMA kernel (0: layer not eligible)."""
     t = kh * kw
@@ -390,6 +412,16 @@ def set_conv_precision(mode: str) -> str:
     'f16x3' : spatial convolutions with >= 16 input channels run on the fp16 matrix cores as
               three MFMAs over an exact hi/lo split of both operands (fp32 accumulate, ~22
               mantissa bits; flow EPE ~1e-4 px vs fp32 on this path), everything else fp32.
+    The contract of 'f16x3' (tests/test_conv_f16x3_host.py derives it, tests/test_gpu_conv_f16x3.py holds the kernel to it):
+      * operands with 2**-14 <= |v| <= 65504 (or 0): |result - true| <= (3 + 2**-22) 2**-22 sum|w||x| on top of the fp32
+        accumulation error (K + 1) 2**-24 sum|w||x| -- fp32 class;
+      * below 2**-14 the split's error stops shrinking with the operand (<= 2**-25 per half, 2**-36 left over, absolute):
+        results degrade gracefully, a layer whose operands are all near 1e-6 keeps about five bits.  WEIGHTS are checked at
+        pack time (``f16x3_weight_excess``): ``PackedConv.from_weight`` gives such a layer no split packing and it runs on the
+        fp32 kernels (``record_conv_kernels`` shows which); activations cannot be checked before the launch;
+      * a finite activation of 65520 or more becomes an infinite high half: every output of its receptive field, in every
+        output channel, is non-finite (a ReLU epilogue, compare + select, turns NaN and -inf into 0), and nothing outside the
+        field changes by a bit (the fp32 routes return finite numbers).
     Returns the previous mode."""
     global _CONV_PRECISION
     if mode not in ('f32', 'f16x3'):
@@ -446,7 +478,10 @@ class PackedConv:
         kc = choose_kc(cin, kh, kw, stride)
         wp, mld = pack_conv_weight(weight, kc)
         wp_alt = pack_conv_weight(weight, 32)[0] if (kc == 8 and cin >= 32) else None
-        wp16 = pack_conv_weight_f16x3(weight) if (cin >= 16 and kh * kw > 1) else None
+        # the split-fp16 route only for weights inside the split's domain (f16x3_weight_excess): a layer of tiny or
+        # over-range weights keeps wp16 = None and runs on the fp32 kernels under every conv precision
+        wp16 = pack_conv_weight_f16x3(weight) if (cin >= 16 and kh * kw > 1 and
+                                                  f16x3_weight_excess(weight) <= F16X3_WEIGHT_EXCESS_MAX) else None
         ph, pw = (padding, padding) if isinstance(padding, int) else padding
         scale = shift = None
         if bn is not None:

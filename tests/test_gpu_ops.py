@@ -1116,24 +1116,53 @@ F16_CASES += [(2, 128, 128, (3, 3), 1, (1, 1), 60, 80),     # 16-column fragment
 
 @pytest.mark.parametrize('case', F16_CASES)
 def test_conv2d_f16x3(case):
-    """fp32-class accuracy of the split-fp16 kernel: error vs fp64 must stay within a small
-    multiple of the fp32 kernel's own error (both ~1e-6 relative to the output scale)."""
-    n, cin, cout, k, s, p, H, W = case
-    x = rnd((n, cin, H, W), 10)
+    """the split-fp16 kernel per element, no tensor-wide scale and no floor (tests/test_conv_f16x3_host.py): within B_acc of
+    its specification ``f16x3_ref64`` and within B_acc + B_model of float64, on the first sample; where the launch goes to an
+    fp32 family under 'f16x3' (stride 2, thin outputs) within the fp32 bound.  The tensor-wide statement the test used to make
+    still holds over all samples."""
+    import ctypes as C
+    import test_conv_exact_host as H
+    import test_conv_f16x3_host as X
+    n, cin, cout, k, s, p, Hh, W = case
+    x = rnd((n, cin, Hh, W), 10)
     wt = rnd((cout, cin, *k), 11, (1.0 / (cin * k[0] * k[1])) ** 0.5)
     b = rnd((cout,), 12, 0.1)
     ref64 = torch.relu(F.conv2d(x.double(), wt.double(), b.double(), stride=s, padding=p))
     pc = ops.PackedConv.from_weight(wt.to(DEV), b.to(DEV), stride=s, padding=p)
+    assert pc.wp16 is not None
     got32 = ops.conv2d(pc, x.to(DEV), act=ops.ACT_RELU).cpu().double()
     prev = ops.set_conv_precision('f16x3')
     try:
-        got16 = ops.conv2d(pc, x.to(DEV), act=ops.ACT_RELU).cpu().double()
+        d, _ = ops.conv_desc(pc, x.to(DEV), act=ops.ACT_RELU)
+        info = (C.c_int32 * 4)()
+        assert ops._lib.load().scf_conv2d_query(C.byref(d), info) == 0
+        with ops.record_conv_kernels() as ran:
+            got16 = ops.conv2d(pc, x.to(DEV), act=ops.ACT_RELU).cpu().double()
     finally:
         ops.set_conv_precision(prev)
+    fams = {f for _, f in ran}
     e32 = float((got32 - ref64).abs().max())
     e16 = float((got16 - ref64).abs().max())
     scale = float(ref64.abs().max())
     assert e16 <= 4e-6 * scale + 1e-6, f'{case}: f16x3 err {e16:.2e} (fp32 kernel {e32:.2e}, scale {scale:.2f})'
+    split = fams == {'f16x3'}
+    row = H.Row(str(case), n, cin, cout, k, s, p, Hh, W, 0, dict(f16=True), 'f16x3' if split else 'fp32',
+                tuple(info) if split else (1, 1, 1, -1), '')
+    spec = X.variants(row)['bias_relu']
+    one = slice(0, 1)
+    opnd = dict(x=x, w=wt, b=b)
+    err = lambda want: (got16[one] - want).abs()
+    if split:
+        bd = X.bounds(row, opnd, spec, one)
+        in_acc, in_true = err(bd['ref']) <= bd['b_acc'], err(bd['true']) <= bd['b_acc'] + bd['b_model']
+        print(f"[measured] {case} <{X.instantiation(row)}>: {float((err(bd['ref']) / bd['b_acc']).max()):.3f} of B_acc, "
+              f"{float((err(bd['true']) / (bd['b_acc'] + bd['b_model'])).max()):.3f} of B_acc + B_model")
+        assert bool(in_acc.all()), f'{case}: {int((~in_acc).sum())} elements outside B_acc of the specification'
+        assert bool(in_true.all()), f'{case}: {int((~in_true).sum())} elements outside B_acc + B_model of float64'
+    else:
+        assert 'f16x3' not in fams, fams
+        lim = X.fp32_bound(row, opnd, spec, one)
+        assert bool((err(ref64[one]) <= lim).all()), f'{case} on {sorted(fams)}: outside the fp32 bound'
 
 
 def test_conv2d_f16x3_gru_and_segments():
