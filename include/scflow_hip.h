@@ -1148,8 +1148,14 @@ int scf_instance_norm_res_norm_grad(const float* g, const float* y, const float*
  * small, or M == 1 (no unbiased variance; torch raises there too): SCF_EINVAL.  M > 2^24 (the counts travel as floats) or
  * more than 2^31 - 1 blocks: SCF_EUNSUPPORTED.  Nothing is launched or written then.
  * Added without a version bump; the presence of scf_batch_norm_train marks the feature.
+ * scf_batch_norm_train_route (a host call, the launcher's own decision): what both entries launch for (N, C, HW) with
+ *   aligned != 0: every (N, C, HW) operand on a 16-byte boundary -> route[0] the statistics kernel (1, 4 or 16 float4 per
+ *   thread in registers; 0: the looped kernel), route[1] 1: float4 sweeps in every pass, 0: scalar, route[2] K chunks per
+ *   plane, route[3] apply blocks per plane (4096 elements each), route[4] groups of 64 partials per channel
+ *   (ceil(N K / 64)).  Returns SCF_OK, or the size's error code as above (route NULL: SCF_EINVAL) with route unwritten.
  * --------------------------------------------------------------------------------- */
 int64_t scf_batch_norm_train_workspace(int N, int C, int HW);
+int scf_batch_norm_train_route(int N, int C, int HW, int aligned, int* route);
 int scf_batch_norm_train(const float* u, const float* gamma, const float* beta, float* running_mean, float* running_var,
                          const float* res, const float* gamma_r, const float* beta_r, float* running_mean_r,
                          float* running_var_r, int relu, float momentum, float eps, float* y, float* saved, float* saved_r,
@@ -1217,9 +1223,16 @@ int scf_gru_gate_state(const float* h, int64_t h_stride, const float* gate, int6
  * A null g_corr / flow / g_vol, a non-positive size, r < 1, an empty level: SCF_EINVAL; L > SCF_MAX_LEVELS or
  * T > SCF_TAIL_MAX_T: SCF_EUNSUPPORTED; nothing launched or written.  Added without a version bump; the presence of
  * the symbol marks the feature.
+ * scf_corr_lookup_grad_route (a host call, the launcher's own decision): what a call with these sizes launches ->
+ *   route[0] 0: staged through LDS, 1: one thread per element; on the staged route route[1] the radius the kernel is
+ *   instantiated for (1 .. 4), route[2] log2 of the queries per block (0 .. 4: the largest whose staging, centres and
+ *   accumulators fit in 64 KB with at most 24 cotangents per thread), route[3] 1 when the last block holds fewer queries
+ *   than that (N h w is no multiple); on the other route 0, -1, 0.  Returns SCF_OK, or the sizes' error code as above
+ *   (route NULL: SCF_EINVAL) with route unwritten.
  * --------------------------------------------------------------------------------- */
 int scf_corr_lookup_grad(const float* g_corr, const float* flow, const float* mask, float* g_vol, int accumulate, int T,
                          int N, int h, int w, int r, int L, scf_stream_t stream);
+int scf_corr_lookup_grad_route(int N, int h, int w, int r, int L, int* route);
 
 /* ---------------------------------------------------------------------------------
  * Adjoint of scf_corr_build's level 0 with respect to the two feature maps (corr_build_grad.hip).  g_vol (N, hw, hw)

@@ -328,6 +328,7 @@ SIGNATURES = {
     'scf_instance_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
     'scf_instance_norm_res_norm_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, _fp, C.c_int64, C.c_int, C.c_float, _fp]),
     'scf_batch_norm_train_workspace': (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    'scf_batch_norm_train_route': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_batch_norm_train': (C.c_int, [_fp] * 10 + [C.c_int, C.c_float, C.c_float, _fp, _fp, _fp, _fp, C.c_int64, C.c_int,
                                        C.c_int, C.c_int, _fp]),
     'scf_batch_norm_train_grad': (C.c_int, [_fp] * 15 + [C.c_int, _fp, C.c_int64, C.c_int, C.c_int, C.c_int, _fp]),
@@ -339,6 +340,7 @@ SIGNATURES = {
     'scf_gru_gate_state': (C.c_int, [_fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, _fp, C.c_int64, C.c_int, C.c_int64,
                                      _fp]),
     'scf_corr_lookup_grad': (C.c_int, [_fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
+    'scf_corr_lookup_grad_route': (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_corr_build_grad': (C.c_int, [_fp, _fp, _fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, _fp]),
     'scf_convex_upsample': (C.c_int, [_fp, _fp, _fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                       C.c_float, C.c_float, _fp]),

@@ -375,12 +375,42 @@ int bnt_geometry(int N, int C, int HW, BntGeom& geo) {
 
 inline uintptr_t bnt_bits(const void* p) { return (uintptr_t)p; }
 
+// What the two entries launch, a function of (N, C, HW) and of the alignment class of the maps alone (aligned: every
+// (N, C, HW) operand on a 16-byte boundary).  The entries launch what it says and scf_batch_norm_train_route reports it.
+struct BntRoute {
+  BntGeom geo;
+  bool vec;    // the float4 sweeps of every pass
+  int stats;   // VEC4 of bnt_stats_kernel: 1, 4 or 16; 0: bnt_stats_loop_kernel
+};
+
+int bnt_route(int N, int C, int HW, bool aligned, BntRoute& rt) {
+  const int rc = bnt_geometry(N, C, HW, rt.geo);
+  if (rc != SCF_OK) return rc;
+  rt.vec = (HW % 4 == 0) && aligned;
+  const int n4 = (HW < BNT_CHUNK ? HW : BNT_CHUNK) / 4;
+  rt.stats = !rt.vec ? 0 : n4 <= 256 ? 1 : n4 <= 1024 ? 4 : 16;
+  return SCF_OK;
+}
+
 }  // namespace
 
 extern "C" int64_t scf_batch_norm_train_workspace(int N, int C, int HW) {
   BntGeom geo;
   const int rc = bnt_geometry(N, C, HW, geo);
   return rc != SCF_OK ? rc : 6 * geo.chunks;
+}
+
+extern "C" int scf_batch_norm_train_route(int N, int C, int HW, int aligned, int* route) {
+  if (!route) return SCF_EINVAL;
+  BntRoute rt;
+  const int rc = bnt_route(N, C, HW, aligned != 0, rt);
+  if (rc != SCF_OK) return rc;
+  route[0] = rt.stats;
+  route[1] = rt.vec;
+  route[2] = rt.geo.K;
+  route[3] = rt.geo.bpp;
+  route[4] = (int)scf_cdiv((int64_t)N * rt.geo.K, 64);   // groups of 64 partials a channel's N K partials fold in
+  return SCF_OK;
 }
 
 extern "C" int scf_batch_norm_train(const float* u, const float* gamma, const float* beta, float* running_mean,
@@ -398,19 +428,19 @@ extern "C" int scf_batch_norm_train(const float* u, const float* gamma, const fl
                         bnt_bits(gamma_r) | bnt_bits(beta_r) | bnt_bits(running_mean_r) | bnt_bits(running_var_r) |
                         bnt_bits(saved) | bnt_bits(saved_r) | bnt_bits(workspace);
   if (all & 3) return SCF_EINVAL;
-  BntGeom geo;
-  const int rc = bnt_geometry(N, C, HW, geo);
+  BntRoute rt;
+  const int rc = bnt_route(N, C, HW, (big & 15) == 0, rt);
   if (rc != SCF_OK) return rc;
+  const BntGeom& geo = rt.geo;
   if (workspace_floats < 6 * geo.chunks) return SCF_EINVAL;
   hipStream_t st = scf_stream(stream);
   const dim3 blk(BNT_NT), sgrid((unsigned)geo.chunks), agrid((unsigned)geo.blocks);
-  const bool vec = (HW % 4 == 0) && ((big & 15) == 0);
-  const int n4 = (HW < BNT_CHUNK ? HW : BNT_CHUNK) / 4;
+  const bool vec = rt.vec;
   float* ws_r = workspace + 3 * geo.chunks;
   auto stats = [&](const float* x, float* ws) {
-    if (vec && n4 <= 256) scf_launch((bnt_stats_kernel<1>), sgrid, blk, 0, st, x, ws, HW, geo.K);
-    else if (vec && n4 <= 1024) scf_launch((bnt_stats_kernel<4>), sgrid, blk, 0, st, x, ws, HW, geo.K);
-    else if (vec) scf_launch((bnt_stats_kernel<16>), sgrid, blk, 0, st, x, ws, HW, geo.K);
+    if (rt.stats == 1) scf_launch((bnt_stats_kernel<1>), sgrid, blk, 0, st, x, ws, HW, geo.K);
+    else if (rt.stats == 4) scf_launch((bnt_stats_kernel<4>), sgrid, blk, 0, st, x, ws, HW, geo.K);
+    else if (rt.stats == 16) scf_launch((bnt_stats_kernel<16>), sgrid, blk, 0, st, x, ws, HW, geo.K);
     else scf_launch(bnt_stats_loop_kernel, sgrid, blk, 0, st, x, ws, HW, geo.K);
   };
   stats(u, workspace);
@@ -444,13 +474,14 @@ extern "C" int scf_batch_norm_train_grad(const float* g, const float* y, const f
   const uintptr_t all = big | bnt_bits(saved) | bnt_bits(saved_r) | bnt_bits(gamma) | bnt_bits(gamma_r) | bnt_bits(dgamma) |
                         bnt_bits(dbeta) | bnt_bits(dgamma_r) | bnt_bits(dbeta_r) | bnt_bits(workspace);
   if (all & 3) return SCF_EINVAL;
-  BntGeom geo;
-  const int rc = bnt_geometry(N, C, HW, geo);
+  BntRoute rt;
+  const int rc = bnt_route(N, C, HW, (big & 15) == 0, rt);
   if (rc != SCF_OK) return rc;
+  const BntGeom& geo = rt.geo;
   if (workspace_floats < 6 * geo.chunks) return SCF_EINVAL;
   hipStream_t st = scf_stream(stream);
   const dim3 blk(BNT_NT), rgrid((unsigned)geo.chunks), agrid((unsigned)geo.blocks);
-  const bool vec = (HW % 4 == 0) && ((big & 15) == 0);
+  const bool vec = rt.vec;
 #define BNT_REDUCE(V, T, D) \
   scf_launch((bnt_grad_reduce_kernel<V, T, D>), rgrid, blk, 0, st, g, y, u, r, saved, saved_r, gp, workspace, C, HW, geo.K)
   if (vec) {

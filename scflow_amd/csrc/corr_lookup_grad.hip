@@ -237,14 +237,14 @@ __global__ __launch_bounds__(LG_THREADS) void corr_lookup_grad_plain_kernel(LgPa
   }
 }
 
-extern "C" int scf_corr_lookup_grad(const float* g_corr, const float* flow, const float* mask, float* g_vol,
-                                    int accumulate, int T, int N, int h, int w, int r, int L, scf_stream_t stream) {
-  if (!g_corr || !flow || !g_vol || T <= 0 || N <= 0 || h <= 0 || w <= 0 || L <= 0 || r < 1) return SCF_EINVAL;
+// The launch plan, a function of the sizes alone: the size checks, the level geometry and the route.  scf_corr_lookup_grad
+// launches what it says and scf_corr_lookup_grad_route reports it.  -> 1: the fast route (p.qb_log2, p.sstride set), 0: the
+// plain route, < 0: the error code of sizes the kernels do not take.  Fills N, h, w, r, L, total_q, lh, lw, soff of p.
+static int lg_plan(int T, int N, int h, int w, int r, int L, LgParams& p) {
+  if (T <= 0 || N <= 0 || h <= 0 || w <= 0 || L <= 0 || r < 1) return SCF_EINVAL;
   if (L > SCF_MAX_LEVELS || T > SCF_TAIL_MAX_T) return SCF_EUNSUPPORTED;
   if ((long long)h * w > 0x7fffffffLL || r > 16383) return SCF_EUNSUPPORTED;
-  LgParams p;
-  p.g = g_corr; p.flow = flow; p.mask = mask; p.out = g_vol;
-  p.accumulate = accumulate != 0; p.T = T; p.N = N; p.h = h; p.w = w; p.r = r; p.L = L;
+  p.T = T; p.N = N; p.h = h; p.w = w; p.r = r; p.L = L;
   p.total_q = (long long)N * h * w;
   if ((long long)h * w > 0x7fffffffffffLL / p.total_q) return SCF_EUNSUPPORTED;         // 64-bit element offsets of g_vol
   long long cells = 0;
@@ -271,8 +271,36 @@ extern "C" int scf_corr_lookup_grad(const float* g_corr, const float* flow, cons
   if (qb_log2 >= 0 && scf_cdiv(p.total_q, 1LL << qb_log2) <= 0x7fffffffLL) {
     p.qb_log2 = qb_log2;
     p.sstride = (int)sstride;
-    const int qb = 1 << qb_log2;
-    const size_t lds = ((size_t)K * qb + (size_t)sstride * qb) * sizeof(float) + (size_t)L * qb * sizeof(LgCentre);
+    return 1;
+  }
+  p.qb_log2 = 0; p.sstride = 0;
+  return 0;
+}
+
+extern "C" int scf_corr_lookup_grad_route(int N, int h, int w, int r, int L, int* route) {
+  if (!route) return SCF_EINVAL;
+  LgParams p;
+  const int fast = lg_plan(1, N, h, w, r, L, p);
+  if (fast < 0) return fast;
+  route[0] = fast ? 0 : 1;
+  route[1] = fast ? (r < 4 ? r : 4) : 0;
+  route[2] = fast ? p.qb_log2 : -1;
+  route[3] = fast && (p.total_q & ((1LL << p.qb_log2) - 1)) != 0;
+  return SCF_OK;
+}
+
+extern "C" int scf_corr_lookup_grad(const float* g_corr, const float* flow, const float* mask, float* g_vol,
+                                    int accumulate, int T, int N, int h, int w, int r, int L, scf_stream_t stream) {
+  if (!g_corr || !flow || !g_vol) return SCF_EINVAL;
+  LgParams p;
+  const int fast = lg_plan(T, N, h, w, r, L, p);
+  if (fast < 0) return fast;
+  p.g = g_corr; p.flow = flow; p.mask = mask; p.out = g_vol;
+  p.accumulate = accumulate != 0;
+  if (fast) {
+    const long long D = 2LL * r + 1, K = L * D * D;
+    const int qb = 1 << p.qb_log2;
+    const size_t lds = ((size_t)K * qb + (size_t)p.sstride * qb) * sizeof(float) + (size_t)L * qb * sizeof(LgCentre);
     const dim3 grid((unsigned)scf_cdiv(p.total_q, qb));
     switch (r) {
       case 1: scf_launch(corr_lookup_grad_kernel<1>, grid, dim3(LG_THREADS), lds, scf_stream(stream), p); break;
@@ -282,7 +310,6 @@ extern "C" int scf_corr_lookup_grad(const float* g_corr, const float* flow, cons
     }
     return scf_launch_status();
   }
-  p.qb_log2 = 0; p.sstride = 0;
   long long nb = scf_cdiv(p.total_q * h * w, LG_THREADS);
   if (nb > 262144) nb = 262144;
   scf_launch(corr_lookup_grad_plain_kernel, dim3((unsigned)nb), dim3(LG_THREADS), 0, scf_stream(stream), p);

@@ -1106,6 +1106,16 @@ def corr_lookup_grad(g_corr: Tensor, flow: Tensor, mask: Optional[Tensor] = None
     return out
 
 
+def corr_lookup_grad_route(n: int, h: int, w: int, radius: int = 4, num_levels: int = 4) -> dict:
+    """what ``corr_lookup_grad`` launches for these sizes (``scf_corr_lookup_grad_route``, the launcher's own decision; a
+    host call) -> dict(route 'fast' | 'plain', radius: the kernel's template radius (0 on the plain route), qb_log2: log2
+    of the queries per block (-1 on the plain route), ragged: the last block holds fewer queries)."""
+    r = (C.c_int * 4)()
+    _lib.check(_lib.load().scf_corr_lookup_grad_route(int(n), int(h), int(w), int(radius), int(num_levels), r),
+               'scf_corr_lookup_grad_route')
+    return dict(route=('fast', 'plain')[r[0]], radius=int(r[1]), qb_log2=int(r[2]), ragged=bool(r[3]))
+
+
 def corr_build_grad(g_vol: Tensor, feat1: Tensor, feat2: Tensor, out: Optional[Sequence[Optional[Tensor]]] = None
                     ) -> Tuple[Tensor, Tensor]:
     """Adjoint of ``corr_build``'s level 0 with respect to the two feature maps (``scf_corr_build_grad``): ``g_vol``
@@ -2699,6 +2709,17 @@ def instance_norm_grad(g: Tensor, u: Tensor, y: Optional[Tensor] = None, r: Opti
 def batch_norm_train_workspace(n: int, c: int, hw: int) -> int:
     """floats of workspace ``batch_norm_train`` / ``batch_norm_train_grad`` need (``scf_batch_norm_train_workspace``)."""
     return _workspace_floats('batch_norm_train_workspace', n, c, hw)
+
+
+def batch_norm_train_route(n: int, c: int, hw: int, aligned: bool = True) -> dict:
+    """what ``batch_norm_train`` / ``batch_norm_train_grad`` launch for (N, C, HW) maps, ``aligned``: all of them on 16-byte
+    boundaries (``scf_batch_norm_train_route``, the launcher's own decision; a host call) -> dict(stats: float4 per thread
+    of the statistics kernel, 1, 4 or 16, or 'loop'; vec: float4 sweeps; K: chunks per plane; bpp: apply blocks per plane;
+    groups: groups of 64 partials per channel)."""
+    r = (C.c_int * 5)()
+    _lib.check(_lib.load().scf_batch_norm_train_route(int(n), int(c), int(hw), int(bool(aligned)), r),
+               'scf_batch_norm_train_route')
+    return dict(stats=int(r[0]) or 'loop', vec=bool(r[1]), K=int(r[2]), bpp=int(r[3]), groups=int(r[4]))
 
 
 def _bnt_maps(what: str, shape, named: dict) -> dict:

@@ -40,7 +40,7 @@ HEADER = open(os.path.join(ROOT, 'include', 'scflow_hip.h')).read()
 F = torch.nn.functional
 EPS = float(np.float32(1e-5))
 MOMENTUM = 0.1
-SYMBOLS = ['scf_batch_norm_train_workspace', 'scf_batch_norm_train', 'scf_batch_norm_train_grad']
+SYMBOLS = ['scf_batch_norm_train_workspace', 'scf_batch_norm_train', 'scf_batch_norm_train_grad', 'scf_batch_norm_train_route']
 FORMS = ['mid', 'tail', 'tail_ds']
 CHUNK = 16384
 
@@ -48,8 +48,33 @@ CHUNK = 16384
 # blocks on the vector route; a plane beyond one chunk (two chunks, the second a partial one); more partials than a
 # butterfly's first level pairs up, odd N
 SHAPES = [(3, 5, 2, 3), (1, 2, 4, 4), (2, 3, 8, 12), (4, 64, 16, 16), (2, 2, 136, 132), (33, 2, 4, 4)]
+# every launch geometry of batch_norm_train.hip (ROUTE_WHY: what ops.batch_norm_train_route must say of each, which
+# test_route_coverage asserts): HW 1040 / 4096, the two ends of the 4-float4 statistics kernel, 4096 one full apply block;
+# HW 4100, the bottom of the 16-float4 kernel, a second apply block of 4 elements; HW 16384, one whole chunk, 4 full apply
+# blocks; HW 16388, a second chunk of 4 elements (one float4); HW 16389 / 16386, the looped kernel with a second chunk of 5 /
+# of 2 elements, 5 scalar apply blocks; P = N K = 65, 128, 129 partials: a second group of 64 with one entry, full, and a
+# third with one entry (HW 2: the scalar route); M = 2, the smallest count that has an unbiased variance
+SHAPES += [(2, 3, 20, 52), (1, 2, 64, 64), (2, 2, 25, 164), (1, 2, 128, 128), (1, 2, 4, 4097), (2, 2, 3, 5463), (1, 2, 1, 16386),
+           (65, 2, 2, 2), (128, 2, 1, 2), (129, 1, 1, 2), (1, 2, 1, 2)]
+ROUTE_WHY = {(2, 3, 20, 52): dict(stats=4, vec=True, K=1, bpp=1, groups=1),
+             (1, 2, 64, 64): dict(stats=4, vec=True, K=1, bpp=1, groups=1),
+             (2, 2, 25, 164): dict(stats=16, vec=True, K=1, bpp=2, groups=1),
+             (1, 2, 128, 128): dict(stats=16, vec=True, K=1, bpp=4, groups=1),
+             (1, 2, 4, 4097): dict(stats=16, vec=True, K=2, bpp=5, groups=1),
+             (2, 2, 3, 5463): dict(stats='loop', vec=False, K=2, bpp=5, groups=1),
+             (1, 2, 1, 16386): dict(stats='loop', vec=False, K=2, bpp=5, groups=1),
+             (65, 2, 2, 2): dict(stats=1, vec=True, K=1, bpp=1, groups=2),
+             (128, 2, 1, 2): dict(stats='loop', vec=False, K=1, bpp=1, groups=2),
+             (129, 1, 1, 2): dict(stats='loop', vec=False, K=1, bpp=1, groups=3),
+             (1, 2, 1, 2): dict(stats='loop', vec=False, K=1, bpp=1, groups=1),
+             (3, 2, 4, 4097): dict(stats=16, vec=True, K=2, bpp=5, groups=1)}
 REGIMES = ['nominal', 'offset', 'constant', 'channel_masked', 'gamma_zero']
 REGIME_SHAPE = (2, 3, 8, 12)
+# every regime again where a channel's moments are combined across chunks (K = 2, P = 6) and across groups (P = 65)
+REGIME_SHAPES = [REGIME_SHAPE, (3, 2, 4, 4097), (65, 2, 2, 2)]
+# planes that take the vector route, run again with every map 4 bytes off a 16-byte boundary: one scalar block; two scalar
+# apply blocks; the looped statistics kernel over two chunks
+UNALIGNED_SHAPES = [(2, 3, 8, 12), (2, 2, 25, 164), (1, 2, 4, 4097)]
 
 
 # ============================================================================================ layout and the float64 forms
@@ -297,7 +322,8 @@ def grad_args(case):
 
 
 ALL_CASES = ([(form, shape, 'nominal') for form in FORMS for shape in SHAPES]
-             + [(form, REGIME_SHAPE, regime) for form in FORMS for regime in REGIMES[1:]])
+             + [(form, shape, regime) for shape in REGIME_SHAPES for form in FORMS for regime in REGIMES
+                if regime != 'nominal' or shape not in SHAPES])
 
 
 def case_id(v):
@@ -357,6 +383,234 @@ def test_forms_equal_float64_torch_and_fp32_torch_falls_inside(case):
             worst = max(worst, worst_ratio(got[k], *ref[k]))
     measured(f'fp32 torch batch_norm(training=True) and autograd, {case_id(case)}: worst error / bound', worst)
     assert worst <= 1
+
+
+# ============================================================================= fp32 in the kernels' own operation order
+F32 = np.float32
+
+
+def _chain(terms):
+    """(B, n) fp32 -> (B, 256): thread t of the workgroup adds terms t, t + 256, ... to one chain from +0"""
+    b, n = terms.shape
+    its = -(-n // 256)
+    pad = np.zeros((b, its * 256), F32)
+    pad[:, :n] = terms
+    acc = np.zeros((b, 256), F32)
+    for i in range(its):
+        acc = acc + pad[:, i * 256:(i + 1) * 256]
+    return acc
+
+
+def _wave(v):
+    """(B, 64) -> (B,): v[l] += v[l ^ off] for off = 32, ..., 1 (bnt_wave_sum); every lane ends with the same bits"""
+    lanes = np.arange(64)
+    for off in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, lanes ^ off]
+    return v[:, 0]
+
+
+def _block(v):
+    """(B, 256) -> (B,): the four waves, then (w0 + w1) + (w2 + w3) (bnt_block_sum)"""
+    w = _wave(v.reshape(-1, 64)).reshape(-1, 4)
+    return (w[:, 0] + w[:, 1]) + (w[:, 2] + w[:, 3])
+
+
+def _quad(t):
+    """(B, 4 m) -> (B, m): a float4's terms as (a + b) + (c + d)"""
+    q = t.reshape(t.shape[0], -1, 4)
+    return (q[..., 0] + q[..., 1]) + (q[..., 2] + q[..., 3])
+
+
+def _chunk_sum(terms, vec):
+    return _block(_chain(_quad(terms) if vec else terms))
+
+
+def _chan32(a, b):
+    """bnt_chan on (..., 3) arrays of (count, mean, m2); a holds the lower partial indices"""
+    with np.errstate(all='ignore'):
+        n = a[..., 0] + b[..., 0]
+        d = b[..., 1] - a[..., 1]
+        f = b[..., 0] / n
+        r = np.stack([n, a[..., 1] + d * f, (a[..., 2] + b[..., 2]) + (d * d) * (a[..., 0] * f)], -1)
+    r = np.where((a[..., :1] == 0), b, r)
+    return np.where((b[..., :1] == 0), a, r).astype(F32)
+
+
+def _moments32(ws):
+    """ws (N, C, K, 3) -> (C, 3): bnt_channel_moments, groups of 64 partials p = n K + k in a tree whose lower lane is the
+    left operand at every level, the groups folded in ascending order"""
+    n, c, k, _ = ws.shape
+    part = np.moveaxis(ws, 1, 0).reshape(c, n * k, 3)
+    acc = np.zeros((c, 3), F32)
+    for p0 in range(0, n * k, 64):
+        m = np.zeros((c, 64, 3), F32)
+        m[:, :min(64, n * k - p0)] = part[:, p0:p0 + 64]
+        while m.shape[1] > 1:
+            m = _chan32(m[:, 0::2], m[:, 1::2])
+        acc = _chan32(acc, m[:, 0])
+    return acc
+
+
+def _stats32(x, vec, K):
+    """x (N, C, HW) fp32 -> the workspace (N, C, K, 3) of the statistics pass: per chunk the count, the mean, then the sum of
+    the squared differences from it"""
+    n, c, hw = x.shape
+    planes = x.reshape(n * c, hw)
+    ws = np.zeros((n * c, K, 3), F32)
+    for k in range(K):
+        ch = planes[:, k * CHUNK:(k + 1) * CHUNK]
+        cnt = F32(ch.shape[1])
+        mean = _chunk_sum(ch, vec) / cnt
+        a = ch - mean[:, None]
+        ws[:, k] = np.stack([np.full_like(mean, cnt), mean, _chunk_sum(a * a, vec)], -1)
+    return ws.reshape(n, c, K, 3)
+
+
+def _np32(t):
+    return np.ascontiguousarray(t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else t, dtype=F32)
+
+
+def bn_forward32(case, vec, K, momentum=MOMENTUM, eps=EPS):
+    """batch_norm_train.hip's forward with relu in numpy fp32, every operation rounded on its own, in the order of the
+    route (``vec``, ``K`` chunks per plane) -> dict keyed as bn_forward64"""
+    shape = tuple(case['u'].shape)
+    n, c, h, w = shape
+    mom, eps = F32(momentum), F32(eps)
+    one = F32(1)
+
+    def operand(x, gam, bet, rm, rv):
+        x = _np32(x).reshape(n, c, h * w)
+        m = _moments32(_stats32(x, vec, K))
+        mean = m[:, 1]
+        rstd = one / np.sqrt(m[:, 2] / m[:, 0] + eps)
+        keep, unb = one - mom, m[:, 2] / (m[:, 0] - one)
+        B = lambda v: _np32(v).reshape(1, c, 1)                    # noqa: E731
+        v = ((x - B(mean)) * B(rstd)) * B(gam) + B(bet)
+        return v, np.stack([mean, rstd]), keep * _np32(rm) + mom * mean, keep * _np32(rv) + mom * unb
+
+    with np.errstate(all='ignore'):
+        v, saved, rm, rv = operand(case['u'], case['gamma'], case['beta'], case['running_mean'], case['running_var'])
+        out = dict(saved=saved, running_mean=rm, running_var=rv)
+        if 'res_bn' in case:
+            v2, saved_r, rm2, rv2 = operand(case['res'], *case['res_bn'])
+            v = v + v2
+            out.update(saved_r=saved_r, running_mean_r=rm2, running_var_r=rv2)
+        elif 'res' in case:
+            v = v + _np32(case['res']).reshape(n, c, h * w)
+        out['y'] = np.where(v > 0, v, F32(0)).reshape(shape)
+    assert all(v.dtype == F32 for v in out.values())
+    return out
+
+
+def bn_grad32(case, fwd, vec, K):
+    """batch_norm_train.hip's backward in numpy fp32 on the forward ``fwd`` (its saved statistics; the mask is read from
+    ``case['y']``) -> dict keyed as bn_grad64"""
+    shape = tuple(case['u'].shape)
+    n, c, h, w = shape
+    hw = h * w
+    flat = lambda v: _np32(v).reshape(n, c, hw)                    # noqa: E731
+    B = lambda v: _np32(v).reshape(1, c, 1)                        # noqa: E731
+    g, u = flat(case['g']), flat(case['u'])
+    tail, ds = 'res' in case, 'res_bn' in case
+    with np.errstate(all='ignore'):
+        gm = np.where(flat(case['y']) > 0, g, F32(0)) if tail else g
+        ops_ = [(u, fwd['saved'], case['gamma'])] + ([(flat(case['res']), fwd['saved_r'], case['res_bn'][0])] if ds else [])
+        xh = [(x - B(sv[0])) * B(sv[1]) for x, sv, _ in ops_]
+        ws = np.zeros((n * c, K, 3), F32)
+        for k in range(K):
+            sl = slice(k * CHUNK, (k + 1) * CHUNK)
+            terms = [gm[..., sl]] + [gm[..., sl] * t[..., sl] for t in xh]
+            for j, t in enumerate(terms):
+                ws[:, k, j] = _chunk_sum(t.reshape(n * c, -1), vec)
+        part = np.moveaxis(ws.reshape(n, c, K, 3), 1, 0).reshape(c, n * K, 3)
+        its = -(-(n * K) // 64)
+        pad = np.zeros((c, its * 64, 3), F32)
+        pad[:, :n * K] = part
+        acc = np.zeros((c, 64, 3), F32)
+        for i in range(its):                                        # lane l adds p = l, l + 64, ... to one chain from +0
+            acc = acc + pad[:, i * 64:(i + 1) * 64]
+        s = np.stack([_wave(acc[..., j]) for j in range(3)], -1)    # (C, 3)
+        M = F32(n * hw)
+        m1 = s[:, 0] / M
+
+        def grad(x_hat, sv, gam, s2):
+            return ((gm - B(m1)) - x_hat * B(s2 / M)) * B(_np32(gam) * sv[1])
+
+        out = dict(du=grad(xh[0], fwd['saved'], case['gamma'], s[:, 1]).reshape(shape), dgamma=s[:, 1], dbeta=s[:, 0])
+        if tail and not ds:
+            out['gp'] = gm.reshape(shape)
+        if ds:
+            out.update(dr=grad(xh[1], fwd['saved_r'], case['res_bn'][0], s[:, 2]).reshape(shape), dgamma_r=s[:, 2], dbeta_r=s[:, 0])
+    assert all(v.dtype == F32 for v in out.values())
+    return out
+
+
+def kernel_order_case(case, form, vec, K):
+    """``case`` with y, and the mid form's mask, taken from the fp32 forward in the kernel's order, as the encoder has them
+    -> (case, that forward)"""
+    fwd = bn_forward32(case, vec, K)
+    case = dict(case, y=torch.from_numpy(fwd['y']))
+    if form == 'mid':
+        case['g'] = torch.where(case['y'] > 0, _rand(tuple(case['u'].shape), 99), torch.zeros(()))
+    return case, fwd
+
+
+ORDER_CASES = [(c, True) for c in ALL_CASES] + [((form, shape, 'nominal'), False) for form in FORMS for shape in UNALIGNED_SHAPES]
+
+
+@pytest.mark.parametrize('case, aligned', ORDER_CASES, ids=lambda v: case_id(v) if isinstance(v, tuple) else ('aligned' if v else 'off16'))
+def test_fp32_in_the_kernels_order_is_inside_the_bound(case, aligned):
+    """the forward and the backward restated in fp32 in the order of the route the library itself names for the shape
+    (ops.batch_norm_train_route, a host call), against float64 and the bound at that route's depth"""
+    from scflow_amd import ops
+    form, shape, regime = case
+    n, ch, h, w = shape
+    route = ops.batch_norm_train_route(n, ch, h * w, aligned)
+    assert route['vec'] == (aligned and h * w % 4 == 0) and route['K'] == -(-h * w // CHUNK) and route['groups'] == -(-n * route['K'] // 64)
+    c, fwd = kernel_order_case(bn_case(form, shape, regime=regime), form, route['vec'], route['K'])
+    got = bn_grad32(c, fwd, route['vec'], route['K'])
+    depths = bn_depths(n, h * w, aligned)
+    fref = bn_forward_ref(**forward_args(c), relu=True, depths=depths)
+    gref = bn_grad_ref(**grad_args(c), depths=depths)
+    assert sorted(fwd) == sorted(fref) and sorted(got) == sorted(gref)
+    worst = {k: worst_ratio(have[k], *ref[k]) for have, ref in ((fwd, fref), (got, gref)) for k in ref}
+    measured(f'fp32 in the kernel\'s order, {case_id(case)} {"aligned" if aligned else "4 bytes off"}: worst error / bound',
+             max(worst.values()))
+    assert max(worst.values()) <= 1, worst
+    assert all(np.isfinite(v).all() for v in list(fwd.values()) + list(got.values()))
+
+
+def test_route_coverage():
+    """the library's own route decision over every case the kernel tests run (tests/test_gpu_bn_train.py runs ALL_CASES
+    aligned and UNALIGNED_SHAPES 4 bytes off): each added shape lands where it was put, and every statistics kernel, float4
+    and scalar sweeps, one and several chunks per plane, one and several apply blocks per plane, one and several groups of
+    partials are each reached by a case of each form"""
+    from scflow_amd import ops
+    route = lambda shape, aligned=True: ops.batch_norm_train_route(shape[0], shape[1], shape[2] * shape[3], aligned)   # noqa: E731
+    for shape, want in ROUTE_WHY.items():
+        assert shape in [s for _, s, _ in ALL_CASES] and route(shape) == want, (shape, route(shape))
+    assert [route(s, False) for s in UNALIGNED_SHAPES] == [dict(stats='loop', vec=False, K=1, bpp=1, groups=1),
+                                                          dict(stats='loop', vec=False, K=1, bpp=2, groups=1),
+                                                          dict(stats='loop', vec=False, K=2, bpp=5, groups=1)]
+    for form in FORMS:
+        seen = [route(s) for f, s, _ in ALL_CASES if f == form] + [route(s, False) for s in UNALIGNED_SHAPES]
+        for key, values in (('stats', (1, 4, 16, 'loop')), ('vec', (True, False))):
+            assert {r[key] for r in seen} == set(values), (form, key)
+        for key in ('K', 'bpp', 'groups'):
+            assert {min(r[key], 2) for r in seen} == {1, 2}, (form, key)
+        # the combinations a single property does not pin down
+        has = lambda **kw: any(all(r[k] == v if k in ('stats', 'vec') else (r[k] > 1) == v for k, v in kw.items()) for r in seen)  # noqa: E731
+        assert has(vec=False, bpp=True) and has(vec=True, bpp=True) and has(stats='loop', K=True) and has(stats=16, K=True)
+        assert has(vec=False, groups=True) and has(vec=True, groups=True)
+    # the regimes meet the combination across chunks and across groups
+    for regime in REGIMES:
+        seen = [route(s) for _, s, r in ALL_CASES if r == regime]
+        assert any(r['K'] > 1 for r in seen) and any(r['groups'] > 1 for r in seen), regime
+    # a size the kernels do not take is the entries' own error code
+    from scflow_amd._lib import ScflowHipError
+    for bad in ((1, 1, 1, 1), (0, 1, 2, 2), (2 ** 10, 1, 1, 2 ** 15)):
+        with pytest.raises(ScflowHipError):
+            route(bad)
 
 
 def test_bound_is_tight_where_it_matters():

@@ -151,10 +151,10 @@ def test_forms_against_float64(case):
     assert all(same_bits(acc[k], got[k] + base[k]) for k in vec) and all(same_bits(acc[k], got[k]) for k in got if k not in vec)
 
 
-@pytest.mark.parametrize('form', BH.FORMS)
-def test_unaligned_pointers_take_the_scalar_route(form):
-    """a plane size that would take the vector route, every map 4 bytes off a 16-byte boundary"""
-    shape = (2, 3, 8, 12)
+def unaligned_case(form, shape):
+    """a plane size that would take the vector route, every map 4 bytes off a 16-byte boundary -> worst error / bound"""
+    assert ops.batch_norm_train_route(shape[0], shape[1], shape[2] * shape[3], True)['vec']
+    assert not ops.batch_norm_train_route(shape[0], shape[1], shape[2] * shape[3], False)['vec']
     case = kernel_case(form, shape, 'nominal')
     off = lambda v: torch.empty((v.numel() + 1,), device=DEV)[1:].view(v.shape).copy_(v)      # noqa: E731
     u, g = off(case['u']), off(case['g'])
@@ -176,8 +176,21 @@ def test_unaligned_pointers_take_the_scalar_route(form):
     gref = BH.bn_grad_ref(**BH.grad_args(case), depths=depths)
     names = dict(mid=['du'], tail=['gp', 'du'], tail_ds=['du', 'dr'])[form] + ['dgamma', 'dbeta']
     worst = max([worst] + [worst_ratio(cpu(v), *gref[k]) for k, v in zip(names, got)])
-    measured(f'batch_norm_train {form} 8x12 unaligned: worst error / bound', worst)
-    assert worst <= 1.0
+    measured(f'batch_norm_train {form} {shape[2]}x{shape[3]} unaligned: worst error / bound', worst)
+    return worst
+
+
+@pytest.mark.parametrize('form', BH.FORMS)
+def test_unaligned_pointers_take_the_scalar_route(form):
+    assert unaligned_case(form, (2, 3, 8, 12)) <= 1.0
+
+
+@pytest.mark.parametrize('form', BH.FORMS)
+@pytest.mark.parametrize('shape', BH.UNALIGNED_SHAPES[1:], ids=lambda s: 'x'.join(map(str, s)))
+def test_unaligned_pointers_at_two_apply_blocks_and_two_chunks(shape, form):
+    """HW 4100: two scalar apply blocks, the second of 4 elements; HW 16388: the looped statistics kernel over two chunks,
+    the second of 4 elements"""
+    assert unaligned_case(form, shape) <= 1.0
 
 
 def test_running_statistics_after_two_forwards_match_torch():

@@ -42,12 +42,9 @@ def guards_intact(buf):
 
 
 # ===================================================================================================== the lookup adjoint
-# (N, T, h, w, r, L).  8 x 8: levels 8, 4, 2, 1 -- both axes flat at level 3; 12 x 20: 12 x 20, 6 x 10, 3 x 5, 1 x 2 -- a flat
-# y axis, dropped rows and a dropped column; 16 queries a block there.  32 x 32: a query's accumulators take 5.4 KB, so a
-# block holds 8 queries.  r = 5: the plain route (one thread per element), which r <= 4 reaches only with maps whose
-# accumulators exceed 64 KB a query.
-KERNEL_SHAPES = [(2, 2, 8, 8, 4, 4), (1, 1, 8, 8, 4, 4), (2, 2, 12, 20, 4, 4), (1, 1, 12, 20, 4, 4), (2, 2, 8, 8, 3, 2),
-                 (1, 1, 12, 20, 3, 2), (1, 1, 32, 32, 4, 4), (2, 2, 8, 8, 5, 2), (1, 2, 5, 7, 5, 3)]
+# (N, T, h, w, r, L): every launch geometry of corr_lookup_grad.hip, listed and explained next to the restatement;
+# tests/test_motion_grad_host.py::test_lookup_route_coverage holds the list to the library's own route decision
+KERNEL_SHAPES = MH.KERNEL_SHAPES
 
 
 def _run(g_corr, fl, mask, r, L, prev=None):
@@ -59,14 +56,15 @@ def _run(g_corr, fl, mask, r, L, prev=None):
 
 
 @pytest.mark.parametrize('with_mask', [False, True], ids=['plain', 'masked'])
-@pytest.mark.parametrize('shape', KERNEL_SHAPES, ids=lambda s: 'N{}T{}-{}x{}-r{}L{}'.format(*s))
+@pytest.mark.parametrize('shape', KERNEL_SHAPES, ids=MH.shape_id)
 def test_lookup_adjoint_against_float64(shape, with_mask):
     n, T, h, w, r, L = shape
     g_corr, fl, mask = MH.adjoint_case(n, T, h, w, r, L, with_mask=with_mask)
-    ref, bound = MH.lookup_adjoint(g_corr, fl, mask, r, L)
+    rows = MH.kernel_rows(shape)        # the two largest maps: a few hundred rows restated, every row in the checks below
+    ref, bound = MH.lookup_adjoint(g_corr, fl, mask, r, L, rows=rows)
     got = _run(g_corr, fl, mask, r, L)
     assert bool(torch.isfinite(got).all())
-    v = worst_ratio(cpu(got), ref, bound)
+    v = worst_ratio(cpu(got if rows is None else got[torch.from_numpy(rows).to(DEV)]), ref, bound)
     measured(f'corr_lookup_grad {shape} mask {with_mask}, worst error / bound', v)
     assert v <= 1.0
     assert same_bits(got, _run(g_corr, fl, mask, r, L)), 'two runs differ'
@@ -89,6 +87,24 @@ def test_lookup_adjoint_against_float64(shape, with_mask):
     if n == 2:                                                          # a sample alone == the same sample inside the batch
         one = _run(g_corr[:, 1:], fl[:, 1:], None if mask is None else mask[:, 1:], r, L)
         assert same_bits(one, got[h * w:])
+
+
+@pytest.mark.parametrize('with_mask', [False, True], ids=['plain', 'masked'])
+@pytest.mark.parametrize('shape', MH.EXACT_SHAPES, ids=MH.shape_id)
+def test_lookup_adjoint_on_exact_operands_bit_for_bit(shape, with_mask):
+    """operands on which no operation rounds (MH.exact_case; the host test shows fp32 == float64 on them): the kernel's
+    bits are float64's, on each route, so a cell that gathers a wrong tap, level or query cannot hide inside a bound"""
+    n, T, h, w, r, L = shape
+    g_corr, fl, mask = MH.exact_case(n, T, h, w, r, L, with_mask=with_mask)
+    ref, _ = MH.lookup_adjoint(g_corr, fl, mask, r, L)
+    want = torch.from_numpy(ref.astype(np.float32))
+    assert np.array_equal(f64(want), ref)
+    got = _run(g_corr, fl, mask, r, L)
+    wrong = int((cpu(got).view(torch.int32) != want.view(torch.int32)).sum())
+    measured(f'corr_lookup_grad {shape} mask {with_mask} on exact operands, elements whose bits differ', wrong)
+    assert wrong == 0
+    prev = D(torch.randint(-8, 9, (n * h * w, h, w), generator=MH.gen(12)).float())       # previous + result: exact too
+    assert same_bits(_run(g_corr, fl, mask, r, L, prev=prev), prev + D(want))
 
 
 def test_a_single_iteration_may_come_without_the_leading_axis():

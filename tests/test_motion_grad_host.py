@@ -67,15 +67,18 @@ ADJOINT_DEFECTS = ['a_b_swapped', 'ne_sw_swapped', 'half_per_level', 'odd_not_dr
                    'iteration_missing', 'mask_not_applied']
 
 
-def lookup_adjoint(g_corr, flows, mask, r, L, mode='64', prev=None, defect=None):
+def lookup_adjoint(g_corr, flows, mask, r, L, mode='64', prev=None, defect=None, rows=None):
     """scf_corr_lookup_grad restated in the gather form.  g_corr (T, N, L D D, h, w), flows (T, N, 2, h, w), mask None or
     (T, N, 1, h, w), prev None or (N h w, h, w): what the call accumulates into.  mode '64': float64 -> (g_vol, bound);
-    mode '32': fp32 in the header's order, every fma and product rounded once -> g_vol."""
+    mode '32': fp32 in the header's order, every fma and product rounded once -> g_vol.  ``rows``: the queries (rows of
+    g_vol) to restate, in that order; a query's row depends on that query alone."""
     g = g_corr.detach().cpu().numpy() if isinstance(g_corr, torch.Tensor) else np.asarray(g_corr)
     T, N, K, h, w = g.shape
     D = 2 * r + 1
     assert K == L * D * D
-    Q = N * h * w
+    sel = np.arange(N * h * w) if rows is None else np.asarray(rows, dtype=np.int64)
+    assert sel.ndim == 1 and sel.size and 0 <= sel.min() and sel.max() < N * h * w
+    full, Q = N * h * w, sel.size
     hi = mode == '64'
     dt = np.float64 if hi else F32
     S = [np.zeros((Q, h >> l, w >> l), dt) for l in range(L)]
@@ -85,14 +88,15 @@ def lookup_adjoint(g_corr, flows, mask, r, L, mode='64', prev=None, defect=None)
         for t in range(T):
             if defect == 'iteration_missing' and t == T - 1:
                 continue
-            G = np.ascontiguousarray(g[t].astype(F32).transpose(0, 2, 3, 1)).reshape(Q, L, D, D)
+            G = np.ascontiguousarray(g[t].astype(F32).transpose(0, 2, 3, 1)).reshape(full, L, D, D)[sel]
             if mask is not None and defect != 'mask_not_applied':
-                m = (mask[t].detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask[t])).astype(F32).reshape(Q, 1, 1, 1)
+                m = (mask[t].detach().cpu().numpy() if isinstance(mask, torch.Tensor) else np.asarray(mask[t])).astype(F32).reshape(full, 1, 1, 1)[sel]
                 G = m.astype(np.float64) * G.astype(np.float64) if hi else m * G
             G = G.astype(dt)
             for l in range(L):
                 lh, lw = h >> l, w >> l
                 x0, y0, wt, bad = lk_centre32(flows[t], l, lh, lw, r, defect)
+                x0, y0, bad, wt = x0[sel], y0[sel], bad[sel], {n_: v[sel] for n_, v in wt.items()}
                 if defect == 'ne_sw_swapped':
                     wt = dict(wt, ne=wt['sw'], sw=wt['ne'])
                 Gl = G[:, l].transpose(0, 2, 1) if defect == 'a_b_swapped' else G[:, l]
@@ -133,9 +137,10 @@ def lookup_adjoint(g_corr, flows, mask, r, L, mode='64', prev=None, defect=None)
                 v = np.where(valid, fma32(np.full(v.shape, F32(scale)), S[l][:, iy, ix], v), v)
         if prev is not None:
             pv = prev.detach().cpu().numpy() if isinstance(prev, torch.Tensor) else np.asarray(prev)
-            v = v + pv.astype(dt).reshape(v.shape)
+            pv = pv.reshape(full, h, w)[sel]
+            v = v + pv.astype(dt)
             if hi:
-                bound += gamma(max(d)) * np.abs(pv.astype(np.float64).reshape(v.shape))
+                bound += gamma(max(d)) * np.abs(pv.astype(np.float64))
     return (v, bound) if hi else v
 
 
@@ -204,6 +209,151 @@ def adjoint_case(n, T, h, w, r, L, with_mask=True, kinds=FLOW_KINDS, seed=0, dya
     return g_corr, fl, mask
 
 
+def exact_case(n, T, h, w, r, L, with_mask=True, seed=0):
+    """operands on which every intermediate of the adjoint is an fp32 number, so that any order of evaluation and float64
+    give the same bits: flows at multiples of 1 / 4 (whole numbers among them) reaching past every edge of the map,
+    cotangents whole numbers in [-3, 3], masks in {0, 1 / 2, 1}.  A centre at level l is a multiple of 2^-(l + 2), a weight
+    a multiple of 2^-(2 l + 4), a masked cotangent of 1 / 2, the fold's 4^-l exact: every term and partial sum of g_vol is a
+    multiple of 2^-(4 l + 5), 2^-17 at l = 3.  The four weights of a pass sum to 1, so a pass adds at most 3 in magnitude and
+    |g_vol| <= 3 T sum_l 4^-l (passes at l) < 2^5 for T <= 2 even with (2r + 1)^2 = 121 passes at l = 3: 22 bits.
+    test_exact_operands_leave_no_rounding does not take this on trust, it compares the fp32 evaluation with float64's bit
+    for bit."""
+    g = gen(9100 + seed + n + 3 * T + 5 * h + 7 * w + 11 * r)
+    K = L * (2 * r + 1) ** 2
+    g_corr = torch.randint(-3, 4, (T, n, K, h, w), generator=g).float()
+    reach = 4 * (r + 3)
+    fl = torch.randint(-reach, reach + 1, (T, n, 2, h, w), generator=g).float() / 4
+    mask = torch.randint(0, 3, (T, n, 1, h, w), generator=g).float() / 2 if with_mask else None
+    return g_corr, fl, mask
+
+
+# (N, T, h, w, r, L), the launches of corr_lookup_grad.hip that tests/test_gpu_motion_grad.py runs.  8 x 8: levels 8, 4, 2,
+# 1 -- both axes flat at level 3; 12 x 20: 12 x 20, 6 x 10, 3 x 5, 1 x 2 -- a flat y axis, dropped rows and a dropped column; 16
+# queries a block there.  32 x 32: a query's accumulators take 5.4 KB, so a block holds 8 queries.  r = 5: the plain route (one
+# thread per element), which r <= 4 reaches only with maps whose accumulators exceed 64 KB a query.
+KERNEL_SHAPES = [(2, 2, 8, 8, 4, 4), (1, 1, 8, 8, 4, 4), (2, 2, 12, 20, 4, 4), (1, 1, 12, 20, 4, 4), (2, 2, 8, 8, 3, 2),
+                 (1, 1, 12, 20, 3, 2), (1, 1, 32, 32, 4, 4), (2, 2, 8, 8, 5, 2), (1, 2, 5, 7, 5, 3)]
+# the other launch geometries (what ops.corr_lookup_grad_route must say of each, which test_lookup_route_coverage
+# asserts): the radius 1 and 2 instances; 35 and 27 queries, a last block of 3 and of 11 whose other lanes serve no query,
+# the second without a fold (L = 1); 8 queries a block because a thread holds at most 24 cotangents (L = 5), not for want of
+# LDS; 4, 2 and 1 queries a block (a query's accumulators take 9.9, 18 and 33 KB); the plain route with a flat y axis and
+# dropped rows
+NEW_KERNEL_SHAPES = {(1, 1, 8, 8, 1, 4): dict(route='fast', radius=1, qb_log2=4, ragged=False),
+                     (2, 2, 12, 20, 2, 3): dict(route='fast', radius=2, qb_log2=4, ragged=False),
+                     (1, 2, 5, 7, 4, 3): dict(route='fast', radius=4, qb_log2=4, ragged=True),
+                     (3, 1, 3, 3, 2, 1): dict(route='fast', radius=2, qb_log2=4, ragged=True),
+                     (1, 1, 16, 16, 4, 5): dict(route='fast', radius=4, qb_log2=3, ragged=False),
+                     (1, 1, 40, 40, 4, 4): dict(route='fast', radius=4, qb_log2=2, ragged=False),
+                     (1, 1, 56, 56, 4, 4): dict(route='fast', radius=4, qb_log2=1, ragged=False),
+                     (1, 1, 76, 78, 4, 4): dict(route='fast', radius=4, qb_log2=0, ragged=False),
+                     (1, 1, 12, 20, 5, 4): dict(route='plain', radius=0, qb_log2=-1, ragged=False)}
+KERNEL_SHAPES += list(NEW_KERNEL_SHAPES)
+# one per route, and the fast route with a ragged last block
+EXACT_SHAPES = [(2, 2, 12, 20, 4, 4), (1, 2, 5, 7, 4, 3), (1, 2, 5, 7, 5, 3)]
+
+
+def shape_id(s):
+    return 'N{}T{}-{}x{}-r{}L{}'.format(*s)
+
+
+def kernel_rows(shape):
+    """the queries of a kernel shape that are restated: all of them, or on the two largest maps a few hundred -- the first
+    and the last 32 (at least a whole first and last block), adjoint_case's special queries (flat index below 3 T + 41) and
+    every 23rd"""
+    n, T, h, w, _, _ = shape
+    q = n * h * w
+    if q < 3000:
+        return None
+    return np.unique(np.concatenate([np.arange(max(32, 3 * T + 41)), np.arange(0, q, 23), np.arange(q - 32, q)]))
+
+
+def test_lookup_route_coverage():
+    """the library's own route decision (ops.corr_lookup_grad_route, a host call) over KERNEL_SHAPES: each added shape
+    lands where it was put, and every radius instance, every block size, a ragged and a whole last block and the plain
+    route are each reached"""
+    from scflow_amd import _lib, ops
+    route = lambda s: ops.corr_lookup_grad_route(s[0], s[2], s[3], s[4], s[5])        # noqa: E731
+    for shape, want in NEW_KERNEL_SHAPES.items():
+        assert shape in KERNEL_SHAPES and route(shape) == want, (shape, route(shape))
+    seen = [route(s) for s in KERNEL_SHAPES]
+    fast = [r for r in seen if r['route'] == 'fast']
+    assert {r['radius'] for r in fast} == {1, 2, 3, 4} and {r['qb_log2'] for r in fast} == {0, 1, 2, 3, 4}
+    assert {r['ragged'] for r in fast} == {True, False} and any(r['route'] == 'plain' for r in seen)
+    assert any(r['route'] == 'plain' and s[5] == 4 and s[2] >> 3 == 1 for s, r in zip(KERNEL_SHAPES, seen))   # a flat y axis there
+    assert any(s[5] == 1 and r['ragged'] for s, r in zip(KERNEL_SHAPES, seen))                               # no fold
+    # 8 queries a block by the register cap: 16 of them would fit in LDS
+    s = (1, 1, 16, 16, 4, 5)
+    cells = sum((s[2] >> l) * (s[3] >> l) for l in range(5)) | 1
+    assert (5 * 81 * 16 + cells * 16) * 4 + 5 * 16 * 32 <= 64 * 1024 and -(-5 * 81 * 16 // 256) > 24 >= -(-5 * 81 * 8 // 256)
+    assert all(route(e)['route'] == want for e, want in zip(EXACT_SHAPES, ('fast', 'fast', 'plain'))) and route(EXACT_SHAPES[1])['ragged']
+    # sizes the kernels do not take are the entry's own error codes
+    for bad in ((0, 1, 8, 8, 4, 4), (1, 1, 8, 8, 0, 4), (1, 1, 8, 8, 4, 5), (1, 1, 8, 8, 4, _lib.MAX_LEVELS + 1)):
+        with pytest.raises(_lib.ScflowHipError):
+            route(bad)
+
+
+@pytest.mark.parametrize('shape', KERNEL_SHAPES, ids=shape_id)
+def test_adjoint_case_plants_two_nonfinite_queries_an_iteration(shape):
+    n, T, h, w, r, L = shape
+    _, fl, _ = adjoint_case(n, T, h, w, r, L)
+    bad = ~torch.isfinite(fl).all(2)
+    assert int(bad.sum()) == 2 * T and all(int(bad[t].sum()) == 2 for t in range(T))
+
+
+@pytest.mark.parametrize('shape', list(NEW_KERNEL_SHAPES), ids=shape_id)
+def test_fp32_in_the_stated_order_at_every_kernel_shape(shape):
+    n, T, h, w, r, L = shape
+    rows = kernel_rows(shape)
+    g_corr, fl, mask = adjoint_case(n, T, h, w, r, L)
+    ref, bound = lookup_adjoint(g_corr, fl, mask, r, L, rows=rows)
+    got = lookup_adjoint(g_corr, fl, mask, r, L, mode='32', rows=rows)
+    assert np.isfinite(ref).all() and np.isfinite(got).all() and ref.any()
+    assert (rows is None) == (h < 50) and (rows is None or 200 <= len(rows) <= 400)
+    v = worst_ratio(got, ref, bound)
+    measured(f'lookup adjoint in fp32 {shape}: worst error / bound', v)
+    assert v <= 1.0
+
+
+def test_a_selection_of_rows_is_those_rows():
+    n, T, h, w, r, L = 2, 2, 12, 20, 4, 4
+    g_corr, fl, mask = adjoint_case(n, T, h, w, r, L)
+    prev = torch.randn((n * h * w, h, w), generator=gen(5))
+    rows = [479, 0, 38, 240, 17]
+    for mode in ('64', '32'):
+        whole = lookup_adjoint(g_corr, fl, mask, r, L, mode=mode, prev=prev)
+        part = lookup_adjoint(g_corr, fl, mask, r, L, mode=mode, prev=prev, rows=rows)
+        for a, b in zip(whole if mode == '64' else (whole,), part if mode == '64' else (part,)):
+            assert b.shape == (5, h, w) and np.array_equal(a[rows], b, equal_nan=True)
+
+
+@pytest.mark.parametrize('with_mask', [False, True], ids=['plain', 'masked'])
+@pytest.mark.parametrize('shape', EXACT_SHAPES, ids=shape_id)
+def test_exact_operands_leave_no_rounding(shape, with_mask):
+    """on exact_case the fp32 evaluation in the header's order and float64 give the same numbers, bit for bit, with a zero
+    error bound only where the value is zero: the kernel's result on these operands is then one set of bits, whatever
+    order it sums in, and a wrong tap, level or query shows"""
+    n, T, h, w, r, L = shape
+    g_corr, fl, mask = exact_case(n, T, h, w, r, L, with_mask=with_mask)
+    assert (fl * 4 == torch.round(fl * 4)).all() and (fl == torch.round(fl)).any() and (fl != torch.round(fl)).any()
+    ref, _ = lookup_adjoint(g_corr, fl, mask, r, L)
+    got = lookup_adjoint(g_corr, fl, mask, r, L, mode='32')
+    assert got.dtype == F32 and np.array_equal(ref.astype(F32).astype(np.float64), ref)
+    assert np.array_equal(ref.astype(F32).view(np.int32), got.view(np.int32))
+    # the case is not degenerate: most cells of most rows are non-zero and take many distinct values, on every level
+    assert (ref != 0).mean() > 0.2 and len(np.unique(ref)) > 100
+    D = 2 * r + 1
+    for l in range(L):
+        only = g_corr.clone()
+        only[:, :, :l * D * D], only[:, :, (l + 1) * D * D:] = 0, 0
+        assert lookup_adjoint(only, fl, mask, r, L)[0].any(), l
+    # and a defect of the indexing changes bits
+    for defect in ('a_b_swapped', 'ne_sw_swapped', 'odd_not_dropped', 'iteration_missing'):
+        if defect == 'odd_not_dropped' and all((h >> l) * 2 == (h >> (l - 1)) and (w >> l) * 2 == (w >> (l - 1)) for l in range(1, L)):
+            continue
+        bad = lookup_adjoint(g_corr, fl, mask, r, L, mode='32', defect=defect)
+        assert not np.array_equal(bad, got), defect
+
+
 def test_symbols_are_declared_exported_and_bound():
     import scflow_amd
     from scflow_amd import _lib, ops
@@ -213,6 +363,8 @@ def test_symbols_are_declared_exported_and_bound():
     assert re.search(r'\bint\s+scf_corr_lookup_grad\s*\(', text)
     assert 'scf_corr_lookup_grad' in _lib.SIGNATURES and hasattr(_lib.load(), 'scf_corr_lookup_grad')
     assert len(_lib.SIGNATURES['scf_corr_lookup_grad'][1]) == 12
+    assert re.search(r'\bint\s+scf_corr_lookup_grad_route\s*\(', text) and hasattr(_lib.load(), 'scf_corr_lookup_grad_route')
+    assert callable(ops.corr_lookup_grad_route)
     assert callable(ops.corr_lookup_grad) and callable(MotionEncoder.backward) and callable(MotionEncoder.branches)
     assert callable(SCFlowDecoder.motion_backward) and callable(SCFlowRefiner.loss_and_motion_grads)
     dec = scflow_amd.build_refiner(scflow_amd.scflow_model_cfg(iters=2)).decoder
